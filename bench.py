@@ -12,10 +12,21 @@ T5-shaped prompt [1,256,4096] with the first 16 tokens valid. One "step" = one m
 forward + backward (train_step); every 16th step also runs the DP gradient all-reduce and the
 AdamW update (gradient_accumulation_steps 16, train-avatars.yaml:23), inside the timed region.
 
-Prints ONE JSON line (rank 0): value = samples/s summed over ranks (= tokens/s / 1792), plus the
-roofline of the dominant kernel (the kernel class with the most launch time in the timed region,
-timed live with HIP events on its stream; algorithmic FLOPs per launch), a per-kernel table, and
-the CPU baseline (the oracle restatement, rank 0 at N=1 only).
+Prints ONE JSON line (rank 0): value = samples/s summed over ranks (= tokens/s / 1792) and
+ms_per_step, the milliseconds one timed step took. A plain run sets up, warms up, times the K steps
+and prints that line, nothing else.
+
+  --dump-outputs DIR  after the timed steps, write what the last timed step handed its caller as
+                      DIR/<name>.npy (float32): the loss scalars, the trainable gradients and the
+                      trainable parameters (a fixed, seeded sample of each beyond 4M elements).
+                      Inputs, weights, timesteps and noise are seeded: the same arguments give the
+                      same inputs in every run, so two builds compare output for output.
+  --full              everything else the benchmark measures, after the timed region: the roofline
+                      of the dominant kernel (the kernel class with the most launch time in one
+                      further step, timed live with HIP events on its stream; algorithmic FLOPs per
+                      launch), a per-kernel table, the kernel selfcheck against torch fp32, and the
+                      CPU baseline (the oracle restatement, rank 0 at N=1 only;
+                      --no-cpu-baseline leaves it out).
 """
 import argparse
 import json
@@ -103,6 +114,32 @@ def synthetic_batch(device, rank):
     prompt = torch.randn(1, L_TXT, 4096, generator=g).to(device=device, dtype=torch.bfloat16)
     mask = (torch.arange(L_TXT) < N_VALID_TXT).long().view(1, L_TXT).to(device)
     return batch, prompt, mask
+
+
+DUMP_MAX_ELEMS = 4 * 1024 * 1024  # per array: 16 MB of float32, three arrays at the most
+
+
+def _sampled_f32(tensors):
+    """The tensors flattened and joined as one float32 numpy array. Beyond DUMP_MAX_ELEMS elements
+    each tensor gives its share of them at fixed positions (seeded, sorted, the same in every run)."""
+    total = sum(t.numel() for t in tensors)
+    g = torch.Generator().manual_seed(20251015)
+    parts = []
+    for t in tensors:
+        flat = t.detach().reshape(-1)
+        if total > DUMP_MAX_ELEMS:
+            k = max(1, min(flat.numel(), flat.numel() * DUMP_MAX_ELEMS // total))
+            idx = torch.randint(0, flat.numel(), (k,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts).numpy()
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def selfcheck(device):
@@ -294,6 +331,8 @@ def infer_main(args):
             lat = denoise_step(model, sch, lat, sch.timesteps[i], **kw)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # the latents the last timed denoising step returned
+        dump_outputs(args.dump_outputs, {"latents": _sampled_f32([lat])})
     fwd, _ = step_flops_per_sample(N, r=LORA_RANK)
     tflops = fwd * 3 * B * args.steps / (elapsed * 1e12)
     print(json.dumps({
@@ -315,7 +354,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kernel timer steps (roofline, kernel "
+                         "table), the kernel selfcheck and the CPU baseline, and add them to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss scalars, trainable gradients and "
+                         "parameters) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--infer", action="store_true", help="inference denoising-step benchmark")
     ap.add_argument("--infer-batch", type=int, default=1)
     ap.add_argument("--config", choices=["a", "x"], default="a",
@@ -395,13 +440,12 @@ def main():
     torch.manual_seed(20251015 + rank)
 
     N = F_LAT * H_LAT * W_LAT
-    timer = ops.LaunchTimer()
 
     def one_step(i):
         last = (i + 1) % ACCUM == 0
         if last:
             (opt if full else reducer).arm()
-        train_step(model, batch, sched, model.patchifier, cfg, prompt, mask, device)
+        out = train_step(model, batch, sched, model.patchifier, cfg, prompt, mask, device)
         if last:
             reducer()
             opt.step()
@@ -409,7 +453,9 @@ def main():
                 opt.zero_grad(set_to_none=True)
             else:
                 reducer.zero_grad()
+        return out
 
+    step_out = None
     for i in range(args.warmup):
         one_step(i)
     torch.cuda.synchronize()
@@ -418,7 +464,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
-        one_step(i)
+        step_out = one_step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -428,23 +474,16 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # per-kernel durations with HIP events on the launch stream, in further steps of the same loop
-    # right after the timed region (an event pair around every launch costs the step ~5 %, so the
-    # timed region stays un-instrumented): one step with every GEMM / attention launch bracketed
-    # ranks the kernels; then `prof_steps` steps bracket only the dominant one (few events, the
-    # per-launch figure the roofline uses)
-    i0 = args.warmup + args.steps
-    ops.set_launch_timer(timer)
-    one_step(i0)
-    ops.set_launch_timer(None)
-    kernels = timer.summary()
-    prof_steps = min(args.steps, 4)
-    dom_timer = ops.LaunchTimer(only=kernels[0]["kernel"])
-    ops.set_launch_timer(dom_timer)
-    for i in range(i0 + 1, i0 + 1 + prof_steps):
-        one_step(i)
-    ops.set_launch_timer(None)
-    dom = dom_timer.summary()[0]
+    if args.dump_outputs and rank == 0 and step_out is not None:
+        # what the last timed step handed its caller: train_step's scalars, the gradients it left in
+        # .grad (accumulated since the cycle began; none when that step ended a cycle with the
+        # optimizer update and zero_grad) and the trainable parameters as they stand after it
+        loss, rel_mse, nrmse, ld = step_out
+        arrays = {"loss": _sampled_f32([loss, rel_mse, nrmse, ld["_mse_f32"]]),
+                  "params": _sampled_f32(trainable)}
+        if (args.warmup + args.steps) % ACCUM != 0 and all(p.grad is not None for p in trainable):
+            arrays["grads"] = _sampled_f32([p.grad for p in trainable])
+        dump_outputs(args.dump_outputs, arrays)
 
     samples = B_PER_GPU * args.steps * world
     value = samples / elapsed
@@ -456,15 +495,6 @@ def main():
     # skipped key blocks' products are exact zeros, VERDICT r03 asks for both figures)
     fwd_v, bwd_v = step_flops_per_sample(N, r=LORA_RANK, L_att=N_VALID_TXT)
     step_tflops_valid = step_tflops * (fwd_v + bwd_v) / (fwd + bwd)
-    # the dominant kernel = the class with the most HIP-event time in the ranking step (all of them
-    # are hand-written); its algorithmic TFLOP/s = its FLOPs / its summed launch durations
-    for k in kernels + [dom]:
-        k["tflops"] = k["flops"] / (k["ms"] * 1e-3) / 1e12
-    achieved = dom["tflops"]
-    if args.config == "a" and not full:
-        traffic, traffic_src = load_traffic(dom["kernel"])
-    else:
-        traffic, traffic_src = None, "measured for config A LoRA only"
     line = {
         "metric": f"LTX-2B {'full (ZeRO-2)' if full else 'LoRA'} train-step samples/sec (latent-tokens/sec = samples/sec x {N})",
         "value": round(value, 4),
@@ -499,6 +529,53 @@ def main():
         "step_mfma_frac": round(step_tflops / MFMA_BF16_PEAK_TFLOPS, 4),
         "step_tflops_per_gpu_excl_padding_keys": round(step_tflops_valid, 1),
         "step_mfma_frac_excl_padding_keys": round(step_tflops_valid / MFMA_BF16_PEAK_TFLOPS, 4),
+    }
+    if args.full:
+        line.update(full_measurements(args, one_step, ops, elapsed, device, full))
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "a" and not full:
+            try:
+                line["cpu_baseline"] = cpu_baseline()
+            except Exception as exc:  # the baseline must never hide the GPU measurement
+                line["cpu_baseline"] = {"value": None, "error": repr(exc)[:200]}
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, one_step, ops, elapsed, device, full):
+    """--full: the roofline of the dominant kernel, the per-kernel table and the selfcheck, measured
+    in further steps of the same loop after the timed region."""
+    # per-kernel durations with HIP events on the launch stream, in further steps of the same loop
+    # right after the timed region (an event pair around every launch costs the step ~5 %, so the
+    # timed region stays un-instrumented): one step with every GEMM / attention launch bracketed
+    # ranks the kernels; then `prof_steps` steps bracket only the dominant one (few events, the
+    # per-launch figure the roofline uses)
+    i0 = args.warmup + args.steps
+    timer = ops.LaunchTimer()
+    ops.set_launch_timer(timer)
+    one_step(i0)
+    ops.set_launch_timer(None)
+    kernels = timer.summary()
+    prof_steps = min(args.steps, 4)
+    dom_timer = ops.LaunchTimer(only=kernels[0]["kernel"])
+    ops.set_launch_timer(dom_timer)
+    for i in range(i0 + 1, i0 + 1 + prof_steps):
+        one_step(i)
+    ops.set_launch_timer(None)
+    dom = dom_timer.summary()[0]
+
+    # the dominant kernel = the class with the most HIP-event time in the ranking step (all of them
+    # are hand-written); its algorithmic TFLOP/s = its FLOPs / its summed launch durations
+    for k in kernels + [dom]:
+        k["tflops"] = k["flops"] / (k["ms"] * 1e-3) / 1e12
+    achieved = dom["tflops"]
+    if args.config == "a" and not full:
+        traffic, traffic_src = load_traffic(dom["kernel"])
+    else:
+        traffic, traffic_src = None, "measured for config A LoRA only"
+    return {
         "roofline": {"bound": "mfma", "kernel": dom["kernel"],
                      "achieved": round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4),
@@ -515,18 +592,8 @@ def main():
         "kernels": [{"kernel": k["kernel"], "launches_per_step": k["launches"],
                      "ms_per_step": round(k["ms"], 3), "tflops": round(k["tflops"], 1),
                      "frac": round(k["tflops"] / MFMA_BF16_PEAK_TFLOPS, 4)} for k in kernels[:10]],
+        "selfcheck": selfcheck(device),
     }
-    line["selfcheck"] = selfcheck(device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "a" and not full:
-        try:
-            line["cpu_baseline"] = cpu_baseline()
-        except Exception as exc:  # the baseline must never hide the GPU measurement
-            line["cpu_baseline"] = {"value": None, "error": repr(exc)[:200]}
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

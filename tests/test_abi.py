@@ -103,3 +103,33 @@ def test_bench_traffic_lookup_reads_newest_profile():
     assert src == os.path.basename(newest) and got == val
     got, why = bench.load_traffic("ltx::no_such_kernel<1>")
     assert got is None and "no entry" in why
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole, in order, as float32; beyond
+    DUMP_MAX_ELEMS every tensor gives its share at the same seeded positions in every call, so two
+    runs' files line up element for element and stay under the size cap."""
+    import importlib.util
+    import os
+
+    import numpy as np
+    import torch
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = torch.arange(6, dtype=torch.bfloat16).view(2, 3)
+    b = torch.tensor(7.0)
+    whole = bench._sampled_f32([a, b])
+    assert whole.dtype == np.float32 and whole.tolist() == [0, 1, 2, 3, 4, 5, 7]
+    cap = bench.DUMP_MAX_ELEMS
+    big = [torch.arange(cap, dtype=torch.float32), torch.arange(3 * cap, dtype=torch.float32), torch.ones(1)]
+    s1, s2 = bench._sampled_f32(big), bench._sampled_f32([t.clone() for t in big])
+    assert np.array_equal(s1, s2)
+    n0, n1 = cap * cap // (4 * cap + 1), 3 * cap * cap // (4 * cap + 1)
+    assert s1.size == n0 + n1 + 1 and s1.nbytes <= 16 * 2 ** 20 + 4 * len(big)
+    # positions ascend within each tensor's share, and the values are the sampled elements themselves
+    assert (np.diff(s1[:n0]) >= 0).all() and s1[:n0].max() < cap
+    assert (np.diff(s1[n0:n0 + n1]) >= 0).all() and s1[n0:n0 + n1].max() >= cap
+    bench.dump_outputs(str(tmp_path / "d"), {"x": whole})
+    assert np.array_equal(np.load(tmp_path / "d" / "x.npy"), whole)

@@ -23,7 +23,7 @@ def _run(extra, port, timeout):
     env = dict(os.environ, LTX_BENCH_BACKEND="gloo", LTX_BENCH_SAME_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--no-cpu-baseline"] + extra
+           "--gpus", "2", "--full", "--no-cpu-baseline"] + extra  # --full: the selfcheck asserted below
     torch.cuda.empty_cache()
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, f"rc {p.returncode}\n{p.stdout[-3000:]}\n{p.stderr[-3000:]}"

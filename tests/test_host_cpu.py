@@ -20,7 +20,7 @@ from safetensors.torch import load_file, save_file
 from params import canonical_name
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_YAML = "/root/reference/configs/train-avatars.yaml"
+REF_YAML = os.path.join(GOLD, "train-avatars.yaml")  # the reference's configs/train-avatars.yaml
 
 TINY = None
 
@@ -49,7 +49,6 @@ def test_train_config_golden_fields():
     assert cfg.gradient_accumulation_steps == 16 and cfg.lora_rank == 32
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference tree not present")
 def test_train_config_matches_reference_parse():
     from dataclasses import asdict
 

@@ -14,7 +14,7 @@ done
 for i in $(seq 1 $N); do
   for L in "$A" "$B"; do
     echo "== bench $L"
-    LTX_HIP_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline ${BENCH_ARGS:-} 2>>gpurun_out/ab_libs.err \
+    LTX_HIP_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} \
       | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], [(k["kernel"][:60], k["ms_per_step"]) for k in d["kernels"][:4]])' || exit $?
   done
 done

@@ -10,8 +10,8 @@ if [ -n "$TESTS" ]; then
   rc=$?; tail -3 $O/tests.log; [ $rc -eq 0 ] || exit $rc
 fi
 for i in 1 2; do
-  timeout -k 10 200 python -u bench.py --no-cpu-baseline > $O/bench_new$i.json 2>$O/bench_new$i.err || exit 6
-  LTX_HIP_LIB=$PWD/build_ab/libltxhip_base.so timeout -k 10 200 python -u bench.py --no-cpu-baseline > $O/bench_base$i.json 2>$O/bench_base$i.err || exit 7
+  timeout -k 10 200 python -u bench.py --full --no-cpu-baseline > $O/bench_new$i.json 2>$O/bench_new$i.err || exit 6
+  LTX_HIP_LIB=$PWD/build_ab/libltxhip_base.so timeout -k 10 200 python -u bench.py --full --no-cpu-baseline > $O/bench_base$i.json 2>$O/bench_base$i.err || exit 7
 done
 python - <<PY
 import json

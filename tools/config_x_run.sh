@@ -10,10 +10,10 @@ mkdir -p $OUT $RAW
 cd /tmp
 export TMPDIR=/tmp
 B=${XB:-8}
-timeout -k 10 400 python3 -u $R/bench.py --config x --batch $B --steps 5 --warmup 2 --no-cpu-baseline \
+timeout -k 10 400 python3 -u $R/bench.py --full --config x --batch $B --steps 5 --warmup 2 --no-cpu-baseline \
     > $OUT/bench_x_b$B.jsonl 2> $OUT/bench_x_b$B.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format rocpd csv -d $RAW/trace -o run -- \
-    python3 $R/bench.py --config x --batch $B --steps 3 --warmup 1 --no-cpu-baseline \
+    python3 $R/bench.py --full --config x --batch $B --steps 3 --warmup 1 --no-cpu-baseline \
     > $OUT/bench_x_b${B}_under_rocprof.jsonl 2> $RAW/trace.err
 cp $RAW/trace/run_kernel_stats.csv $OUT/kernel_stats_x_b$B.csv
 # 1 warm-up + 3 timed + 1 + 3 timer steps in the trace

@@ -6,6 +6,7 @@
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 cd $R
+BENCH_ARGS=${BENCH_ARGS:---full}  # the default bench line carries the roofline, selfcheck and CPU baseline
 fatal() { case $1 in 124|134|137|139) return 0;; esac; [ $1 -gt 128 ] && return 0; return 1; }
 timeout -k 10 ${TEST_TIMEOUT:-600} python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ${1:-} \
     > gpurun_out/gpu_tests.log 2>&1
