@@ -210,7 +210,9 @@ int ltx_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
 
 /* ---- bf16 MFMA GEMM: C[M,N] = epilogue(A[M,K] . W[N,K]^T) ------------------------------------ */
 /* nn.Linear forward (W as stored) and dgrad (W^T packed once: frozen weights). K % 64 == 0,
- * N % 8 == 0, leading dims % 8 == 0, 16-B aligned operands. rank in {8,16,32} for LoRA. */
+ * N % 8 == 0, leading dims % 8 == 0, 16-B aligned operands. rank in {8,16,32} for the LORA
+ * epilogues (the in-epilogue f32 adapter product the model no longer uses: its adapters ride the
+ * K extension A2 / W2, any K2 % 64 == 0, which carries ranks up to 128). */
 int ltx_gemm_bf16_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C,
                      int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
                      const void* bias, const void* aux0, int64_t ld0, const void* aux1,
@@ -272,7 +274,9 @@ int ltx_attn_bwd_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, cons
 /* ---- LoRA skinny contractions in f32 (peft lora_A / lora_B, training.py:50-68) --------------- */
 /* out[m,j] = alpha * sum_k x[m,k] * Wr[j,k], Wr element (j,k) at Wr[j*wj + k*wk]; x bf16 [M,K]
  * (ldx), out f32 [M,r] (ldo). lora_A forward (u = x.A^T: wj = K, wk = 1) and the lora_B dgrad
- * (w = s*dY.B with B f32 [N,r]: wj = 1, wk = r). r in {8, 16, 32}. When split != null the rows
+ * (w = s*dY.B with B f32 [N,r]: wj = 1, wk = r). r in {8, 16, 32, 64, 128}: that set holds for
+ * every ltx_lora_* entry point (ranks above 32 run as 32-wide rank slices of one launch, 16-wide
+ * in ltx_lora_rows' whole-K kernel). When split != null the rows
  * are also written as the activation K-extension operand (bf16 [M, K2], ld_split: role 0 of
  * ltx_lora_split_bf16 with scale 1), saving that launch. */
 int ltx_lora_down(const void* x, int64_t ldx, const float* Wr, int64_t wj, int64_t wk,
@@ -324,7 +328,9 @@ int ltx_lora_wgrad_grouped(const void* y, int64_t ldy, const float* u, int64_t l
  * (w3[j] + w3[RP+j] + w3[2RP+j])[n] (f32, ldw_out) with its K-extension split row [hi|hi|lo|0..]
  * (bf16 [M, K2], ld_split) and dw[n*on + j*oj] (+)= alpha * sum_m Y[m,n] * U[m,j] (accumulate != 0
  * adds into the buffer). Y bf16 [M,N] (ldy), U f32 [M,r] (ldu), w3 = ltx_lora_pieces of B^T.
- * M % 32 == 0, N % 512 == 0, rank 8 or 16. workspace: ltx_lora_dy_workspace floats (f32). */
+ * M % 32 == 0, N % 512 == 0, rank 8, 16, 32, 64 or 128: up to rank 32 one stream of dY from HBM
+ * feeds both products; ranks 64 / 128 run 2 / 4 rank slices of 32 in the same launch, each
+ * streaming its dY tile again. workspace: ltx_lora_dy_workspace floats (f32). */
 int ltx_lora_dy(const void* y, int64_t ldy, const float* u, int64_t ldu, const void* w3, int64_t ldw3,
                 int64_t M, int64_t N, int64_t r, float alpha, float* w, int64_t ldw_out, void* split,
                 int64_t ld_split, int64_t K2, float* dw, int64_t on, int64_t oj, int accumulate,

@@ -275,8 +275,13 @@ def body2(MF):
     return L
 
 
-def body3(MF):
-    """Variant 3 (gemm_ring2_kernel's LDS layout and operands, LTX_GEMM_RING=3): the DMA of the
+def body3(MF, marked=False):
+    """marked: the same stream cut into the pieces main() emits as macros ("#NAME" lines ahead of each:
+    HEAD, the two loop tiles LT0 / LT1, LOOPEND, the two tail tiles TAIL0 / TAIL1, END), the loop
+    tiles' DMA operands as tokens (@W@ / @X@ offsets, @WS@ / @XS@ buffers) that main() turns into
+    macro parameters, so that the long K extensions reuse the loop tiles on their own operands.
+
+    Variant 3 (gemm_ring2_kernel's LDS layout and operands, LTX_GEMM_RING=3): the DMA of the
     tile after next gets ~1.5x the latency slack. Each K-tile t (stage s = t % 2) is three segments:
       S1 (k-half 0, all MFMAs): ds_read (t, k-half 1) -> F1;
          s_waitcnt lgkmcnt(0); s_barrier     -- M1: every wave done reading stage s
@@ -304,13 +309,15 @@ def body3(MF):
             out.append(f"ds_read_b128 {fr(st, 8 + jm)}, %[xr{stage}{kh}] offset:{jm * 2048}")
         return out
 
-    def wdma(stage):
+    def wdma(stage, tok=False):
+        o, srd = ("@W@", "@WS@") if tok else ("ow", "wsrd")
         return [(f"s_add_u32 m0, %[mw], {stage * ST + i * 4096}",
-                 f"buffer_load_dwordx4 %[ow{i}], %[wsrd], %[koff] offen lds") for i in range(8)]
+                 f"buffer_load_dwordx4 %[{o}{i}], %[{srd}], %[koff] offen lds") for i in range(8)]
 
-    def xdma(stage):
+    def xdma(stage, tok=False):
+        o, srd = ("@X@", "@XS@") if tok else ("ox", "xsrd")
         return [(f"s_add_u32 m0, %[mx], {stage * ST + i * 4096}",
-                 f"buffer_load_dwordx4 %[ox{i}], %[xsrd], %[koff] offen lds") for i in range(MF)]
+                 f"buffer_load_dwordx4 %[{o}{i}], %[{srd}], %[koff] offen lds") for i in range(MF)]
 
     mf = [(i, jm) for i in range(8) for jm in range(MF)]
     nm = len(mf)
@@ -342,12 +349,17 @@ def body3(MF):
         run(0, range(nm), reads(1, stage, 1), [])
         a("s_waitcnt lgkmcnt(0)")
         a("s_barrier")
-        run(1, range(half), [], wdma(stage) if with_dma else [])
+        run(1, range(half), [], wdma(stage, marked) if with_dma else [])
         a("s_waitcnt vmcnt(8)" if with_dma else "s_waitcnt vmcnt(0)")
         a("s_barrier")
-        run(1, range(half, nm), [] if last else reads(0, 1 - stage, 0), xdma(stage) if with_dma else [],
+        run(1, range(half, nm), [] if last else reads(0, 1 - stage, 0), xdma(stage, marked) if with_dma else [],
             koff_after=with_dma)
 
+    def mark(name):
+        if marked:
+            a("#" + name)
+
+    mark("HEAD")
     a("s_nop 4")
     a("s_mov_b32 %[keep], m0")
     for stage in range(2):  # tiles 0 and 1
@@ -362,18 +374,66 @@ def body3(MF):
     a("s_cmp_eq_u32 %[iters], 0")
     a("s_cbranch_scc1 L_tail_%=")
     a("L_loop_%=:")
+    mark("LT0")
     tile(0, True, False)
+    mark("LT1")
     tile(1, True, False)
+    mark("LOOPEND")
     a("s_sub_u32 %[iters], %[iters], 1")
     a("s_cmp_eq_u32 %[iters], 0")
     a("s_cbranch_scc0 L_loop_%=")
     a("L_tail_%=:")
+    mark("TAIL0")
     tile(0, False, False)
+    mark("TAIL1")
     tile(1, False, True)
+    mark("END")
     a("s_mov_b32 m0, %[keep]")
     a("s_nop 15")
     a("s_nop 15")
     return L
+
+
+# The long K extensions of LoRA ranks 64 / 128 (K2 = 192 / 384: 3 / 6 tiles) continue the main loop's
+# pipeline instead of following it in bursts (ext_body2: each burst exposes a DMA latency, measured
+# slower than gemm_nt_kernel_t at these lengths): after the loop, %[koff]
+# restarts at 0 and loop-tile pairs on the extension's operands (XD) run in place of the tail -- the
+# main K's last two tiles issue the DMA of extension tiles 0 and 1, extension tile e that of tile
+# e + 2 -- then the ordinary tail tiles finish. No new instruction text: the pieces of body3(marked).
+#   K2 = 384: XD XD XD TAIL0 TAIL1 (tiles T-2, T-1, e0 .. e3 with DMA; e4, e5 without)
+#   K2 = 192: XD XD TAIL0          (e1's DMA asks for a tile past K2: the buffer bounds make it zeros
+#             or the next row's bytes, into a stage nobody computes on again; e2 = TAIL0 prefetches
+#             that stage's first fragments into dead registers, retired by the added lgkmcnt(0))
+# Same tiles, same k-half order as gemm_nt_kernel_t: bitwise its sums. The closing barrier keeps the
+# epilogue's C image off a slower wave's last reads (ext_body2()).
+MAIN_OPS = '("ow", "ox", "wsrd", "xsrd")'
+EXT_OPS = '("ew", "ex", "w2srd", "x2srd")'
+LONG_EXT = {3: ["XD", "XD", "TAIL0", '"s_waitcnt lgkmcnt(0)\\n\\t"'], 6: ["XD", "XD", "XD", "TAIL0", "TAIL1"]}
+
+
+def emit_pieces(txt, define, MF):
+    """body3(MF, marked) as the macros LTX_RING_<PIECE>_MF<MF> (LT0 / LT1 take the DMA operand names),
+    LTX_RING_BODY_MF<MF> composed of them (the same string as before) and the long extensions."""
+    pieces, name = {}, None
+    for l in body3(MF, marked=True):
+        if l.startswith("#"):
+            name = l[1:]
+            pieces[name] = []
+        else:
+            pieces[name].append(l)
+    flat = [l for n in pieces for l in pieces[n]]
+    plain = lambda l: l.replace("@W@", "ow").replace("@X@", "ox").replace("@WS@", "wsrd").replace("@XS@", "xsrd")
+    assert [plain(l) for l in flat] == body3(MF)
+    m = lambda n: f"LTX_RING_{n}_MF{MF}"
+    for n, lines in pieces.items():
+        define(txt, m(n) + ("(W, X, WS, XS)" if n in ("LT0", "LT1") else ""), lines)
+    loop = f"{m('HEAD')} {m('LT0')}{MAIN_OPS} {m('LT1')}{MAIN_OPS} {m('LOOPEND')}"
+    txt.append(f"#define LTX_RING_BODY_MF{MF} {loop} {m('TAIL0')} {m('TAIL1')} {m('END')}\n")
+    txt.append(f"#define {m('XD')} {m('LT0')}{EXT_OPS} {m('LT1')}{EXT_OPS}\n")
+    for T2, seq in LONG_EXT.items():
+        body = " ".join(s if s.startswith('"') else m(s) for s in seq)
+        txt.append(f'#define LTX_RING_BODY_EXT{T2}_MF{MF} {loop} "s_mov_b32 %[koff], 0\\n\\t" {body} '
+                   f'"s_barrier\\n\\t" {m("END")}\n')
 
 
 def ext_body2(MF, T2):
@@ -636,12 +696,13 @@ def main():
         return ["// GENERATED by tools/gen_gemm_ring.py -- do not edit by hand.", what, "#pragma once", ""]
 
     def define(txt, name, lines):
-        txt.append(f"#define {name} \\\n" + " \\\n".join(f'  "{l}\\n\\t"' for l in lines) + "\n")
+        tok = lambda l: l.replace("@WS@", '" WS "').replace("@XS@", '" XS "').replace("@W@", '" W "').replace("@X@", '" X "')
+        txt.append(f"#define {name} \\\n" + " \\\n".join(f'  "{tok(l)}\\n\\t"' for l in lines) + "\n")
     txt = header("// The hand-scheduled K loop of gemm_ring_kernel (gemm_ring.h): body3() and ext_body2() of the\n"
                  "// generator (body() / body2() / body4() are measured-and-not-adopted variants, DESIGN.md §7).")
     for MF in (7, 8):
         main = body3(MF)
-        define(txt, f"LTX_RING_BODY_MF{MF}", main)
+        emit_pieces(txt, define, MF)
         assert main[-3:] == ["s_mov_b32 m0, %[keep]", "s_nop 15", "s_nop 15"]
         for T2 in (1, 2):
             define(txt, f"LTX_RING_BODY_EXT{T2}_MF{MF}", main[:-3] + ext_body2(MF, T2))

@@ -801,7 +801,10 @@ static int launch_lora(const GemmParams& p, hipStream_t s) {
     case 8: return launch<EPI, 8>(p, s);
     case 16: return launch<EPI, 16>(p, s);
     case 32: return launch<EPI, 32>(p, s);
-    default: return fail(LTX_ERR_BAD_ARG, "gemm lora: rank must be 8, 16 or 32");
+    // the in-epilogue f32 adapter product (R products per output element from registers): kept for
+    // its direct callers at the ranks it was built for; the model's adapters, ranks 64 / 128
+    // included, ride the K extension (A2 / W2)
+    default: return fail(LTX_ERR_BAD_ARG, "gemm lora epilogue: rank must be 8, 16 or 32 (ranks 64 / 128: use the K extension)");
   }
 }
 

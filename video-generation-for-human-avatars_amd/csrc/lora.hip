@@ -1,6 +1,8 @@
 // LoRA adapter contractions in f32 (peft 0.17.1 keeps adapters in f32 on a bf16 base:
-// training.py:50-68 + autocast_adapter_dtype). Rank r <= 32 makes these skinny, so they are
-// HBM-bound (x or dY is read once: 2 B/element for 2r FLOP/element) and run on the exact-f32
+// training.py:50-68 + autocast_adapter_dtype). Ranks 8, 16, 32, 64 and 128. Up to r = 32 these
+// are skinny and HBM-bound (x or dY is read once: 2 B/element for 2r FLOP/element); ranks 64 / 128
+// run as 32-wide rank slices of one launch (grid z, y or x below), each slice reading its rows
+// again (L2 / MALL), with the register and LDS budget of r = 32. They run on the exact-f32
 // matrix core v_mfma_f32_16x16x4_f32 (an f32 fma chain, bitwise like the VALU, at 4x its rate),
 // which keeps the adapters' f32 semantics while freeing the VALU for address math.
 // The up-projection (B) and its input-gradient half are fused into the bf16 GEMM epilogues
@@ -38,10 +40,15 @@ __global__ __launch_bounds__(64 * KW) void lora_down_kernel(const bf16_t* __rest
   out += blockIdx.y * go;
   if (split) split += blockIdx.y * gs;
   constexpr int RP = R >= 16 ? R : 16;  // R = 8 runs as a padded 16-wide tile
-  constexpr int JT = RP / 16;
+  // ranks above 32 run as 32-wide rank slices, one per blockIdx.z of the same launch (the weight
+  // fragments and accumulators of a wider tile would not fit the register file); j0 = slice origin
+  constexpr int SW = RP < 32 ? RP : 32;
+  constexpr int RW = R < SW ? R : SW;  // real columns of a slice
+  constexpr int JT = SW / 16;
+  const int j0 = blockIdx.z * SW;
   // RG = 16-row groups per block: 2 (one weight fetch serves 32 rows) when there are rows enough
   // to fill the chip, else 1
-  __shared__ float part[KW][16 * RG][RP + 1];
+  __shared__ float part[KW][16 * RG][SW + 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m0 = blockIdx.x * 16 * RG;
   const int g = lane >> 4;
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(64 * KW) void lora_down_kernel(const bf16_t* __rest
       for (int q = 0; q < RG; ++q) xv[st][q] = *(const u32x4*)(xr[q] + k);
 #pragma unroll
       for (int t = 0; t < JT; ++t) {
-        const int j = t * 16 + (lane & 15);
+        const int j = j0 + t * 16 + (lane & 15);
         if (j < R) {
           const float* wp = Wr + (int64_t)j * wj + (int64_t)k * wk;
           if (wk == 1) {
@@ -106,13 +113,13 @@ __global__ __launch_bounds__(64 * KW) void lora_down_kernel(const bf16_t* __rest
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) part[wave][16 * q + (lane >> 4) * 4 + rr][t * 16 + (lane & 15)] = acc[q][t][rr];
   __syncthreads();
-  for (int e = threadIdx.x; e < 16 * RG * R; e += 64 * KW) {
-    const int rr = e / R, j = e % R;
+  for (int e = threadIdx.x; e < 16 * RG * RW; e += 64 * KW) {
+    const int rr = e / RW, jl = e % RW, j = j0 + jl;
     const int m = m0 + rr;
     if (m >= M) continue;
     float sum = 0.f;
 #pragma unroll
-    for (int w = 0; w < KW; ++w) sum += part[w][rr][j];
+    for (int w = 0; w < KW; ++w) sum += part[w][rr][jl];
     const float v = sum * alpha;
     out[(int64_t)m * ldo + j] = v;
     if (split) {
@@ -124,7 +131,7 @@ __global__ __launch_bounds__(64 * KW) void lora_down_kernel(const bf16_t* __rest
       sr[2 * R + j] = lo;
     }
   }
-  if (split) {  // zero padding columns 3R .. K2
+  if (split && blockIdx.z == 0) {  // zero padding columns 3R .. K2
     const int pad = K2 - 3 * R;
     for (int e = threadIdx.x; e < 16 * RG * pad; e += 64 * KW) {
       const int rr = e / pad, c = 3 * R + e % pad;
@@ -176,8 +183,13 @@ __global__ __launch_bounds__(64 * NW) void lora_rows_kernel(const bf16_t* __rest
                                                             int K2) {
   static_assert(NR >= 4, "ring depth (the counted waits assume D(s) precedes W(s))");
   constexpr int RP = R >= 16 ? R : 16;
-  constexpr int JT = RP / 16;
+  // ranks above 32: 32-wide rank slices, one per blockIdx.y of the same launch (three register sets
+  // of piece fragments for a wider tile would not fit beside the accumulators); j0 = slice origin
+  constexpr int SW = RP < 32 ? RP : 32;
+  constexpr int RW = R < SW ? R : SW;
+  constexpr int JT = SW / 16;
   constexpr int NF = 3 * JT;  // piece fragments per 32-deep k step
+  const int j0 = blockIdx.y * SW;
   constexpr int WL = 2 * NF;  // fragment loads per slot
   __shared__ __attribute__((aligned(16))) char ring[NW][NR][4096];
   const int lane = threadIdx.x & 63;
@@ -213,7 +225,7 @@ __global__ __launch_bounds__(64 * NW) void lora_rows_kernel(const bf16_t* __rest
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int t = 0; t < JT; ++t)
-      wo[p * JT + t] = (uint32_t)((((int64_t)(p * RP + t * 16 + (lane & 15))) * ldw + (lane >> 4) * 8) * 2);
+      wo[p * JT + t] = (uint32_t)((((int64_t)(p * RP + j0 + t * 16 + (lane & 15))) * ldw + (lane >> 4) * 8) * 2);
   const char* wbase = (const char*)(w3 + kw0);
   s16x8 wf[3][2][NF];  // [register set][k half][fragment]
   auto wload = [&](int s, s16x8 (&dst)[2][NF]) {
@@ -282,8 +294,8 @@ __global__ __launch_bounds__(64 * NW) void lora_rows_kernel(const bf16_t* __rest
   }
   // cross-wave sum through LDS (the ring is free once every wave is past its last reads)
   __syncthreads();
-  float(*part)[32][RP + 1] = (float(*)[32][RP + 1])&ring[0][0][0];
-  static_assert(NW * 32 * (RP + 1) * 4 <= NW * NR * 4096, "partials fit the ring");
+  float(*part)[32][SW + 1] = (float(*)[32][SW + 1])&ring[0][0][0];
+  static_assert(NW * 32 * (SW + 1) * 4 <= NW * NR * 4096, "partials fit the ring");
   // C layout: col j = lane & 15 (+16t), row m = (lane >> 4) * 4 + reg
 #pragma unroll
   for (int q = 0; q < 2; ++q)
@@ -292,13 +304,13 @@ __global__ __launch_bounds__(64 * NW) void lora_rows_kernel(const bf16_t* __rest
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) part[wave][16 * q + (lane >> 4) * 4 + rr][t * 16 + (lane & 15)] = acc[q][t][rr];
   __syncthreads();
-  for (int e = threadIdx.x; e < 32 * R; e += 64 * NW) {
-    const int rr = e / R, j = e % R;
+  for (int e = threadIdx.x; e < 32 * RW; e += 64 * NW) {
+    const int rr = e / RW, jl = e % RW, j = j0 + jl;
     const int m = m0 + rr;
     if (m >= M) continue;
     float sum = 0.f;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) sum += part[w][rr][j];
+    for (int w = 0; w < NW; ++w) sum += part[w][rr][jl];
     const float v = sum * alpha;
     out[(int64_t)m * ldo + j] = v;
     if (split) {
@@ -310,7 +322,7 @@ __global__ __launch_bounds__(64 * NW) void lora_rows_kernel(const bf16_t* __rest
       sr[2 * R + j] = lo;
     }
   }
-  if (split) {  // zero padding columns 3R .. K2
+  if (split && blockIdx.y == 0) {  // zero padding columns 3R .. K2
     const int pad = K2 - 3 * R;
     for (int e = threadIdx.x; e < 32 * pad; e += 64 * NW) {
       const int rr = e / pad, c = 3 * R + e % pad;
@@ -347,11 +359,17 @@ __global__ __launch_bounds__(512) void lora_wgrad_kernel(const bf16_t* __restric
   u += blockIdx.z * gu;
   dw += blockIdx.z * gd;
   constexpr int RP = R >= 16 ? R : 16;
-  constexpr int JT = RP / 16;
+  // ranks above 32: 32-wide rank slices, NSL consecutive blockIdx.x per 128 columns in the same
+  // launch (the wave partials of a wider tile would not fit the LDS); j0 = slice origin
+  constexpr int SW = RP < 32 ? RP : 32;
+  constexpr int RW = R < SW ? R : SW;
+  constexpr int NSL = RP / SW;
+  constexpr int JT = SW / 16;
   constexpr int NW = 8;  // waves per block, interleaved over row quads
-  __shared__ float red[NW][RP][128 + 1];
+  __shared__ float red[NW][SW][128 + 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n0 = blockIdx.x * 128;
+  const int n0 = (blockIdx.x / NSL) * 128;
+  const int j0 = (blockIdx.x % NSL) * SW;
   const int mb = blockIdx.y * rows_per_split;
   const int me = min(M, mb + rows_per_split);
   const int c8 = n0 + 8 * (lane & 15);  // this lane's 8 columns
@@ -374,7 +392,7 @@ __global__ __launch_bounds__(512) void lora_wgrad_kernel(const bf16_t* __restric
       if (rowok && colok) yv[q] = *(const u32x4*)(y + (int64_t)m * ldy + c8);
 #pragma unroll
       for (int t = 0; t < JT; ++t) {
-        const int j = t * 16 + (lane & 15);
+        const int j = j0 + t * 16 + (lane & 15);
         uv[q][t] = (rowok && j < R) ? u[(int64_t)m * ldu + j] : 0.f;
       }
     }
@@ -397,16 +415,16 @@ __global__ __launch_bounds__(512) void lora_wgrad_kernel(const bf16_t* __restric
   __syncthreads();
   // consecutive threads -> consecutive output addresses (j fastest when the output is [N, r])
   const bool jfast = (oj == 1);
-  for (int e = tid; e < R * 128; e += 64 * NW) {
-    const int j = jfast ? e % R : e / 128;
-    const int c = jfast ? e / R : e % 128;
+  for (int e = tid; e < RW * 128; e += 64 * NW) {
+    const int jl = jfast ? e % RW : e / 128;
+    const int c = jfast ? e / RW : e % 128;
     const int n = n0 + c;
     if (n < N) {
       float sum = 0.f;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) sum += red[w][j][c];
+      for (int w = 0; w < NW; ++w) sum += red[w][jl][c];
       const float v = sum * alpha;
-      const int64_t o = (int64_t)n * on + (int64_t)j * oj;
+      const int64_t o = (int64_t)n * on + (int64_t)(j0 + jl) * oj;
       if (part != nullptr) {  // this split's partial, in the output's own layout
         part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * ((int64_t)N * R) + o] = v;
       } else {
@@ -489,7 +507,8 @@ extern "C" int ltx_lora_down_grouped(const void* x, int64_t ldx, const float* Wr
   // 32-row blocks for token-sized M (16-row blocks measured 26 vs 21 us at M = 14336); K split 8
   // ways (512 threads) there: 19.7 vs 20.7 us (forward A), 18.6 vs 19.6 us (split B^T dgrad)
   const bool big = M >= 8192;
-  const dim3 grid((unsigned)(big ? (M + 31) / 32 : (M + 15) / 16), (unsigned)groups);
+  // ranks above 32: one 32-wide rank slice per grid z
+  const dim3 grid((unsigned)(big ? (M + 31) / 32 : (M + 15) / 16), (unsigned)groups, (unsigned)(r > 32 ? r / 32 : 1));
   hipStream_t s = (hipStream_t)stream;
   bf16_t* sp = (bf16_t*)split;
 #define LTX_LORA_DOWN(RR)                                                                                      \
@@ -509,7 +528,9 @@ extern "C" int ltx_lora_down_grouped(const void* x, int64_t ldx, const float* Wr
     case 8: LTX_LORA_DOWN(8) break;
     case 16: LTX_LORA_DOWN(16) break;
     case 32: LTX_LORA_DOWN(32) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_down: rank must be 8, 16 or 32");
+    case 64: LTX_LORA_DOWN(64) break;
+    case 128: LTX_LORA_DOWN(128) break;
+    default: return fail(LTX_ERR_BAD_ARG, "lora_down: rank must be 8, 16, 32, 64 or 128");
   }
 #undef LTX_LORA_DOWN
   LTX_LAUNCH_CHECK();
@@ -525,8 +546,8 @@ extern "C" int ltx_lora_down(const void* x, int64_t ldx, const float* Wr, int64_
 
 extern "C" int ltx_lora_pieces(const float* src, int64_t rs, int64_t cs, int64_t r, int64_t K, void* out,
                                int64_t ldo, void* stream) {
-  LTX_CHECK_ARG(src && out && K > 0 && ldo >= K && (r == 8 || r == 16 || r == 32),
-                "lora_pieces: bad args (rank 8, 16 or 32)");
+  LTX_CHECK_ARG(src && out && K > 0 && ldo >= K && (r == 8 || r == 16 || r == 32 || r == 64 || r == 128),
+                "lora_pieces: bad args (rank 8, 16, 32, 64 or 128)");
   const int RP = r >= 16 ? (int)r : 16;
   const int64_t total = (int64_t)RP * K;
   int64_t g = (total + 255) / 256;
@@ -544,7 +565,7 @@ extern "C" int ltx_lora_rows(const void* x, int64_t ldx, const void* w3, int64_t
   LTX_CHECK_ARG(K % 256 == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldw % 8 == 0 &&
                     ((uintptr_t)w3 % 16) == 0 && ldw >= K,
                 "lora_rows: K % 256, 16-B aligned rows of x and of the pieces");
-  LTX_CHECK_ARG((int64_t)ldx * 2 * (M - 1) + 2 * K < ((int64_t)1 << 32) && (int64_t)ldw * 2 * 3 * 32 < ((int64_t)1 << 32),
+  LTX_CHECK_ARG((int64_t)ldx * 2 * (M - 1) + 2 * K < ((int64_t)1 << 32) && (int64_t)ldw * 2 * 3 * (r > 32 ? r : 32) < ((int64_t)1 << 32),
                 "lora_rows: 32-bit DMA offsets");
   LTX_CHECK_ARG(!split || (K2 >= 3 * r && K2 % 64 == 0 && ld_split >= K2), "lora_rows: split needs K2 >= 3r, %64");
   hipStream_t s = (hipStream_t)stream;
@@ -553,7 +574,7 @@ extern "C" int ltx_lora_rows(const void* x, int64_t ldx, const void* w3, int64_t
     LTX_LAUNCH_CHECK();
     return LTX_OK;
   }
-  const dim3 grid((unsigned)((M + 31) / 32));
+  const dim3 grid((unsigned)((M + 31) / 32), (unsigned)(r > 32 ? r / 32 : 1));  // y: 32-wide rank slices
   // 4 waves x K/4 per 32-row block, 4-slot ring: 16.3 us at M = 14336, K = 2048, r = 16 against
   // 19.9 us for lora_down_kernel (8 waves x K/8 with a 3-slot ring: 17.8 us)
 #define LTX_LORA_ROWS(RR)                                                                             \
@@ -563,7 +584,9 @@ extern "C" int ltx_lora_rows(const void* x, int64_t ldx, const void* w3, int64_t
     case 8: LTX_LORA_ROWS(8) break;
     case 16: LTX_LORA_ROWS(16) break;
     case 32: LTX_LORA_ROWS(32) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_rows: rank must be 8, 16 or 32");
+    case 64: LTX_LORA_ROWS(64) break;
+    case 128: LTX_LORA_ROWS(128) break;
+    default: return fail(LTX_ERR_BAD_ARG, "lora_rows: rank must be 8, 16, 32, 64 or 128");
   }
 #undef LTX_LORA_ROWS
   LTX_LAUNCH_CHECK();
@@ -611,13 +634,16 @@ extern "C" int ltx_lora_wgrad_grouped(const void* y, int64_t ldy, const float* u
       rps = (int)M;
     }
   }
-  const dim3 grid((unsigned)nb, (unsigned)splits, (unsigned)groups);
+  // ranks above 32: r / 32 rank slices per 128 columns (consecutive blockIdx.x)
+  const dim3 grid((unsigned)(nb * (r > 32 ? r / 32 : 1)), (unsigned)splits, (unsigned)groups);
   const int acc = accumulate ? 1 : 0;
   switch (r) {
     case 8: hipLaunchKernelGGL(lora_wgrad_kernel<8>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
     case 16: hipLaunchKernelGGL(lora_wgrad_kernel<16>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
     case 32: hipLaunchKernelGGL(lora_wgrad_kernel<32>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_wgrad: rank must be 8, 16 or 32");
+    case 64: hipLaunchKernelGGL(lora_wgrad_kernel<64>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
+    case 128: hipLaunchKernelGGL(lora_wgrad_kernel<128>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
+    default: return fail(LTX_ERR_BAD_ARG, "lora_wgrad: rank must be 8, 16, 32, 64 or 128");
   }
   LTX_LAUNCH_CHECK();
   if (part != nullptr) {

@@ -6,19 +6,21 @@
 // ltx_lora_wgrad, ~18.5 us each at M = 14336, N = 2048); here one LDS-DMA stream of dY feeds both
 // products on the bf16 matrix core, and a small second kernel finishes the sums.
 //
-// Block = 8 waves over 512 columns x G row groups of 32 rows (grid: N / 512 column splits x
-// ceil(M / 32G) row splits). Wave w owns columns c0 = 512 bx + 64 w .. +64 and streams its 32 x 64
+// Block = 8 waves over 512 columns x G row groups of 32 rows x one rank slice of SW <= 32 adapter
+// columns (grid: N / 512 column splits x r / SW rank slices in x, ceil(M / 32G) row splits in y;
+// G = 7, SW = 16 up to r = 16; G = 4, SW = 32 from r = 32 on: see dy_g / dy_sw below). Wave w owns columns c0 = 512 bx + 64 w .. +64 and streams its 32 x 64
 // slot of every row group (4 KiB, the attention tiles' chunk swizzle swz<64>) through a private
 // 4-slot ring, so no barrier is needed in the loop. Per slot:
-//   * w:  [32 rows x 16 j] += slot . (B^T pieces)^T: 12 v_mfma_f32_16x16x32_bf16 (2 row halves x
-//         2 k halves x 3 pieces), the B^T pieces (ltx_lora_pieces) in registers for the whole block;
-//   * dB: [16 j x 64 cols] += (u pieces)^T . slot: 12 MFMAs (4 column blocks x 3 pieces), the
+//   * w:  [32 rows x SW j] += slot . (B^T pieces)^T: 12 v_mfma_f32_16x16x32_bf16 per 16 j (2 row
+//         halves x 2 k halves x 3 pieces), the slice's B^T pieces (ltx_lora_pieces) in registers for
+//         the whole block;
+//   * dB: [SW j x 64 cols] += (u pieces)^T . slot: 12 MFMAs per 16 j (4 column blocks x 3 pieces), the
 //         slot read transposed (ds_read_b64_tr_b16, the attention dQ product's k-slot order), u
 //         split into exact hi / mid / lo bf16 pieces from an LDS copy of the block's u rows.
 // Exact bf16 products summed in f32, as ltx_lora_rows; the sums run in a different order than
 // ltx_lora_rows / ltx_lora_wgrad (f32 rounding differences only).
-// Partials (deterministic, no atomics): w over the 4 column splits [CS][M][RP], dB over the row
-// splits [RS][N][RP]; lora_dy_finish_kernel sums them in a fixed order, applies alpha, writes w,
+// Partials (deterministic, no atomics): w over the 4 column splits [CS][RP][M], dB over the row
+// splits [RS][N][RP] (a rank slice writes its own j range of both); lora_dy_finish_kernel sums them in a fixed order, applies alpha, writes w,
 // its [hi | hi | lo | 0..] split operand, and adds dB into the gradient buffer.
 #include <cstdlib>
 
@@ -31,11 +33,21 @@ namespace ltx {
 #define LTX_RF_NR 5
 #endif
 namespace {
-constexpr int DY_G = 7;      // row groups of 32 per block (14336 = 64 x 7 x 32)
 constexpr int DY_NR = 4;     // ring slots per wave
 constexpr int DY_COLS = 512; // columns per block
-constexpr int DY_UPAD = DY_G * 32 + 4;  // u^T row length in LDS (floats; +4 spreads the banks)
 constexpr int DY_MAXCS = 4;  // column splits a MODE-6 pass sums its u from (N <= 2048)
+// A block works on one rank slice of DY_SW(r) <= 32 columns of the adapter: the whole rank up to
+// r = 32, so dY is streamed from HBM once; ranks 64 / 128 run 2 / 4 slices per dY tile as
+// consecutive blockIdx.x of the same launch, each streaming the tile again (at 6r FLOP/B those
+// ranks sit at or past the matrix-core ridge, and the slice's B^T pieces (24 VGPRs per 16 columns),
+// accumulators and the 8 waves' w partials keep the r = 32 budget). Row groups of 32 per block:
+// 7 for 16-wide slices (14336 = 64 x 7 x 32), 4 for 32-wide ones -- the 8 waves' w partials,
+// 8 . 32 . (32 G + 4) . 4 B, must fit the ring plus the u^T area they overlay (147,968 B at G = 4;
+// G = 7 would need 236,544 B), and 4 divides config A's 448 row groups where 3 would not.
+constexpr int dy_sw(int r) { return r <= 16 ? 16 : 32; }
+constexpr int dy_g(int r) { return r <= 16 ? 7 : 4; }
+constexpr int dy_nsl(int r) { return r <= 32 ? 1 : r / 32; }
+constexpr bool dy_rank_ok(int64_t r) { return r == 8 || r == 16 || r == 32 || r == 64 || r == 128; }
 }  // namespace
 
 // MODE: bit 0 the w product, bit 1 the dB product. MODE 2 is ltx_lora_wgrad's token-sized path
@@ -51,19 +63,23 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
                                                       float* __restrict__ part_w, float* __restrict__ part_b,
                                                       int M, int N, const float* __restrict__ part_u, int CSu,
                                                       float alpha_u) {
-  constexpr int RP = R >= 16 ? R : 16;
-  constexpr int JT = RP / 16;
+  constexpr int RP = R >= 16 ? R : 16;    // padded rank: the stride of the pieces and of the partials
+  constexpr int SW = dy_sw(R);             // this block's rank slice j0 .. j0 + SW
+  constexpr int NSL = dy_nsl(R);
+  constexpr int DY_G = dy_g(R);
+  constexpr int DY_UPAD = DY_G * 32 + 4;   // u^T row length in LDS (floats; +4 spreads the banks)
+  constexpr int JT = SW / 16;
   constexpr int NF = 3 * JT;
   constexpr int RING = 8 * DY_NR * 4096;
-  constexpr int UT = RP * DY_UPAD * 4;
-  static_assert(R == 8 || R == 16, "rank 8 or 16 (the w partials of rank 32 would not fit the ring)");
-  static_assert(8 * DY_G * 32 * (RP + 1) * 4 <= RING, "w partials fit the ring");
+  constexpr int UT = SW * DY_UPAD * 4;
+  static_assert(dy_rank_ok(R), "rank 8, 16, 32, 64 or 128");
   // ONE shared array (the DMA target): the ring, then u^T of the block's rows
   __shared__ __attribute__((aligned(16))) char smem[RING + UT];
   float* ut = (float*)(smem + RING);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cs = blockIdx.x, rs = blockIdx.y;
+  const int cs = blockIdx.x / NSL, rs = blockIdx.y;
+  const int j0 = (blockIdx.x % NSL) * SW;
   const int c0 = cs * DY_COLS + wave * 64;
   const int mb = rs * DY_G * 32;
 
@@ -98,7 +114,7 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int t = 0; t < JT && (MODE & 1); ++t) {
-      const bf16_t* src = w3 + (int64_t)(p * RP + t * 16 + (lane & 15)) * ldw + c0 + (lane >> 4) * 8;
+      const bf16_t* src = w3 + (int64_t)(p * RP + j0 + t * 16 + (lane & 15)) * ldw + c0 + (lane >> 4) * 8;
       bp[0][p * JT + t] = *(const s16x8*)src;
       bp[1][p * JT + t] = *(const s16x8*)(src + 32);
     }
@@ -115,7 +131,7 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
 
   // u^T of rows mb .. mb + 32G (zero past M): all loads in flight before the first LDS write (a
   // rolled loop waited out one load round trip per element, ~2 us per block)
-  constexpr int UPT = (DY_G * 32 * RP + 511) / 512;
+  constexpr int UPT = (DY_G * 32 * SW + 511) / 512;
   float uv[UPT];
   if constexpr ((MODE & 4) != 0) {  // u from the w partials: e -> (j, row), rows fastest (coalesced)
     // every partial load in flight before the first add (CSu <= DY_MAXCS; loads past CSu or past the
@@ -123,36 +139,36 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
     float pv[UPT][DY_MAXCS];
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i, j = e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
-      const bool ok = e < DY_G * 32 * RP && m < M && j < R;
+      const int e = tid + 512 * i, j = j0 + e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
+      const bool ok = e < DY_G * 32 * SW && m < M && j < R;
 #pragma unroll
       for (int c = 0; c < DY_MAXCS; ++c)
         pv[i][c] = part_u[((int64_t)(c < CSu ? c : 0) * RP + (ok ? j : 0)) * M + (ok ? m : 0)];
     }
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i, j = e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
+      const int e = tid + 512 * i, j = j0 + e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
       float acc = 0.f;
 #pragma unroll
       for (int c = 0; c < DY_MAXCS; ++c)
         if (c < CSu) acc += pv[i][c];
-      uv[i] = (e < DY_G * 32 * RP && m < M && j < R) ? acc * alpha_u : 0.f;
+      uv[i] = (e < DY_G * 32 * SW && m < M && j < R) ? acc * alpha_u : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
       const int e = tid + 512 * i;
-      if (e < DY_G * 32 * RP) ut[(e / (DY_G * 32)) * DY_UPAD + e % (DY_G * 32)] = uv[i];
+      if (e < DY_G * 32 * SW) ut[(e / (DY_G * 32)) * DY_UPAD + e % (DY_G * 32)] = uv[i];
     }
   } else {
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i, rr = e / RP, j = e % RP, m = mb + rr;
-      uv[i] = ((MODE & 2) && e < DY_G * 32 * RP && m < M && j < R) ? u[(int64_t)m * ldu + j] : 0.f;
+      const int e = tid + 512 * i, rr = e / SW, j = j0 + e % SW, m = mb + rr;
+      uv[i] = ((MODE & 2) && e < DY_G * 32 * SW && m < M && j < R) ? u[(int64_t)m * ldu + j] : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < UPT; ++i) {
       const int e = tid + 512 * i;
-      if ((MODE & 2) && e < DY_G * 32 * RP) ut[(e % RP) * DY_UPAD + e / RP] = uv[i];
+      if ((MODE & 2) && e < DY_G * 32 * SW) ut[(e % SW) * DY_UPAD + e / SW] = uv[i];
     }
   }
   __syncthreads();  // u^T staged; every ordinary load retired before the counted waits below
@@ -253,34 +269,36 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
       const int n = c0 + 16 * nb + (lane & 15);
-      *(f32x4*)(part_b + ((int64_t)rs * N + n) * RP + 16 * t + 4 * g4) = bacc[t][nb];
+      *(f32x4*)(part_b + ((int64_t)rs * N + n) * RP + j0 + 16 * t + 4 * g4) = bacc[t][nb];
     }
   if constexpr (!(MODE & 1)) return;
   // w partial: the 8 waves' [j][32G rows] sums through LDS (the ring is free once all waves are
   // past their last slot; a C fragment's 4 values are 4 consecutive rows of one j: one 16-B write),
-  // then one column-split partial part_w[cs][j][m] per row quad (16-B reads and stores)
+  // then one column-split partial part_w[cs][j][m] per row quad (16-B reads and stores). The
+  // partials overlay the ring and, for 32-wide slices, the head of u^T (read for the last time
+  // before the barrier)
   __syncthreads();
   constexpr int WROW = DY_G * 32 + 4;  // floats per (wave, j) row; +4 spreads the banks
   float* part = (float*)smem;
-  static_assert(8 * RP * WROW * 4 <= RING, "w partials fit the ring");
+  static_assert(8 * SW * WROW * 4 <= RING + UT, "w partials fit the ring and the u^T area");
 #pragma unroll
   for (int g = 0; g < DY_G; ++g)
 #pragma unroll
     for (int q = 0; q < 2; ++q)
 #pragma unroll
       for (int t = 0; t < JT; ++t)
-        *(f32x4*)(part + (wave * RP + 16 * t + (lane & 15)) * WROW + 32 * g + 16 * q + 4 * g4) = wacc[g][q][t];
+        *(f32x4*)(part + (wave * SW + 16 * t + (lane & 15)) * WROW + 32 * g + 16 * q + 4 * g4) = wacc[g][q][t];
   __syncthreads();
-  for (int e = tid; e < RP * DY_G * 8; e += 512) {  // (j, row quad)
+  for (int e = tid; e < SW * DY_G * 8; e += 512) {  // (j, row quad)
     const int j = e / (DY_G * 8), r4 = 4 * (e % (DY_G * 8));
     if (mb + r4 >= M) continue;  // M % 32 == 0: a quad is all in or all out
     f32x4 sum = *(const f32x4*)(part + j * WROW + r4);
 #pragma unroll
     for (int w = 1; w < 8; ++w) {
-      const f32x4 v = *(const f32x4*)(part + (w * RP + j) * WROW + r4);
+      const f32x4 v = *(const f32x4*)(part + (w * SW + j) * WROW + r4);
       sum[0] += v[0]; sum[1] += v[1]; sum[2] += v[2]; sum[3] += v[3];
     }
-    *(f32x4*)(part_w + ((int64_t)cs * RP + j) * M + mb + r4) = sum;
+    *(f32x4*)(part_w + ((int64_t)cs * RP + j0 + j) * M + mb + r4) = sum;
   }
 }
 
@@ -386,13 +404,18 @@ __global__ __launch_bounds__(512) void lora_rows_full_kernel(const bf16_t* __res
                                                              float* __restrict__ out, int64_t ldo, int M, float alpha,
                                                              bf16_t* __restrict__ split, int64_t lds, int K2) {
   constexpr int RP = R >= 16 ? R : 16;
-  constexpr int JT = RP / 16;
+  // ranks above 16: 16-wide rank slices, one per blockIdx.y of the same launch (a wave keeps the
+  // pieces of its slice for all CH chunks in registers: 24 CH VGPRs per 16 columns); j0 = slice origin
+  constexpr int SW = 16;
+  constexpr int RW = R < SW ? R : SW;
+  constexpr int JT = SW / 16;
   constexpr int NF = 3 * JT;
   constexpr int NS = RG * CH;  // slots per wave
   constexpr int RING = 8 * NR * 4096;
   constexpr int PROW = RG * 32 + 4;  // floats per (wave, j) partial row; +4 spreads the banks
-  static_assert(R == 8 || R == 16, "rank 8 or 16");
-  static_assert(8 * RP * PROW * 4 <= RING, "wave partials fit the ring");
+  static_assert(dy_rank_ok(R), "rank 8, 16, 32, 64 or 128");
+  static_assert(8 * SW * PROW * 4 <= RING, "wave partials fit the ring");
+  const int j0 = blockIdx.y * SW;
   __shared__ __attribute__((aligned(16))) char smem[RING];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -432,7 +455,7 @@ __global__ __launch_bounds__(512) void lora_rows_full_kernel(const bf16_t* __res
     for (int p = 0; p < 3; ++p)
 #pragma unroll
       for (int t = 0; t < JT; ++t) {
-        const bf16_t* src = w3 + (int64_t)(p * RP + t * 16 + (lane & 15)) * ldw + c0 + 64 * c + (lane >> 4) * 8;
+        const bf16_t* src = w3 + (int64_t)(p * RP + j0 + t * 16 + (lane & 15)) * ldw + c0 + 64 * c + (lane >> 4) * 8;
         bp[c][0][p * JT + t] = *(const s16x8*)src;
         bp[c][1][p * JT + t] = *(const s16x8*)(src + 32);
       }
@@ -498,9 +521,9 @@ __global__ __launch_bounds__(512) void lora_rows_full_kernel(const bf16_t* __res
     for (int q = 0; q < 2; ++q)
 #pragma unroll
       for (int t = 0; t < JT; ++t)
-        *(f32x4*)(part + (wave * RP + 16 * t + (lane & 15)) * PROW + 32 * g + 16 * q + 4 * (lane >> 4)) = acc[g][q][t];
+        *(f32x4*)(part + (wave * SW + 16 * t + (lane & 15)) * PROW + 32 * g + 16 * q + 4 * (lane >> 4)) = acc[g][q][t];
   __syncthreads();
-  constexpr int NQ = R / 4;
+  constexpr int NQ = RW / 4;
   for (int e = tid; e < RG * 32 * NQ; e += 512) {
     const int q = e / (RG * 32), rr = e % (RG * 32), m = mb + rr;
     if (m >= M) continue;
@@ -509,10 +532,11 @@ __global__ __launch_bounds__(512) void lora_rows_full_kernel(const bf16_t* __res
     for (int k = 0; k < 4; ++k) {
       float v = part[(4 * q + k) * PROW + rr];
 #pragma unroll
-      for (int w = 1; w < 8; ++w) v += part[(w * RP + 4 * q + k) * PROW + rr];
+      for (int w = 1; w < 8; ++w) v += part[(w * SW + 4 * q + k) * PROW + rr];
       wv[k] = v * alpha;
     }
-    *(f32x4*)(out + (int64_t)m * ldo + 4 * q) = wv;
+    const int jq = j0 + 4 * q;  // the quad's first column in the whole rank
+    *(f32x4*)(out + (int64_t)m * ldo + jq) = wv;
     if (split == nullptr) continue;
     uint32_t hi[2], lo[2];
 #pragma unroll
@@ -522,10 +546,10 @@ __global__ __launch_bounds__(512) void lora_rows_full_kernel(const bf16_t* __res
       lo[k] = (uint32_t)f2bf(wv[2 * k] - bf2f(h0)) | ((uint32_t)f2bf(wv[2 * k + 1] - bf2f(h1)) << 16);
     }
     bf16_t* sr = split + (int64_t)m * lds;
-    *(u32x2*)(sr + 4 * q) = (u32x2){hi[0], hi[1]};
-    *(u32x2*)(sr + R + 4 * q) = (u32x2){hi[0], hi[1]};
-    *(u32x2*)(sr + 2 * R + 4 * q) = (u32x2){lo[0], lo[1]};
-    for (int cc = 3 * R + 4 * q; cc < K2; cc += R) *(u32x2*)(sr + cc) = (u32x2){0u, 0u};
+    *(u32x2*)(sr + jq) = (u32x2){hi[0], hi[1]};
+    *(u32x2*)(sr + R + jq) = (u32x2){hi[0], hi[1]};
+    *(u32x2*)(sr + 2 * R + jq) = (u32x2){lo[0], lo[1]};
+    for (int cc = 3 * R + jq; cc < K2; cc += R) *(u32x2*)(sr + cc) = (u32x2){0u, 0u};
   }
 }
 
@@ -540,14 +564,15 @@ bool lora_wgrad_rows(const bf16_t* y, int64_t ldy, const float* u, int64_t ldu, 
     const char* e = getenv("LTX_LORA_WGRAD_ROWS");
     return e ? atoi(e) : 1;
   }();
-  if (!enabled || M < 2048 || M % 32 != 0 || N % DY_COLS != 0 || (r != 8 && r != 16)) return false;
+  if (!enabled || M < 2048 || M % 32 != 0 || N % DY_COLS != 0 || !dy_rank_ok(r)) return false;
   if (ldy % 8 != 0 || ((uintptr_t)y % 16) != 0 || ldy * 2 * 32 >= ((int64_t)1 << 32) || ldu < r) return false;
   const int64_t RP = r >= 16 ? r : 16;
+  const int DY_G = dy_g((int)r);
   const int RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
   size_t ws = 0;
   float* pb = stream_workspace(s, &ws);
   if (pb == nullptr || (size_t)RS * N * RP * sizeof(float) > ws) return false;
-  const dim3 grid((unsigned)(N / DY_COLS), (unsigned)RS);
+  const dim3 grid((unsigned)(N / DY_COLS * dy_nsl((int)r)), (unsigned)RS);
   const dim3 g2((unsigned)((N * r + 63) / 64));
 #define LTX_LORA_WG(RR)                                                                                       \
   hipLaunchKernelGGL((lora_dy_kernel<RR, 2>), grid, dim3(512), 0, s, y, ldy, u, ldu, nullptr, (int64_t)0, \
@@ -555,10 +580,12 @@ bool lora_wgrad_rows(const bf16_t* y, int64_t ldy, const float* u, int64_t ldu, 
   hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), g2, dim3(256), 0, s, nullptr, 0, pb, RS, (int)M, (int)N,    \
                      alpha, nullptr, (int64_t)0, nullptr, (int64_t)0, 0, dw, on, oj, accumulate, 0, 1 << 30,   \
                      (const float*)nullptr, 0, 1.f, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
-  if (r == 8) {
-    LTX_LORA_WG(8)
-  } else {
-    LTX_LORA_WG(16)
+  switch (r) {
+    case 8: LTX_LORA_WG(8) break;
+    case 16: LTX_LORA_WG(16) break;
+    case 32: LTX_LORA_WG(32) break;
+    case 64: LTX_LORA_WG(64) break;
+    default: LTX_LORA_WG(128) break;
   }
 #undef LTX_LORA_WG
   return true;
@@ -575,7 +602,7 @@ bool lora_rows_dy(const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, f
     const char* e = getenv("LTX_LORA_ROWS_DY");
     return e ? atoi(e) : 1;
   }();
-  if (!enabled || M < 2048 || M % 32 != 0 || K % DY_COLS != 0 || (r != 8 && r != 16)) return false;
+  if (!enabled || M < 2048 || M % 32 != 0 || K % DY_COLS != 0 || !dy_rank_ok(r)) return false;
   if (ldx % 8 != 0 || ((uintptr_t)x % 16) != 0 || ldx * 2 * 32 >= ((int64_t)1 << 32)) return false;
   if (ldw % 8 != 0 || ((uintptr_t)w3 % 16) != 0 || ldw < K) return false;
   if (ldo % 4 != 0 || ((uintptr_t)out % 16) != 0) return false;
@@ -588,25 +615,31 @@ bool lora_rows_dy(const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, f
   }();
   if (full && (K == 512 || K == 1024 || K == 2048)) {
     constexpr int RG = 2, NRF = LTX_RF_NR;
-    const dim3 gf((unsigned)((M + RG * 32 - 1) / (RG * 32)));
+    const dim3 gf((unsigned)((M + RG * 32 - 1) / (RG * 32)), (unsigned)(r > 16 ? r / 16 : 1));  // y: rank slices
 #define LTX_LORA_RF(RR, CHH)                                                                                  \
   hipLaunchKernelGGL((lora_rows_full_kernel<RR, RG, CHH, NRF>), gf, dim3(512), 0, s, x, ldx, w3, ldw, out, ldo, (int)M, \
                      alpha, split, ld_split, (int)K2)
     const int ch = (int)(K / 512);
-    if (r == 8) {
-      if (ch == 1) LTX_LORA_RF(8, 1); else if (ch == 2) LTX_LORA_RF(8, 2); else LTX_LORA_RF(8, 4);
-    } else {
-      if (ch == 1) LTX_LORA_RF(16, 1); else if (ch == 2) LTX_LORA_RF(16, 2); else LTX_LORA_RF(16, 4);
+#define LTX_LORA_RFC(RR) \
+  if (ch == 1) LTX_LORA_RF(RR, 1); else if (ch == 2) LTX_LORA_RF(RR, 2); else LTX_LORA_RF(RR, 4)
+    switch (r) {
+      case 8: LTX_LORA_RFC(8); break;
+      case 16: LTX_LORA_RFC(16); break;
+      case 32: LTX_LORA_RFC(32); break;
+      case 64: LTX_LORA_RFC(64); break;
+      default: LTX_LORA_RFC(128); break;
     }
+#undef LTX_LORA_RFC
 #undef LTX_LORA_RF
     return true;
   }
   const int64_t RP = r >= 16 ? r : 16;
+  const int DY_G = dy_g((int)r);
   const int CS = (int)(K / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
   size_t ws = 0;
   float* pw = stream_workspace(s, &ws);
   if (pw == nullptr || (size_t)CS * M * RP * sizeof(float) > ws) return false;
-  const dim3 grid((unsigned)CS, (unsigned)RS);
+  const dim3 grid((unsigned)(CS * dy_nsl((int)r)), (unsigned)RS);
   const dim3 g2((unsigned)((M * (r / 4) + 255) / 256));
   const int nwb = (int)g2.x;
 #define LTX_LORA_RW(RR)                                                                                      \
@@ -615,18 +648,21 @@ bool lora_rows_dy(const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, f
   hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), g2, dim3(256), 0, s, pw, CS, nullptr, 0, (int)M, (int)K,    \
                      alpha, out, ldo, split, ld_split, (int)K2, nullptr, (int64_t)0, (int64_t)0, 0, nwb, 1 << 30, \
                      (const float*)nullptr, 0, 1.f, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
-  if (r == 8) {
-    LTX_LORA_RW(8)
-  } else {
-    LTX_LORA_RW(16)
+  switch (r) {
+    case 8: LTX_LORA_RW(8) break;
+    case 16: LTX_LORA_RW(16) break;
+    case 32: LTX_LORA_RW(32) break;
+    case 64: LTX_LORA_RW(64) break;
+    default: LTX_LORA_RW(128) break;
   }
 #undef LTX_LORA_RW
   return true;
 }
 
 extern "C" int ltx_lora_dy_workspace(int64_t M, int64_t N, int64_t r, int64_t* floats) {
-  LTX_CHECK_ARG(floats && M > 0 && N > 0 && (r == 8 || r == 16), "lora_dy_workspace: bad args");
+  LTX_CHECK_ARG(floats && M > 0 && N > 0 && dy_rank_ok(r), "lora_dy_workspace: bad args (rank 8, 16, 32, 64 or 128)");
   const int64_t RP = r >= 16 ? r : 16;
+  const int64_t DY_G = dy_g((int)r);
   const int64_t CS = N / DY_COLS, RS = (M + DY_G * 32 - 1) / (DY_G * 32);
   *floats = CS * M * RP + RS * N * RP;
   return LTX_OK;
@@ -637,8 +673,8 @@ extern "C" int ltx_lora_dy(const void* y, int64_t ldy, const float* u, int64_t l
                            int64_t ld_split, int64_t K2, float* dw, int64_t on, int64_t oj, int accumulate,
                            float* workspace, void* stream) {
   LTX_CHECK_ARG(y && u && w3 && w && split && dw && workspace, "lora_dy: null operand");
-  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && (r == 8 || r == 16),
-                "lora_dy: M % 32 == 0, N % 512 == 0, rank 8 or 16");
+  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && dy_rank_ok(r),
+                "lora_dy: M % 32 == 0, N % 512 == 0, rank 8, 16, 32, 64 or 128");
   LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldw3 % 8 == 0 && ((uintptr_t)w3 % 16) == 0 && ldw3 >= N,
                 "lora_dy: 16-B aligned rows of dY and of the pieces");
   LTX_CHECK_ARG(ldy * 2 * 32 < ((int64_t)1 << 32), "lora_dy: 32-bit DMA offsets");
@@ -647,11 +683,12 @@ extern "C" int ltx_lora_dy(const void* y, int64_t ldy, const float* u, int64_t l
                 "lora_dy: 16-B aligned w rows, 8-B aligned split rows");
   LTX_CHECK_ARG((on == r && oj == 1) || (on == 1 && oj == N), "lora_dy: dB must be a dense [N,r] or [r,N]");
   const int64_t RP = r >= 16 ? r : 16;
+  const int DY_G = dy_g((int)r);
   const int CS = (int)(N / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
   float* pw = workspace;
   float* pb = workspace + (int64_t)CS * M * RP;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)CS, (unsigned)RS);
+  const dim3 grid((unsigned)(CS * dy_nsl((int)r)), (unsigned)RS);
   const int nwb = (int)((M * (r / 4) + 255) / 256);
   const dim3 g2((unsigned)(nwb + (N * r + 63) / 64));
 #define LTX_LORA_DY(RR)                                                                                          \
@@ -664,7 +701,10 @@ extern "C" int ltx_lora_dy(const void* y, int64_t ldy, const float* u, int64_t l
   switch (r) {
     case 8: LTX_LORA_DY(8) break;
     case 16: LTX_LORA_DY(16) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_dy: rank must be 8 or 16");
+    case 32: LTX_LORA_DY(32) break;
+    case 64: LTX_LORA_DY(64) break;
+    case 128: LTX_LORA_DY(128) break;
+    default: return fail(LTX_ERR_BAD_ARG, "lora_dy: rank must be 8, 16, 32, 64 or 128");
   }
 #undef LTX_LORA_DY
   LTX_LAUNCH_CHECK();
@@ -672,8 +712,10 @@ extern "C" int ltx_lora_dy(const void* y, int64_t ldy, const float* u, int64_t l
 }
 
 extern "C" int ltx_lora_dy_dA_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t* floats) {
-  LTX_CHECK_ARG(floats && M > 0 && N > 0 && K > 0 && (r == 8 || r == 16), "lora_dy_dA_workspace: bad args");
+  LTX_CHECK_ARG(floats && M > 0 && N > 0 && K > 0 && dy_rank_ok(r),
+                "lora_dy_dA_workspace: bad args (rank 8, 16, 32, 64 or 128)");
   const int64_t RP = r >= 16 ? r : 16;
+  const int64_t DY_G = dy_g((int)r);
   const int64_t CS = N / DY_COLS, RS = (M + DY_G * 32 - 1) / (DY_G * 32);
   *floats = CS * M * RP + RS * N * RP + RS * K * RP;
   return LTX_OK;
@@ -689,8 +731,8 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
                               int64_t on, int64_t oj, int accumulate, float alpha_a, float* dwa, int64_t ona,
                               int64_t oja, int acc_a, float* workspace, void* stream) {
   LTX_CHECK_ARG(y && u && w3 && x && w && split && dw && dwa && workspace, "lora_dy_dA: null operand");
-  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && K % DY_COLS == 0 && (r == 8 || r == 16),
-                "lora_dy_dA: M % 32 == 0, N % 512 == 0, K % 512 == 0, rank 8 or 16");
+  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && K % DY_COLS == 0 && dy_rank_ok(r),
+                "lora_dy_dA: M % 32 == 0, N % 512 == 0, K % 512 == 0, rank 8, 16, 32, 64 or 128");
   LTX_CHECK_ARG(N <= DY_MAXCS * DY_COLS, "lora_dy_dA: N <= 2048 (the dA pass sums w from <= 4 column splits)");
   LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldw3 % 8 == 0 && ((uintptr_t)w3 % 16) == 0 && ldw3 >= N,
                 "lora_dy_dA: 16-B aligned rows of dY and of the pieces");
@@ -704,6 +746,7 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
   LTX_CHECK_ARG((on == r && oj == 1) || (on == 1 && oj == N), "lora_dy_dA: dB must be a dense [N,r] or [r,N]");
   LTX_CHECK_ARG((ona == r && oja == 1) || (ona == 1 && oja == K), "lora_dy_dA: dA must be a dense [K,r] or [r,K]");
   const int64_t RP = r >= 16 ? r : 16;
+  const int DY_G = dy_g((int)r), NSL = dy_nsl((int)r);
   const int CS = (int)(N / DY_COLS), CSx = (int)(K / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
   float* pw = workspace;
   float* pb = pw + (int64_t)CS * M * RP;
@@ -712,10 +755,10 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
   const int nwb = (int)((M * (r / 4) + 255) / 256);
   const int nbb = (int)((N * r + 63) / 64), nba = (int)((K * r + 63) / 64);
 #define LTX_LORA_DYA(RR)                                                                                           \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 3>), dim3((unsigned)CS, (unsigned)RS), dim3(512), 0, s, (const bf16_t*)y, \
+  hipLaunchKernelGGL((lora_dy_kernel<RR, 3>), dim3((unsigned)(CS * NSL), (unsigned)RS), dim3(512), 0, s, (const bf16_t*)y, \
                      ldy, u, ldu, (const bf16_t*)w3, ldw3, pw, pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f);  \
   LTX_LAUNCH_CHECK();                                                                                              \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 6>), dim3((unsigned)CSx, (unsigned)RS), dim3(512), 0, s,                 \
+  hipLaunchKernelGGL((lora_dy_kernel<RR, 6>), dim3((unsigned)(CSx * NSL), (unsigned)RS), dim3(512), 0, s,         \
                      (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr, (int64_t)0, \
                      (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, CS, alpha);                             \
   LTX_LAUNCH_CHECK();                                                                                              \
@@ -725,7 +768,10 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
   switch (r) {
     case 8: LTX_LORA_DYA(8) break;
     case 16: LTX_LORA_DYA(16) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_dy_dA: rank must be 8 or 16");
+    case 32: LTX_LORA_DYA(32) break;
+    case 64: LTX_LORA_DYA(64) break;
+    case 128: LTX_LORA_DYA(128) break;
+    default: return fail(LTX_ERR_BAD_ARG, "lora_dy_dA: rank must be 8, 16, 32, 64 or 128");
   }
 #undef LTX_LORA_DYA
   LTX_LAUNCH_CHECK();

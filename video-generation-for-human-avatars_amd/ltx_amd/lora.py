@@ -8,6 +8,7 @@ it until the wgrad path (next row) lands.
 """
 import torch
 
+from . import ops
 from .transformer3d import LoraLinear
 
 
@@ -20,6 +21,7 @@ def lora_target_modules(num_blocks):
 
 
 def inject_lora(model, targets, r, alpha):
+    ops.check_lora_rank(r)  # before the first module is replaced
     for name in targets:
         parent_name, _, child = name.rpartition(".")
         parent = model.get_submodule(parent_name)

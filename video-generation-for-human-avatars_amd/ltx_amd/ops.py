@@ -706,6 +706,18 @@ def bump_weight_generation():
     _WEIGHT_GENERATION[0] += 1
 
 
+LORA_RANKS = (8, 16, 32, 64, 128)  # the ranks every adapter kernel is built for
+
+
+def check_lora_rank(r):
+    """ValueError for a LoRA rank the adapter kernels are not built for (raised where adapters are
+    created or adopted, ahead of any kernel launch)."""
+    if isinstance(r, bool) or not isinstance(r, int) or r not in LORA_RANKS:
+        raise ValueError(f"LoRA rank {r!r} is not supported: the fused adapter kernels are built for ranks "
+                         f"{', '.join(str(x) for x in LORA_RANKS)}")
+    return r
+
+
 def lora_k2(r):
     return (3 * r + 63) // 64 * 64
 
@@ -769,7 +781,7 @@ def lora_dy_da_fits(y, x, r):
 
 def lora_dy_fits(y, r):
     M, N = y.shape
-    return r in (8, 16) and M % 32 == 0 and N % 512 == 0 and y.stride(1) == 1 and y.stride(0) % 8 == 0
+    return r in LORA_RANKS and M % 32 == 0 and N % 512 == 0 and y.stride(1) == 1 and y.stride(0) % 8 == 0
 
 
 def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=None, dA_out=None,

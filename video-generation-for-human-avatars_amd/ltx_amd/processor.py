@@ -37,6 +37,7 @@ def _linear_parts(m):
         if drop is not None and "default" in drop and getattr(drop["default"], "p", 0.0) > 0 and m.training:
             raise NotImplementedError("HipAttnProcessor: LoRA dropout > 0 is not supported")
         sc = m.scaling["default"] if isinstance(m.scaling, dict) else m.scaling
+        ops.check_lora_rank(int(m.lora_A["default"].weight.shape[0]))
         return base.weight, base.bias, m.lora_A["default"].weight, m.lora_B["default"].weight, float(sc)
     return m.weight, m.bias, None, None, 1.0
 

@@ -100,7 +100,7 @@ class LoraLinear(nn.Module):
     def __init__(self, base_layer: nn.Linear, r: int, lora_alpha: int):
         super().__init__()
         self.base_layer = base_layer
-        self.r = r
+        self.r = ops.check_lora_rank(r)
         self.lora_alpha = lora_alpha
         self.scaling = lora_alpha / r
         dev = base_layer.weight.device
