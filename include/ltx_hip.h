@@ -350,6 +350,34 @@ int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_t ldu, cons
                    int64_t on, int64_t oj, int accumulate, float alpha_a, float* dwa, int64_t ona,
                    int64_t oja, int acc_a, float* workspace, void* stream);
 int ltx_lora_dy_dA_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t* floats);
+/* ltx_lora_rows for `groups` (<= 4) adapters of one rank that share x (the q / k / v adapters of a
+ * LoRA-wrapped self-attention: one modulated norm output, three lora_A): w3[g] = group g's
+ * ltx_lora_pieces (host array of device pointers), group g writes out + g*go and split + g*gs
+ * (element offsets: column blocks of shared [M, .] buffers). One launch with (group, rank slice)
+ * as a grid dimension wherever ltx_lora_rows runs its whole-contraction kernel (M >= 2048,
+ * M % 32 == 0, K = 512 / 1024 / 2048), so each row tile of x leaves HBM once; elsewhere the
+ * one-adapter calls. Every output is bitwise ltx_lora_rows' on the same operands. */
+int ltx_lora_rows_grouped(const void* x, int64_t ldx, const void* const* w3, int64_t ldw, float* out,
+                          int64_t ldo, int64_t go, int64_t M, int64_t K, int64_t r, float alpha,
+                          void* split, int64_t ld_split, int64_t K2, int64_t gs, int64_t groups,
+                          void* stream);
+/* ltx_lora_dy_dA for `groups` (<= 4) adapters of one rank on the column blocks of a packed dY
+ * [M, groups*N] (ldy; group g = columns g*N ..) that share X (the fused dQKV and the self-attention's
+ * input): u[g], w3[g] (pieces of B_g^T), dw[g], dwa[g] are host arrays of device pointers; group g's
+ * w goes to w + g*gw, its split row to split + g*gs (column blocks of shared [M, .] buffers). Three
+ * launches (the dY pass with the groups as a grid dimension, one pass over X serving all groups * r
+ * columns of w, one finish) instead of three per adapter; X leaves HBM once. Deterministic (no
+ * atomics); every output bitwise ltx_lora_dy_dA's on the column slice.
+ * workspace: ltx_lora_dy_dA_grouped_workspace floats. */
+int ltx_lora_dy_dA_grouped(const void* y, int64_t ldy, const float* const* u, int64_t ldu,
+                           const void* const* w3, int64_t ldw3, const void* x, int64_t ldx, int64_t M,
+                           int64_t N, int64_t K, int64_t r, int64_t groups, float alpha, float* w,
+                           int64_t ldw_out, int64_t gw, void* split, int64_t ld_split, int64_t K2,
+                           int64_t gs, float* const* dw, int64_t on, int64_t oj, int accumulate,
+                           float alpha_a, float* const* dwa, int64_t ona, int64_t oja, int acc_a,
+                           float* workspace, void* stream);
+int ltx_lora_dy_dA_grouped_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups,
+                                     int64_t* floats);
 
 /* ---- small ops -------------------------------------------------------------------------------- */
 /* AdaLayerNormSingle sinusoid: out[b,:] = bf16([cos(s*t*f), sin(s*t*f)]) (256 ch), s = scale */

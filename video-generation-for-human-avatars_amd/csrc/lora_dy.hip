@@ -22,6 +22,12 @@
 // Partials (deterministic, no atomics): w over the 4 column splits [CS][RP][M], dB over the row
 // splits [RS][N][RP] (a rank slice writes its own j range of both); lora_dy_finish_kernel sums them in a fixed order, applies alpha, writes w,
 // its [hi | hi | lo | 0..] split operand, and adds dB into the gradient buffer.
+//
+// Grouped launches (ltx_lora_rows_grouped, ltx_lora_dy_dA_grouped): up to 4 adapters of one rank that
+// share an input (the q / k / v adapters of a LoRA-wrapped self-attention) in one launch per kernel.
+// The block programs live in lora_dy_bodies.h and are included into the one-adapter kernels and
+// into their grouped twins, which only map a group's block index and operands: every output keeps
+// the one-adapter kernel's summation order (bitwise the separate calls).
 #include <cstdlib>
 
 #include "attention_common.h"
@@ -63,243 +69,63 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
                                                       float* __restrict__ part_w, float* __restrict__ part_b,
                                                       int M, int N, const float* __restrict__ part_u, int CSu,
                                                       float alpha_u) {
-  constexpr int RP = R >= 16 ? R : 16;    // padded rank: the stride of the pieces and of the partials
-  constexpr int SW = dy_sw(R);             // this block's rank slice j0 .. j0 + SW
-  constexpr int NSL = dy_nsl(R);
-  constexpr int DY_G = dy_g(R);
-  constexpr int DY_UPAD = DY_G * 32 + 4;   // u^T row length in LDS (floats; +4 spreads the banks)
-  constexpr int JT = SW / 16;
-  constexpr int NF = 3 * JT;
-  constexpr int RING = 8 * DY_NR * 4096;
-  constexpr int UT = SW * DY_UPAD * 4;
-  static_assert(dy_rank_ok(R), "rank 8, 16, 32, 64 or 128");
-  // ONE shared array (the DMA target): the ring, then u^T of the block's rows
-  __shared__ __attribute__((aligned(16))) char smem[RING + UT];
-  float* ut = (float*)(smem + RING);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cs = blockIdx.x / NSL, rs = blockIdx.y;
-  const int j0 = (blockIdx.x % NSL) * SW;
-  const int c0 = cs * DY_COLS + wave * 64;
-  const int mb = rs * DY_G * 32;
+#define DY_BX blockIdx.x
+#define DY_BY blockIdx.y
+#define LTX_DY_BODY 1
+#include "lora_dy_bodies.h"
+#undef LTX_DY_BODY
+#undef DY_BX
+#undef DY_BY
+}
 
-  // DMA: piece i of a slot = rows 8i .. 8i+7; lane -> row 8i + (lane >> 3), physical chunk lane & 7
-  uint32_t yo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = 8 * i + (lane >> 3);
-    yo[i] = (uint32_t)(row * ldy + (((lane & 7) ^ swz<64>(row)) * 8)) * 2;
-  }
-  const uint32_t lring = lds_u32(smem + wave * (DY_NR * 4096));
-  auto dma = [&](int g) {
-    const char* sb = (const char*)(y + (int64_t)(mb + 32 * g) * ldy + c0);  // M % 32 == 0
-    const uint32_t l = lring + (g % DY_NR) * 4096;
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(yo[0]), "v"(yo[1]), "v"(yo[2]), "v"(yo[3]), "s"(sb), "s"(l)
-        : "memory", "scc");
-  };
-  const int ng = min(DY_G, (M - mb + 31) / 32);  // row groups of this block
-  // B^T pieces of this wave's 64 columns: [k half][piece x JT] (ltx_lora_rows' fragment layout).
-  // Loaded first and retired, then handed to hipcc as asm outputs: its own waits for these loads
-  // are counted without the asm DMA, and inside the slot loop they drained the prefetched slots
-  // (vmcnt(5) .. vmcnt(0) before every slot's MFMAs)
-  s16x8 bp[2][NF];
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int t = 0; t < JT && (MODE & 1); ++t) {
-      const bf16_t* src = w3 + (int64_t)(p * RP + j0 + t * 16 + (lane & 15)) * ldw + c0 + (lane >> 4) * 8;
-      bp[0][p * JT + t] = *(const s16x8*)src;
-      bp[1][p * JT + t] = *(const s16x8*)(src + 32);
-    }
-  if constexpr ((MODE & 1) != 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int f = 0; f < NF; ++f) asm volatile("" : "+v"(bp[h][f]));
-  }
-  // the first slots' DMA goes out ahead of the u^T staging loads, so their latencies overlap
-  for (int g = 0; g < DY_NR - 1; ++g)
-    if (g < ng) dma(g);
+// Per-group operands of the grouped launches (kernel arguments by value; G <= LORA_MAX_GROUPS)
+constexpr int LORA_MAX_GROUPS = 4;
+struct DyGroupPtrs {
+  const float* u[LORA_MAX_GROUPS];
+  const bf16_t* w3[LORA_MAX_GROUPS];
+  float* dw[LORA_MAX_GROUPS];
+  float* dwa[LORA_MAX_GROUPS];
+};
 
-  // u^T of rows mb .. mb + 32G (zero past M): all loads in flight before the first LDS write (a
-  // rolled loop waited out one load round trip per element, ~2 us per block)
-  constexpr int UPT = (DY_G * 32 * SW + 511) / 512;
-  float uv[UPT];
-  if constexpr ((MODE & 4) != 0) {  // u from the w partials: e -> (j, row), rows fastest (coalesced)
-    // every partial load in flight before the first add (CSu <= DY_MAXCS; loads past CSu or past the
-    // block's rows read partial 0 / row 0 and are not added); then the sum in c order from 0
-    float pv[UPT][DY_MAXCS];
-#pragma unroll
-    for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i, j = j0 + e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
-      const bool ok = e < DY_G * 32 * SW && m < M && j < R;
-#pragma unroll
-      for (int c = 0; c < DY_MAXCS; ++c)
-        pv[i][c] = part_u[((int64_t)(c < CSu ? c : 0) * RP + (ok ? j : 0)) * M + (ok ? m : 0)];
-    }
-#pragma unroll
-    for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i, j = j0 + e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < DY_MAXCS; ++c)
-        if (c < CSu) acc += pv[i][c];
-      uv[i] = (e < DY_G * 32 * SW && m < M && j < R) ? acc * alpha_u : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i;
-      if (e < DY_G * 32 * SW) ut[(e / (DY_G * 32)) * DY_UPAD + e % (DY_G * 32)] = uv[i];
-    }
+// lora_dy_kernel for G adapters on the column blocks of one packed dY [M, G N] (the fused QKV
+// gradient) that share the input x. Every group runs the one-adapter block program on its own
+// operands, so each output is bitwise the one-adapter launch's.
+// MODE 3 (the dY pass): group = blockIdx.z; dY columns from g*gy, the partials of group g at
+// part_w + g*gpw / part_b + g*gpb.
+// MODE 6 (the x pass): the G * NSL (group, rank slice) pairs of one 512-column tile of x are
+// consecutive blockIdx.x, so the tile is fetched from HBM once and serves all G r columns of w
+// (the later slices hit L2 / MALL, as the rank slices of one adapter do); w of group g is summed
+// from part_u + g*gpu, its dA partials go to part_b + g*gpb.
+template <int R, int MODE>
+__global__ __launch_bounds__(512) void lora_dy_grouped_kernel(const bf16_t* __restrict__ y0, int64_t ldy,
+                                                              DyGroupPtrs gp, int64_t ldu, int64_t ldw,
+                                                              float* __restrict__ part_w0,
+                                                              float* __restrict__ part_b0, int M, int N,
+                                                              const float* __restrict__ part_u0, int CSu,
+                                                              float alpha_u, int G, int64_t gy, int64_t gpw,
+                                                              int64_t gpb, int64_t gpu) {
+  unsigned g, gbx;
+  if constexpr ((MODE & 4) != 0) {
+    constexpr unsigned NSLG = dy_nsl(R);
+    g = (blockIdx.x / NSLG) % (unsigned)G;
+    gbx = (blockIdx.x / (NSLG * (unsigned)G)) * NSLG + blockIdx.x % NSLG;
   } else {
-#pragma unroll
-    for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i, rr = e / SW, j = j0 + e % SW, m = mb + rr;
-      uv[i] = ((MODE & 2) && e < DY_G * 32 * SW && m < M && j < R) ? u[(int64_t)m * ldu + j] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < UPT; ++i) {
-      const int e = tid + 512 * i;
-      if ((MODE & 2) && e < DY_G * 32 * SW) ut[(e % SW) * DY_UPAD + e / SW] = uv[i];
-    }
+    g = blockIdx.z;
+    gbx = blockIdx.x;
   }
-  __syncthreads();  // u^T staged; every ordinary load retired before the counted waits below
-
-  // row reads (w product): rows 16q + (lane & 15), logical chunk 4h + (lane >> 4)
-  int roff[2][2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int row = 16 * q + (lane & 15);
-      roff[q][h] = row * 128 + (((4 * h + (lane >> 4)) ^ swz<64>(row)) * 16);
-    }
-  // transposed reads (dB product): k-slot 8g + jj = row 4g + jj (jj < 4) / 16 + 4g + jj - 4
-  const int g4 = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-  int toffs[4];
-#pragma unroll
-  for (int nb = 0; nb < 4; ++nb) toffs[nb] = toff<64>(4 * g4 + qq, 2 * nb + (pp >> 1)) + 8 * (pp & 1);
-  auto tr4 = [](const char* a) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-  };
-
-  f32x4 wacc[DY_G][2][JT];
-  f32x4 bacc[JT][4];
-#pragma unroll
-  for (int t = 0; t < JT; ++t)
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) bacc[t][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int g = 0; g < DY_G; ++g) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < JT; ++t) wacc[g][q][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (g >= ng) continue;
-    // slot g landed: only the slots issued after it (at most DY_NR - 2) stay in flight
-    const int younger = min(DY_NR - 2, ng - 1 - g);
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const char* sl = smem + wave * (DY_NR * 4096) + (g % DY_NR) * 4096;
-    s16x8 xf[2][2];
-#pragma unroll
-    for (int q = 0; q < 2 && (MODE & 1); ++q)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) xf[q][h] = *(const s16x8*)(sl + roff[q][h]);
-    s16x8 yb[4];
-#pragma unroll
-    for (int nb = 0; nb < 4 && (MODE & 2); ++nb) {
-      const s16x4 b0 = tr4(sl + toffs[nb]), b1 = tr4(sl + toffs[nb] + 16 * 128);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        yb[nb][j] = b0[j];
-        yb[nb][4 + j] = b1[j];
-      }
-    }
-    // u pieces of this group's rows in the k-slot order: [piece][t]
-    s16x8 up[3][JT];
-#pragma unroll
-    for (int t = 0; t < JT && (MODE & 2); ++t) {
-      const float* ur = ut + (16 * t + (lane & 15)) * DY_UPAD + 32 * g + 4 * g4;
-      const f32x4 lo4 = *(const f32x4*)ur, hi4 = *(const f32x4*)(ur + 16);
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const float v = jj < 4 ? lo4[jj] : hi4[jj - 4];
-        const bf16_t a = f2bf(v);
-        const float r1 = v - bf2f(a);
-        const bf16_t b = f2bf(r1);
-        const bf16_t c = f2bf(r1 - bf2f(b));
-        up[0][t][jj] = (short)a;
-        up[1][t][jj] = (short)b;
-        up[2][t][jj] = (short)c;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slot g read: its ring slot may be refilled
-    if (g + DY_NR - 1 < ng) dma(g + DY_NR - 1);
-#pragma unroll
-    for (int h = 0; h < 2 && (MODE & 1); ++h)
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int t = 0; t < JT; ++t)
-#pragma unroll
-          for (int q = 0; q < 2; ++q)
-            wacc[g][q][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[q][h], bp[h][p * JT + t], wacc[g][q][t], 0, 0, 0);
-#pragma unroll
-    for (int p = 0; p < 3 && (MODE & 2); ++p)
-#pragma unroll
-      for (int t = 0; t < JT; ++t)
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-          bacc[t][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(up[p][t], yb[nb], bacc[t][nb], 0, 0, 0);
-  }
-  // dB partial: C[j][n] -> part_b[rs][n][j], lane: n = c0 + 16 nb + (lane & 15), j = 16t + 4 g4 + 0..3
-#pragma unroll
-  for (int t = 0; t < JT && (MODE & 2); ++t)
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-      const int n = c0 + 16 * nb + (lane & 15);
-      *(f32x4*)(part_b + ((int64_t)rs * N + n) * RP + j0 + 16 * t + 4 * g4) = bacc[t][nb];
-    }
-  if constexpr (!(MODE & 1)) return;
-  // w partial: the 8 waves' [j][32G rows] sums through LDS (the ring is free once all waves are
-  // past their last slot; a C fragment's 4 values are 4 consecutive rows of one j: one 16-B write),
-  // then one column-split partial part_w[cs][j][m] per row quad (16-B reads and stores). The
-  // partials overlay the ring and, for 32-wide slices, the head of u^T (read for the last time
-  // before the barrier)
-  __syncthreads();
-  constexpr int WROW = DY_G * 32 + 4;  // floats per (wave, j) row; +4 spreads the banks
-  float* part = (float*)smem;
-  static_assert(8 * SW * WROW * 4 <= RING + UT, "w partials fit the ring and the u^T area");
-#pragma unroll
-  for (int g = 0; g < DY_G; ++g)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < JT; ++t)
-        *(f32x4*)(part + (wave * SW + 16 * t + (lane & 15)) * WROW + 32 * g + 16 * q + 4 * g4) = wacc[g][q][t];
-  __syncthreads();
-  for (int e = tid; e < SW * DY_G * 8; e += 512) {  // (j, row quad)
-    const int j = e / (DY_G * 8), r4 = 4 * (e % (DY_G * 8));
-    if (mb + r4 >= M) continue;  // M % 32 == 0: a quad is all in or all out
-    f32x4 sum = *(const f32x4*)(part + j * WROW + r4);
-#pragma unroll
-    for (int w = 1; w < 8; ++w) {
-      const f32x4 v = *(const f32x4*)(part + (w * SW + j) * WROW + r4);
-      sum[0] += v[0]; sum[1] += v[1]; sum[2] += v[2]; sum[3] += v[3];
-    }
-    *(f32x4*)(part_w + ((int64_t)cs * RP + j0 + j) * M + mb + r4) = sum;
-  }
+  const bf16_t* __restrict__ y = y0 + g * gy;
+  const float* __restrict__ u = (MODE & 4) ? nullptr : gp.u[g];
+  const bf16_t* __restrict__ w3 = (MODE & 1) ? gp.w3[g] : nullptr;
+  float* __restrict__ part_w = (MODE & 1) ? part_w0 + g * gpw : nullptr;
+  float* __restrict__ part_b = part_b0 + g * gpb;
+  const float* __restrict__ part_u = (MODE & 4) ? part_u0 + g * gpu : nullptr;
+#define DY_BX gbx
+#define DY_BY blockIdx.y
+#define LTX_DY_BODY 1
+#include "lora_dy_bodies.h"
+#undef LTX_DY_BODY
+#undef DY_BX
+#undef DY_BY
 }
 
 // Blocks [0, nwb): w[m,j] = alpha * sum_c part_w[c][m][j] and the [hi | hi | lo | 0..] split row,
@@ -339,54 +165,39 @@ __global__ __launch_bounds__(256) void lora_dy_finish_kernel(const float* __rest
                                                              const float* __restrict__ part_a, int Na, float alpha_a,
                                                              float* __restrict__ dwa, int64_t ona, int64_t oja,
                                                              int acc_a) {
-  constexpr int RP = R >= 16 ? R : 16;
-  if ((int)blockIdx.x < nwb) {
-    // thread (j quad q, row m), m fastest (the partial reads coalesce): w[m][4q..4q+3],
-    // split[m][4q..] = split[m][R + 4q..] = hi, split[m][2R + 4q..] = lo, and the zero padding
-    // columns 3R + 4q + kR < K2 (the R / 4 quads of a row cover 3R .. K2 between them)
-    constexpr int NQ = R / 4;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)M * NQ) return;
-    const int q = (int)(e / M), m = (int)(e % M);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    int c = 0;
-    for (; c + 4 <= CS; c += 4) {  // 16 loads in flight, summed in split order
-      float t[4][4];
-#pragma unroll
-      for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[cc][k] = part_w[((int64_t)(c + cc) * RP + 4 * q + k) * M + m];
-#pragma unroll
-      for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] += t[cc][k];
-    }
-    for (; c < CS; ++c)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] += part_w[((int64_t)c * RP + 4 * q + k) * M + m];
-    f32x4 wv;
-    uint32_t hi[2], lo[2];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) wv[k] = v[k] * alpha;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const bf16_t h0 = f2bf(wv[2 * k]), h1 = f2bf(wv[2 * k + 1]);
-      hi[k] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-      lo[k] = (uint32_t)f2bf(wv[2 * k] - bf2f(h0)) | ((uint32_t)f2bf(wv[2 * k + 1] - bf2f(h1)) << 16);
-    }
-    *(f32x4*)(w + (int64_t)m * ldw_out + 4 * q) = wv;
-    if (split == nullptr) return;
-    bf16_t* sr = split + (int64_t)m * lds;
-    *(u32x2*)(sr + 4 * q) = (u32x2){hi[0], hi[1]};
-    *(u32x2*)(sr + R + 4 * q) = (u32x2){hi[0], hi[1]};
-    *(u32x2*)(sr + 2 * R + 4 * q) = (u32x2){lo[0], lo[1]};
-    for (int c = 3 * R + 4 * q; c < K2; c += R) *(u32x2*)(sr + c) = (u32x2){0u, 0u};
-    return;
-  }
-  __shared__ float red[4][64];
-  const int blk = (int)blockIdx.x - nwb;
-  if (blk < nbb) finish_rows<R>(part_b, RS, N, alpha, dw, on, oj, accumulate, blk, red);
-  else finish_rows<R>(part_a, RS, Na, alpha_a, dwa, ona, oja, acc_a, blk - nbb, red);
+#define DY_BX blockIdx.x
+#define DY_BY blockIdx.y
+#define LTX_DY_BODY 2
+#include "lora_dy_bodies.h"
+#undef LTX_DY_BODY
+#undef DY_BX
+#undef DY_BY
+}
+
+// the finish of G adapters in one launch: group = blockIdx.y, its partials at g*gpw / g*gpb / g*gpa,
+// its w and split columns at g*gwo / g*gso of the shared [M, .] outputs, its dB / dA from gp
+template <int R>
+__global__ __launch_bounds__(256) void lora_dy_finish_grouped_kernel(
+    const float* __restrict__ part_w0, int CS, const float* __restrict__ part_b0, int RS, int M, int N, float alpha,
+    float* __restrict__ w0, int64_t ldw_out, bf16_t* __restrict__ split0, int64_t lds, int K2, DyGroupPtrs gp,
+    int64_t on, int64_t oj, int accumulate, int nwb, int nbb, const float* __restrict__ part_a0, int Na,
+    float alpha_a, int64_t ona, int64_t oja, int acc_a, int64_t gpw, int64_t gpb, int64_t gpa, int64_t gwo,
+    int64_t gso) {
+  const unsigned g = blockIdx.y;
+  const float* __restrict__ part_w = part_w0 + g * gpw;
+  const float* __restrict__ part_b = part_b0 + g * gpb;
+  const float* __restrict__ part_a = part_a0 + g * gpa;
+  float* __restrict__ w = w0 + g * gwo;
+  bf16_t* __restrict__ split = split0 + g * gso;
+  float* __restrict__ dw = gp.dw[g];
+  float* __restrict__ dwa = gp.dwa[g];
+#define DY_BX blockIdx.x
+#define DY_BY blockIdx.y
+#define LTX_DY_BODY 2
+#include "lora_dy_bodies.h"
+#undef LTX_DY_BODY
+#undef DY_BX
+#undef DY_BY
 }
 
 // u = alpha * x . A^T for token-sized M with the whole contraction inside one block (round 6):
@@ -403,154 +214,41 @@ __global__ __launch_bounds__(512) void lora_rows_full_kernel(const bf16_t* __res
                                                              const bf16_t* __restrict__ w3, int64_t ldw,
                                                              float* __restrict__ out, int64_t ldo, int M, float alpha,
                                                              bf16_t* __restrict__ split, int64_t lds, int K2) {
-  constexpr int RP = R >= 16 ? R : 16;
-  // ranks above 16: 16-wide rank slices, one per blockIdx.y of the same launch (a wave keeps the
-  // pieces of its slice for all CH chunks in registers: 24 CH VGPRs per 16 columns); j0 = slice origin
-  constexpr int SW = 16;
-  constexpr int RW = R < SW ? R : SW;
-  constexpr int JT = SW / 16;
-  constexpr int NF = 3 * JT;
-  constexpr int NS = RG * CH;  // slots per wave
-  constexpr int RING = 8 * NR * 4096;
-  constexpr int PROW = RG * 32 + 4;  // floats per (wave, j) partial row; +4 spreads the banks
-  static_assert(dy_rank_ok(R), "rank 8, 16, 32, 64 or 128");
-  static_assert(8 * SW * PROW * 4 <= RING, "wave partials fit the ring");
-  const int j0 = blockIdx.y * SW;
-  __shared__ __attribute__((aligned(16))) char smem[RING];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c0 = wave * 64 * CH;
-  const int mb = blockIdx.x * RG * 32;
-  const int ng = min(RG, (M - mb) / 32);  // M % 32 == 0
-  const int ns = ng * CH;
+#define DY_BX blockIdx.x
+#define DY_BY blockIdx.y
+#define LTX_DY_BODY 3
+#include "lora_dy_bodies.h"
+#undef LTX_DY_BODY
+#undef DY_BX
+#undef DY_BY
+}
 
-  uint32_t yo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = 8 * i + (lane >> 3);
-    yo[i] = (uint32_t)(row * ldx + (((lane & 7) ^ swz<64>(row)) * 8)) * 2;
-  }
-  const uint32_t lring = lds_u32(smem + wave * (NR * 4096));
-  auto dma = [&](int s) {  // slot s = (group s / CH, chunk s % CH)
-    const char* sb = (const char*)(x + (int64_t)(mb + 32 * (s / CH)) * ldx + c0 + 64 * (s % CH));
-    const uint32_t l = lring + (s % NR) * 4096;
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(yo[0]), "v"(yo[1]), "v"(yo[2]), "v"(yo[3]), "s"(sb), "s"(l)
-        : "memory", "scc");
-  };
-  // the ring's first slots go out first; the pieces' loads overlap them, then everything retires
-  // (hipcc's own waits for the pieces are counted without the asm DMA)
-  for (int s = 0; s < NR - 1; ++s)
-    if (s < ns) dma(s);
-  s16x8 bp[CH][2][NF];
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int t = 0; t < JT; ++t) {
-        const bf16_t* src = w3 + (int64_t)(p * RP + j0 + t * 16 + (lane & 15)) * ldw + c0 + 64 * c + (lane >> 4) * 8;
-        bp[c][0][p * JT + t] = *(const s16x8*)src;
-        bp[c][1][p * JT + t] = *(const s16x8*)(src + 32);
-      }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int f = 0; f < NF; ++f) asm volatile("" : "+v"(bp[c][h][f]));
-
-  int roff[2][2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int row = 16 * q + (lane & 15);
-      roff[q][h] = row * 128 + (((4 * h + (lane >> 4)) ^ swz<64>(row)) * 16);
-    }
-  f32x4 acc[RG][2][JT];
-#pragma unroll
-  for (int g = 0; g < RG; ++g)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < JT; ++t) acc[g][q][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    if (s >= ns) break;
-    const int g = s / CH, c = s % CH;
-    const int younger = min(NR - 2, ns - 1 - s);  // slots issued after s
-    if (younger >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const char* sl = smem + wave * (NR * 4096) + (s % NR) * 4096;
-    s16x8 xf[2][2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) xf[q][h] = *(const s16x8*)(sl + roff[q][h]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slot s read: its ring slot may be refilled
-    if (s + NR - 1 < ns) dma(s + NR - 1);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int t = 0; t < JT; ++t)
-#pragma unroll
-          for (int q = 0; q < 2; ++q)
-            acc[g][q][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[q][h], bp[c][h][p * JT + t], acc[g][q][t], 0, 0, 0);
-  }
-  // the 8 wave partials [j][rows] through LDS (the ring is free once every wave is past its last
-  // slot), then thread (row m, j quad q) sums them in wave order and writes u[m][4q..] and the
-  // [hi | hi | lo | 0..] split row (as lora_dy_finish_kernel)
-  __syncthreads();
-  float* part = (float*)smem;
-#pragma unroll
-  for (int g = 0; g < RG; ++g)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < JT; ++t)
-        *(f32x4*)(part + (wave * SW + 16 * t + (lane & 15)) * PROW + 32 * g + 16 * q + 4 * (lane >> 4)) = acc[g][q][t];
-  __syncthreads();
-  constexpr int NQ = RW / 4;
-  for (int e = tid; e < RG * 32 * NQ; e += 512) {
-    const int q = e / (RG * 32), rr = e % (RG * 32), m = mb + rr;
-    if (m >= M) continue;
-    f32x4 wv;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float v = part[(4 * q + k) * PROW + rr];
-#pragma unroll
-      for (int w = 1; w < 8; ++w) v += part[(w * SW + 4 * q + k) * PROW + rr];
-      wv[k] = v * alpha;
-    }
-    const int jq = j0 + 4 * q;  // the quad's first column in the whole rank
-    *(f32x4*)(out + (int64_t)m * ldo + jq) = wv;
-    if (split == nullptr) continue;
-    uint32_t hi[2], lo[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const bf16_t h0 = f2bf(wv[2 * k]), h1 = f2bf(wv[2 * k + 1]);
-      hi[k] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-      lo[k] = (uint32_t)f2bf(wv[2 * k] - bf2f(h0)) | ((uint32_t)f2bf(wv[2 * k + 1] - bf2f(h1)) << 16);
-    }
-    bf16_t* sr = split + (int64_t)m * lds;
-    *(u32x2*)(sr + jq) = (u32x2){hi[0], hi[1]};
-    *(u32x2*)(sr + R + jq) = (u32x2){hi[0], hi[1]};
-    *(u32x2*)(sr + 2 * R + jq) = (u32x2){lo[0], lo[1]};
-    for (int cc = 3 * R + jq; cc < K2; cc += R) *(u32x2*)(sr + cc) = (u32x2){0u, 0u};
-  }
+// lora_rows_full_kernel for G adapters that share x (the q / k / v adapters on the modulated norm
+// output): blockIdx.y = (group, rank slice), so a row tile is fetched from HBM once and every
+// further slice of every group reads it through L2 / MALL, as the rank slices of one adapter do.
+// Group g takes its pieces from w3[g] and writes out + g*go, split + g*gs; the block program and so
+// each output's summation order are the one-adapter kernel's.
+struct RowsGroupPtrs {
+  const bf16_t* w3[LORA_MAX_GROUPS];
+};
+template <int R, int RG, int CH, int NR>
+__global__ __launch_bounds__(512) void lora_rows_full_grouped_kernel(const bf16_t* __restrict__ x, int64_t ldx,
+                                                                     RowsGroupPtrs gp, int64_t ldw,
+                                                                     float* __restrict__ out0, int64_t ldo, int M,
+                                                                     float alpha, bf16_t* __restrict__ split0,
+                                                                     int64_t lds, int K2, int nsl, int64_t go,
+                                                                     int64_t gs) {
+  const unsigned g = blockIdx.y / (unsigned)nsl, gsl = blockIdx.y % (unsigned)nsl;
+  const bf16_t* __restrict__ w3 = gp.w3[g];
+  float* __restrict__ out = out0 + g * go;
+  bf16_t* __restrict__ split = split0 ? split0 + g * gs : nullptr;
+#define DY_BX blockIdx.x
+#define DY_BY gsl
+#define LTX_DY_BODY 3
+#include "lora_dy_bodies.h"
+#undef LTX_DY_BODY
+#undef DY_BX
+#undef DY_BY
 }
 
 // ltx_lora_wgrad's token-sized path (called from lora.hip): dw (+)= alpha . Y^T . u through the
@@ -774,6 +472,162 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
     default: return fail(LTX_ERR_BAD_ARG, "lora_dy_dA: rank must be 8, 16, 32, 64 or 128");
   }
 #undef LTX_LORA_DYA
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+extern "C" int ltx_lora_dy_dA_grouped_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups,
+                                                int64_t* floats) {
+  LTX_CHECK_ARG(groups >= 1 && groups <= LORA_MAX_GROUPS, "lora_dy_dA_grouped_workspace: 1 to 4 groups");
+  int64_t one = 0;
+  const int rc = ltx_lora_dy_dA_workspace(M, N, K, r, &one);
+  if (rc != LTX_OK) return rc;
+  *floats = groups * one;
+  return LTX_OK;
+}
+
+// ltx_lora_dy_dA for `groups` adapters on the column blocks of one packed dY [M, groups * N] that
+// share x: the dY pass with the groups in grid z, one x pass whose blocks cover every group's rank
+// slices per 512-column tile, one finish with the groups in grid y. Three launches; every output
+// bitwise the one-adapter call on the column slice (the same block program on the same operands).
+extern "C" int ltx_lora_dy_dA_grouped(const void* y, int64_t ldy, const float* const* u, int64_t ldu,
+                                      const void* const* w3, int64_t ldw3, const void* x, int64_t ldx, int64_t M,
+                                      int64_t N, int64_t K, int64_t r, int64_t groups, float alpha, float* w,
+                                      int64_t ldw_out, int64_t gw, void* split, int64_t ld_split, int64_t K2,
+                                      int64_t gs, float* const* dw, int64_t on, int64_t oj, int accumulate,
+                                      float alpha_a, float* const* dwa, int64_t ona, int64_t oja, int acc_a,
+                                      float* workspace, void* stream) {
+  LTX_CHECK_ARG(y && u && w3 && x && w && split && dw && dwa && workspace, "lora_dy_dA_grouped: null operand");
+  LTX_CHECK_ARG(groups >= 1 && groups <= LORA_MAX_GROUPS, "lora_dy_dA_grouped: 1 to 4 groups");
+  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && K % DY_COLS == 0 && dy_rank_ok(r),
+                "lora_dy_dA_grouped: M % 32 == 0, N % 512 == 0, K % 512 == 0, rank 8, 16, 32, 64 or 128");
+  LTX_CHECK_ARG(N <= DY_MAXCS * DY_COLS, "lora_dy_dA_grouped: N <= 2048 per group");
+  LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldy >= groups * N && ldw3 % 8 == 0 && ldw3 >= N,
+                "lora_dy_dA_grouped: 16-B aligned rows of dY (groups * N columns) and of the pieces");
+  LTX_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldx >= K, "lora_dy_dA_grouped: 16-B aligned rows of x");
+  LTX_CHECK_ARG(ldy * 2 * 32 < ((int64_t)1 << 32) && ldx * 2 * 32 < ((int64_t)1 << 32),
+                "lora_dy_dA_grouped: 32-bit DMA offsets");
+  LTX_CHECK_ARG(gw >= r && gs >= K2 && ldw_out >= (groups - 1) * gw + r && ldu >= r && K2 >= 3 * r && K2 % 64 == 0 &&
+                    ld_split >= (groups - 1) * gs + K2,
+                "lora_dy_dA_grouped: every group's w / split columns inside the row, disjoint");
+  LTX_CHECK_ARG(ldw_out % 4 == 0 && gw % 4 == 0 && ((uintptr_t)w % 16) == 0 && ld_split % 4 == 0 && gs % 4 == 0 &&
+                    ((uintptr_t)split % 8) == 0,
+                "lora_dy_dA_grouped: 16-B aligned w rows, 8-B aligned split rows");
+  LTX_CHECK_ARG((on == r && oj == 1) || (on == 1 && oj == N), "lora_dy_dA_grouped: dB must be a dense [N,r] or [r,N]");
+  LTX_CHECK_ARG((ona == r && oja == 1) || (ona == 1 && oja == K),
+                "lora_dy_dA_grouped: dA must be a dense [K,r] or [r,K]");
+  DyGroupPtrs gp{};
+  for (int g = 0; g < (int)groups; ++g) {
+    LTX_CHECK_ARG(u[g] && w3[g] && dw[g] && dwa[g] && ((uintptr_t)w3[g] % 16) == 0,
+                  "lora_dy_dA_grouped: null or misaligned group operand");
+    gp.u[g] = u[g];
+    gp.w3[g] = (const bf16_t*)w3[g];
+    gp.dw[g] = dw[g];
+    gp.dwa[g] = dwa[g];
+  }
+  const int64_t RP = r >= 16 ? r : 16;
+  const int DY_G = dy_g((int)r), NSL = dy_nsl((int)r), G = (int)groups;
+  const int CS = (int)(N / DY_COLS), CSx = (int)(K / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
+  const int64_t gpw = (int64_t)CS * M * RP, gpb = (int64_t)RS * N * RP, gpa = (int64_t)RS * K * RP;
+  float* pw = workspace;
+  float* pb = pw + G * gpw;
+  float* pa = pb + G * gpb;
+  hipStream_t s = (hipStream_t)stream;
+  const int nwb = (int)((M * (r / 4) + 255) / 256);
+  const int nbb = (int)((N * r + 63) / 64), nba = (int)((K * r + 63) / 64);
+#define LTX_LORA_DYG(RR)                                                                                            \
+  hipLaunchKernelGGL((lora_dy_grouped_kernel<RR, 3>), dim3((unsigned)(CS * NSL), (unsigned)RS, (unsigned)G),        \
+                     dim3(512), 0, s, (const bf16_t*)y, ldy, gp, ldu, ldw3, pw, pb, (int)M, (int)N,                 \
+                     (const float*)nullptr, 0, 1.f, G, N, gpw, gpb, (int64_t)0);                                    \
+  LTX_LAUNCH_CHECK();                                                                                               \
+  hipLaunchKernelGGL((lora_dy_grouped_kernel<RR, 6>), dim3((unsigned)(CSx * NSL * G), (unsigned)RS), dim3(512), 0, \
+                     s, (const bf16_t*)x, ldx, gp, (int64_t)0, (int64_t)0, (float*)nullptr, pa, (int)M, (int)K,     \
+                     (const float*)pw, CS, alpha, G, (int64_t)0, (int64_t)0, gpa, gpw);                             \
+  LTX_LAUNCH_CHECK();                                                                                               \
+  hipLaunchKernelGGL((lora_dy_finish_grouped_kernel<RR>), dim3((unsigned)(nwb + nbb + nba), (unsigned)G),           \
+                     dim3(256), 0, s, pw, CS, pb, RS, (int)M, (int)N, alpha, w, ldw_out, (bf16_t*)split, ld_split,  \
+                     (int)K2, gp, on, oj, accumulate, nwb, nbb, (const float*)pa, (int)K, alpha_a, ona, oja, acc_a, \
+                     gpw, gpb, gpa, gw, gs);
+  switch (r) {
+    case 8: LTX_LORA_DYG(8) break;
+    case 16: LTX_LORA_DYG(16) break;
+    case 32: LTX_LORA_DYG(32) break;
+    case 64: LTX_LORA_DYG(64) break;
+    case 128: LTX_LORA_DYG(128) break;
+    default: return fail(LTX_ERR_BAD_ARG, "lora_dy_dA_grouped: rank must be 8, 16, 32, 64 or 128");
+  }
+#undef LTX_LORA_DYG
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+// ltx_lora_rows for `groups` adapters that share x. Where ltx_lora_rows runs its whole-contraction
+// kernel (token-sized M, K = 512 / 1024 / 2048) this is ONE launch with (group, rank slice) as grid y;
+// everywhere else it issues the one-adapter calls. Either way every output is bitwise
+// ltx_lora_rows' on the same operands.
+extern "C" int ltx_lora_rows_grouped(const void* x, int64_t ldx, const void* const* w3, int64_t ldw, float* out,
+                                     int64_t ldo, int64_t go, int64_t M, int64_t K, int64_t r, float alpha,
+                                     void* split, int64_t ld_split, int64_t K2, int64_t gs, int64_t groups,
+                                     void* stream) {
+  LTX_CHECK_ARG(x && w3 && out && M > 0 && K > 0, "lora_rows_grouped: bad args");
+  LTX_CHECK_ARG(groups >= 1 && groups <= LORA_MAX_GROUPS, "lora_rows_grouped: 1 to 4 groups");
+  LTX_CHECK_ARG(go >= r && ldo >= (groups - 1) * go + r, "lora_rows_grouped: every group's out columns inside the row");
+  LTX_CHECK_ARG(!split || (K2 >= 3 * r && K2 % 64 == 0 && gs >= K2 && ld_split >= (groups - 1) * gs + K2),
+                "lora_rows_grouped: split needs K2 >= 3r, %64, every group's columns inside the row");
+  LTX_CHECK_ARG(K % 256 == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldw % 8 == 0 && ldw >= K,
+                "lora_rows_grouped: K % 256, 16-B aligned rows of x and of the pieces");
+  LTX_CHECK_ARG((int64_t)ldx * 2 * (M - 1) + 2 * K < ((int64_t)1 << 32) &&
+                    (int64_t)ldw * 2 * 3 * (r > 32 ? r : 32) < ((int64_t)1 << 32),
+                "lora_rows_grouped: 32-bit DMA offsets");
+  for (int g = 0; g < (int)groups; ++g)
+    LTX_CHECK_ARG(w3[g] && ((uintptr_t)w3[g] % 16) == 0, "lora_rows_grouped: null or misaligned pieces");
+  hipStream_t s = (hipStream_t)stream;
+  const bf16_t* xb = (const bf16_t*)x;
+  bf16_t* sp = (bf16_t*)split;
+  static const int rows_dy = [] {
+    const char* e = getenv("LTX_LORA_ROWS_DY");
+    return e ? atoi(e) : 1;
+  }();
+  static const int full = [] {
+    const char* e = getenv("LTX_LORA_ROWS_FULL");
+    return e ? atoi(e) : 1;
+  }();
+  // the gates of lora_rows_dy's whole-contraction route, for every group's operands
+  bool one = rows_dy && full && M >= 2048 && M % 32 == 0 && (K == 512 || K == 1024 || K == 2048) && dy_rank_ok(r);
+  one = one && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldx * 2 * 32 < ((int64_t)1 << 32) && ldx >= K;
+  one = one && ldw % 8 == 0 && ldw >= K && ldo % 4 == 0 && go % 4 == 0 && ((uintptr_t)out % 16) == 0;
+  one = one && (!split || (ld_split % 4 == 0 && gs % 4 == 0 && ((uintptr_t)split % 8) == 0 && (K2 - 3 * r) % 4 == 0));
+  RowsGroupPtrs gp{};
+  for (int g = 0; g < (int)groups; ++g) {
+    gp.w3[g] = (const bf16_t*)w3[g];
+    one = one && ((uintptr_t)w3[g] % 16) == 0;
+  }
+  if (!one) {
+    for (int g = 0; g < (int)groups; ++g) {
+      const int rc = ltx_lora_rows(x, ldx, w3[g], ldw, out + g * go, ldo, M, K, r, alpha, sp ? sp + g * gs : nullptr,
+                                   ld_split, K2, stream);
+      if (rc != LTX_OK) return rc;
+    }
+    return LTX_OK;
+  }
+  constexpr int RG = 2, NRF = LTX_RF_NR;
+  const int nsl = (int)(r > 16 ? r / 16 : 1);
+  const dim3 gf((unsigned)((M + RG * 32 - 1) / (RG * 32)), (unsigned)(nsl * groups));
+#define LTX_LORA_RFG(RR, CHH)                                                                                     \
+  hipLaunchKernelGGL((lora_rows_full_grouped_kernel<RR, RG, CHH, NRF>), gf, dim3(512), 0, s, xb, ldx, gp, ldw, out, \
+                     ldo, (int)M, alpha, sp, ld_split, (int)K2, nsl, go, gs)
+  const int ch = (int)(K / 512);
+#define LTX_LORA_RFGC(RR) \
+  if (ch == 1) LTX_LORA_RFG(RR, 1); else if (ch == 2) LTX_LORA_RFG(RR, 2); else LTX_LORA_RFG(RR, 4)
+  switch (r) {
+    case 8: LTX_LORA_RFGC(8); break;
+    case 16: LTX_LORA_RFGC(16); break;
+    case 32: LTX_LORA_RFGC(32); break;
+    case 64: LTX_LORA_RFGC(64); break;
+    default: LTX_LORA_RFGC(128); break;
+  }
+#undef LTX_LORA_RFGC
+#undef LTX_LORA_RFG
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

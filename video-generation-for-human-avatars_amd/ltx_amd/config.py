@@ -72,7 +72,7 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     sampler = cfg.get("sampler", None)
     rf_sampler = _SAMPLERS.get(sampler.lower(), "Uniform") if isinstance(sampler, str) else "Uniform"
     t = cfg.get("train", {}) or {}
-    return TrainConfig(
+    config = TrainConfig(
         checkpoint_path=checkpoint_path,
         precision=cfg.get("precision", "bfloat16"),
         condition_latents_dir=t.get("condition_latents_dir"),
@@ -111,3 +111,10 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
         decoder_loss_lpips_weight=float(t.get("decoder_loss_lpips_weight", 0.0)),
         decoder_t_max=float(t.get("decoder_t_max", 0.1)),
     )
+    # this build's extension, not a TrainConfig field (the dataclass stays the reference's): the
+    # attentions that carry LoRA adapters, read by lora.apply_training_strategy with getattr, set
+    # only when the YAML names it ("attn2", "attn1", "attn1+attn2" or a list of those names)
+    if "lora_targets" in t:
+        v = t["lora_targets"]
+        setattr(config, "lora_targets", v if isinstance(v, str) else tuple(v))
+    return config

@@ -3,6 +3,8 @@
 'lora_audio': wraps transformer_blocks.{i}.attn2.{to_q,to_k,to_v,to_out.0} in LoraLinear (peft
 0.17.1 parameter names and init: kaiming-uniform(a=sqrt(5)) A, zero B, f32 adapters on the bf16
 base, scaling = alpha / r) and makes only `lora_*` and `caption_projection` trainable.
+`config.lora_targets` ("attn2" by default; "attn1", "attn1+attn2" or a tuple of those names) also
+or instead wraps the same four projections of the self-attention attn1.
 'full': the reference's substring rule (training.py:75-91); the fused block backward raises for
 it until the wgrad path (next row) lands.
 """
@@ -12,16 +14,58 @@ from . import ops
 from .transformer3d import LoraLinear
 
 
-def lora_target_modules(num_blocks):
+LORA_ATTENTIONS = ("attn1", "attn2")  # the attentions whose four projections can carry adapters
+_PROJECTIONS = ("to_q", "to_k", "to_v", "to_out.0")  # the reference's order (training.py:52-60)
+
+
+def _attentions(attention):
+    """`attention` (a tuple / list of names, or "attn2" / "attn1" / "attn1+attn2") as a tuple in
+    block order (attn1 before attn2); ValueError for anything outside LORA_ATTENTIONS."""
+    names = tuple(a.strip() for a in attention.split("+")) if isinstance(attention, str) else tuple(attention)
+    bad = [a for a in names if a not in LORA_ATTENTIONS]
+    if bad or not names or len(set(names)) != len(names):
+        raise ValueError(f"LoRA targets {attention!r}: expected a non-empty subset of {LORA_ATTENTIONS} "
+                         f"(or 'attn2', 'attn1', 'attn1+attn2')")
+    return tuple(a for a in LORA_ATTENTIONS if a in names)
+
+
+def lora_target_modules(num_blocks, attention=("attn2",)):
     out = []
     for i in range(num_blocks):
-        out += [f"transformer_blocks.{i}.attn2.to_q", f"transformer_blocks.{i}.attn2.to_k",
-                f"transformer_blocks.{i}.attn2.to_v", f"transformer_blocks.{i}.attn2.to_out.0"]
+        for a in _attentions(attention):
+            out += [f"transformer_blocks.{i}.{a}.{p}" for p in _PROJECTIONS]
     return out
+
+
+def _check_targets(model, targets):
+    """Before any module is replaced: every name is `transformer_blocks.<i>.<attn1|attn2>.<to_q|to_k|
+    to_v|to_out.0>` of this model (ValueError naming the accepted set), and together with the
+    adapters already present each attention ends up with none or all four of its projections
+    wrapped (NotImplementedError: the fused block has no path for a partly adapted attention)."""
+    n = len(model.transformer_blocks)
+    want = set()
+    for name in targets:
+        parts = name.split(".", 3)
+        ok = (len(parts) == 4 and parts[0] == "transformer_blocks" and parts[1].isdigit() and int(parts[1]) < n
+              and parts[2] in LORA_ATTENTIONS and parts[3] in _PROJECTIONS)
+        if not ok:
+            raise ValueError(f"LoRA target {name!r}: accepted are transformer_blocks.<0..{n - 1}>."
+                             f"<{'|'.join(LORA_ATTENTIONS)}>.<{'|'.join(_PROJECTIONS)}>")
+        want.add((int(parts[1]), parts[2], parts[3]))
+    for i, blk in enumerate(model.transformer_blocks):
+        for a in LORA_ATTENTIONS:
+            att = getattr(blk, a)
+            have = [isinstance(att.to_out[0] if p == "to_out.0" else getattr(att, p), LoraLinear) or (i, a, p) in want
+                    for p in _PROJECTIONS]
+            if any(have) and not all(have):
+                raise NotImplementedError(f"LoRA must wrap all four projections of transformer_blocks.{i}.{a} "
+                                          f"({', '.join(_PROJECTIONS)}) or none (training.py:52-60)")
 
 
 def inject_lora(model, targets, r, alpha):
     ops.check_lora_rank(r)  # before the first module is replaced
+    targets = list(targets)
+    _check_targets(model, targets)
     for name in targets:
         parent_name, _, child = name.rpartition(".")
         parent = model.get_submodule(parent_name)
@@ -38,7 +82,10 @@ def inject_lora(model, targets, r, alpha):
 
 def apply_training_strategy(model, config, train_mode: str):
     if train_mode == "lora_audio":
-        inject_lora(model, lora_target_modules(len(model.transformer_blocks)), config.lora_rank,
+        # the attentions that carry adapters: config.lora_targets, set with setattr as the reference
+        # sets train_mode (not a TrainConfig field); default = the reference's attn2 (training.py:50-60)
+        attention = getattr(config, "lora_targets", ("attn2",))
+        inject_lora(model, lora_target_modules(len(model.transformer_blocks), attention), config.lora_rank,
                     config.lora_alpha)
         for n, p in model.named_parameters():
             p.requires_grad = ("lora_" in n) or ("caption_projection" in n)
@@ -87,4 +134,8 @@ def unload_lora(model):
                 parent[int(child)] = mod.base_layer
             else:
                 setattr(parent, child, mod.base_layer)
+    # the merge wrote through .data (no version bump): drop every block's packed-weight cache (fused
+    # QKV, W^T copies) so the next forward packs the merged weights
+    for blk in getattr(model, "transformer_blocks", ()):
+        blk._pack = blk._pack_key = None
     return model

@@ -784,21 +784,91 @@ def lora_dy_fits(y, r):
     return r in LORA_RANKS and M % 32 == 0 and N % 512 == 0 and y.stride(1) == 1 and y.stride(0) % 8 == 0
 
 
+def _ptr_array(tensors):
+    """host array of device pointers (the per-group operands of the grouped adapter entries)"""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def lora_rows_grouped(x, w3s, r, alpha=1.0, out=None, split=False, split_out=None, group_strides=None):
+    """lora_rows for len(w3s) adapters of rank r that share x (ltx_lora_rows_grouped: one launch where
+    lora_rows runs its whole-contraction kernel, each row tile of x read from HBM once). Group g
+    writes the [M, r] columns starting g * go of out's row and the [M, K2] columns starting g * gs of
+    split_out's row, group_strides = (go, gs), default (r, K2): out / split_out are the FIRST group's
+    column views of the caller's wider buffers (default: new [M, G r] / [M, G K2] buffers). Returns
+    (out buffer, split buffer) as allocated here, or the views passed in. Bitwise G lora_rows calls."""
+    M, K = x.shape
+    G = len(w3s)
+    K2 = lora_k2(r)
+    go, gs = group_strides if group_strides is not None else (r, K2)
+    ret_out = out
+    if out is None:
+        ret_out = torch.empty(M, (G - 1) * go + r, dtype=F32, device=x.device)
+        out = ret_out[:, :r]
+    assert out.dtype == F32 and out.stride(1) == 1 and out.stride(0) >= (G - 1) * go + r
+    sp, lds, ret_sp = None, 0, None
+    if split:
+        ret_sp = split_out
+        if split_out is None:
+            ret_sp = torch.empty(M, (G - 1) * gs + K2, dtype=BF16, device=x.device)
+            split_out = ret_sp[:, :K2]
+        sp, lds = split_out, _rows(split_out, "split_out")
+        assert sp.dtype == BF16 and lds >= (G - 1) * gs + K2
+    for t in w3s:
+        assert t.dtype == BF16 and t.stride(1) == 1 and t.stride(0) == w3s[0].stride(0) and t.shape[1] == K
+    _gemm_workspace(x.device)
+    call("ltx_lora_rows_grouped", _p(x), _rows(x, "x"), _ptr_array(w3s), w3s[0].stride(0), _p(out),
+         out.stride(0), go, M, K, r, float(alpha), _p(sp), lds, K2 if split else 0, gs if split else 0, G, _s())
+    return (ret_out, ret_sp) if split else ret_out
+
+
+def lora_dy_grouped(y, us, w3s, r, alpha, dB_outs, x, dA_outs, accumulate=True, dA_accumulate=True,
+                    w_out=None, split_out=None):
+    """lora_dy(..., x=, dA_out=) for G = len(us) adapters of rank r on the column blocks of one packed
+    dY [M, G N] that share x (ltx_lora_dy_dA_grouped: three launches, x read once): group g takes
+    y[:, g N:(g+1) N], us[g], w3s[g] (pieces of B_g^T) and adds into dB_outs[g] ([N, r]) and
+    dA_outs[g] ([r, K]). Returns (w [M, G r] f32, split [M, G K2] bf16), group g in its column block.
+    Every output is bitwise the per-group lora_dy call's."""
+    M, GN = y.shape
+    G = len(us)
+    N, K = GN // G, x.shape[1]
+    K2 = lora_k2(r)
+    assert GN == G * N and x.shape[0] == M and x.dtype == BF16 and y.dtype == BF16
+    assert lora_dy_fits(y[:, :N], r) and lora_dy_fits(x, r) and N <= 2048
+    for u, w3, dB, dA in zip(us, w3s, dB_outs, dA_outs):
+        assert u.dtype == F32 and u.shape == (M, r) and u.stride(1) == 1 and u.stride(0) == us[0].stride(0)
+        assert w3.dtype == BF16 and w3.stride(1) == 1 and w3.stride(0) == w3s[0].stride(0) and w3.shape[1] == N
+        assert tuple(dB.shape) == (N, r) and dB.dtype == F32 and dB.is_contiguous()
+        assert tuple(dA.shape) == (r, K) and dA.dtype == F32 and dA.is_contiguous()
+    w = torch.empty(M, G * r, dtype=F32, device=y.device) if w_out is None else w_out
+    sp = torch.empty(M, G * K2, dtype=BF16, device=y.device) if split_out is None else split_out
+    assert w.shape == (M, G * r) and sp.shape == (M, G * K2)
+    n = ctypes.c_int64(0)
+    call("ltx_lora_dy_dA_grouped_workspace", M, N, K, r, G, ctypes.byref(n))
+    ws = torch.empty(n.value, dtype=F32, device=y.device)
+    call("ltx_lora_dy_dA_grouped", _p(y), _rows(y, "y"), _ptr_array(us), us[0].stride(0), _ptr_array(w3s),
+         w3s[0].stride(0), _p(x), _rows(x, "x"), M, N, K, r, G, float(alpha), _p(w), _rows(w, "w"), r, _p(sp),
+         _rows(sp, "split"), K2, K2, _ptr_array(dB_outs), r, 1, 1 if accumulate else 0, 1.0,
+         _ptr_array(dA_outs), 1, K, 1 if dA_accumulate else 0, _p(ws), _s())
+    return w, sp
+
+
 def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=None, dA_out=None,
-            dA_accumulate=True):
+            dA_accumulate=True, w_out=None, split_out=None):
     """One pass over dY (ltx_lora_dy): returns (w, split) as lora_down(y, B, transposed=True,
     split=True) does, and adds alpha * y^T . u into dB_out ([N, r], or [r, N] with transpose_out)
     as lora_wgrad(y, u, alpha, out=dB_out, accumulate=accumulate) does. With x ([M, K] bf16,
     lora_dy_fits; N <= 2048) and dA_out ([r, K] f32): also dA_out (+)= x^T . w as lora_wgrad(x, w,
     transpose_out=True, out=dA_out, accumulate=dA_accumulate) does, bitwise, with one launch fewer
-    than the two calls (ltx_lora_dy_dA)."""
+    than the two calls (ltx_lora_dy_dA). w_out / split_out: [M, r] f32 / [M, K2] bf16 column views of
+    the caller's wider buffers to write w and its split into."""
     M, N = y.shape
     shape = (r, N) if transpose_out else (N, r)
     assert tuple(dB_out.shape) == shape and dB_out.dtype == F32 and dB_out.is_contiguous()
     on, oj = (1, N) if transpose_out else (r, 1)
     K2 = lora_k2(r)
-    w = torch.empty(M, r, dtype=F32, device=y.device)
-    sp = torch.empty(M, K2, dtype=BF16, device=y.device)
+    w = torch.empty(M, r, dtype=F32, device=y.device) if w_out is None else w_out
+    sp = torch.empty(M, K2, dtype=BF16, device=y.device) if split_out is None else split_out
+    assert w.shape == (M, r) and w.dtype == F32 and sp.shape == (M, K2) and sp.dtype == BF16
     n = ctypes.c_int64(0)
     if x is not None:
         K = x.shape[1]

@@ -328,6 +328,96 @@ def _kv_ext(blk, lk, lv):
     return fwd, bwd
 
 
+def _qkv_ext(blk, lq, lk, lv):
+    """K-extension weights of the packed self-attention QKV GEMMs with attn1 adapters, cached per
+    block and rebuilt with the adapters (keyed like LoraLinear.weight_split). Forward: [3D, K2] =
+    [split(s B_q); split(s B_k); split(s B_v)] for the grouped extension (ext_group = (D, K2): the
+    output columns of q / k / v read their own K2 columns of the [M, 3 K2] activation operand); where
+    D is no multiple of the grouped form's 256 columns, the block-diagonal [3D, 3 K2] of a plain
+    extension. Backward: [D, 3 K2] = split(A_q^T) | split(A_k^T) | split(A_v^T) (the three adapters
+    add into dx1). Returns (forward, grouped?, backward)."""
+    fs = [m.weight_split("B") for m in (lq, lk, lv)]
+    bs = [m.weight_split("A") for m in (lq, lk, lv)]
+    key = tuple(id(t) for t in fs + bs)  # the splits are replaced when an adapter changes
+    hit = getattr(blk, "_qkv_ext", None)
+    if hit is not None and hit[0] == key:
+        return hit[1], hit[2], hit[3]
+    D, K2 = fs[0].shape
+    grouped = D % 256 == 0
+    if grouped:
+        fwd = torch.cat(fs, 0).contiguous()
+    else:
+        fwd = torch.zeros(3 * D, 3 * K2, dtype=fs[0].dtype, device=fs[0].device)
+        for g, f in enumerate(fs):
+            fwd[g * D:(g + 1) * D, g * K2:(g + 1) * K2] = f
+    bwd = torch.cat(bs, 1).contiguous()
+    blk._qkv_ext = (key, fwd, grouped, bwd, (fs, bs))  # hold the splits: ids stay unique
+    return fwd, grouped, bwd
+
+
+# the q / k / v adapters of a LoRA-wrapped attn1 share their input (the modulated norm output x1) and
+# their dY is the packed dQKV: LTX_LORA_QKV_GROUPED=1 runs them through the grouped kernels
+# (ltx_lora_rows_grouped, ltx_lora_dy_dA_grouped: one read of x1 each way), 0 through the one-adapter
+# calls. Both give bitwise the same result; profiles/lora_attn1_bench.md has the timings behind the
+# default.
+def _qkv_grouped():
+    return os.environ.get("LTX_LORA_QKV_GROUPED", "1") != "0"
+
+
+def _qkv_lora_down(x1, lora1, ab1, r):
+    """u_g = x1 . A_g^T of the q / k / v adapters side by side: (u [M, 3r] f32, split [M, 3 K2] bf16)."""
+    M, K = x1.shape
+    K2 = ops.lora_k2(r)
+    if _qkv_grouped() and ops._LORA_ROWS and M >= 8192 and K % 256 == 0:  # lora_down's token-sized gate
+        return ops.lora_rows_grouped(x1, [m.weight_pieces("A") for m in lora1[:3]], r, split=True)
+    u = torch.empty(M, 3 * r, dtype=torch.float32, device=x1.device)
+    su = torch.empty(M, 3 * K2, dtype=torch.bfloat16, device=x1.device)
+    for g in range(3):
+        ops.lora_down(x1, ab1[2 * g], split=True, out=u[:, g * r:(g + 1) * r],
+                      split_out=su[:, g * K2:(g + 1) * K2], pieces=lambda m=lora1[g]: m.weight_pieces("A"))
+    return u, su
+
+
+def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None):
+    """One adapter's backward: dB and dA into .grad, returns (w = s dY B, its split operand). The
+    one-pass forms where they apply (ops.lora_dy), else lora_wgrad + lora_down."""
+    dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dy, r)
+    if dy_ok and ops.lora_dy_da_fits(dy, x, r):
+        # one pass over dY, one over x (dA), one finish for w / split, dB and dA
+        return ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), x=x,
+                           dA_out=_grad_buf(lin, "A"), w_out=w_out, split_out=split_out)
+    if dy_ok:  # one pass over dY
+        w, sw = ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), w_out=w_out,
+                            split_out=split_out)
+    else:
+        ops.lora_wgrad(dy, u, alpha=s, out=_grad_buf(lin, "B"), accumulate=True)
+        w, sw = ops.lora_down(dy, Bw, alpha=s, transposed=True, split=True, out=w_out, split_out=split_out,
+                              pieces=lambda: lin.weight_pieces("Bt"))
+    ops.lora_wgrad(x, w, transpose_out=True, out=_grad_buf(lin, "A"), accumulate=True)
+    return w, sw
+
+
+def _qkv_lora_backward(dqkv, u, lora1, ab1, x1, r, s):
+    """dB / dA of the q / k / v adapters into .grad from the packed dQKV [M, 3D]; returns the
+    [M, 3 K2] split operand of w_g = s dY_g B_g, the K extension of dx1 = dQKV . Wqkv^T."""
+    M, D3 = dqkv.shape
+    D = D3 // 3
+    K2 = ops.lora_k2(r)
+    us = [u[:, g * r:(g + 1) * r] for g in range(3)]
+    if (_qkv_grouped() and ops.lora_dy_enabled() and ops.lora_dy_fits(dqkv[:, :D], r)
+            and ops.lora_dy_da_fits(dqkv[:, :D], x1, r)):
+        _, sw = ops.lora_dy_grouped(dqkv, us, [m.weight_pieces("Bt") for m in lora1[:3]], r, s,
+                                    [_grad_buf(m, "B") for m in lora1[:3]], x1,
+                                    [_grad_buf(m, "A") for m in lora1[:3]])
+        return sw
+    w = torch.empty(M, 3 * r, dtype=torch.float32, device=dqkv.device)
+    sw = torch.empty(M, 3 * K2, dtype=torch.bfloat16, device=dqkv.device)
+    for g in range(3):
+        _lora_backward(dqkv[:, g * D:(g + 1) * D], us[g], lora1[g], ab1[2 * g + 1], x1, r, s,
+                       w_out=w[:, g * r:(g + 1) * r], split_out=sw[:, g * K2:(g + 1) * K2])
+    return sw
+
+
 class TimestepEmbedding(nn.Module):
     def __init__(self, in_channels, time_embed_dim):
         super().__init__()
@@ -406,15 +496,24 @@ def _base(m):
     return m._modules["base_layer"] if type(m) is LoraLinear else m
 
 
-def _lora_params(blk):
-    """attn2 LoRA (A, B) per target in _LORA_KEYS order, or None (no adapters)."""
-    a2 = blk._modules["attn2"]._modules
+def _lora_params(blk, attn="attn2"):
+    """The LoraLinear of an attention's four projections in _LORA_KEYS order, or None (no adapters)."""
+    a2 = blk._modules[attn]._modules
     lins = (a2["to_q"], a2["to_k"], a2["to_v"], a2["to_out"]._modules["0"])
     kinds = [type(m) is LoraLinear for m in lins]
     if not all(kinds):
         if any(kinds):
-            raise NotImplementedError("LoRA must wrap all four attn2 projections (training.py:52-60)")
+            raise NotImplementedError(f"LoRA must wrap all four {attn} projections (training.py:52-60)")
         return None
+    return lins
+
+
+def _lora_params1(blk):
+    """The self-attention's adapters (lora_targets 'attn1'): q / k / v and to_out.0 must share one
+    rank and scaling (their u and w rows sit side by side in the packed QKV GEMM's K extension)."""
+    lins = _lora_params(blk, "attn1")
+    if lins is not None and any(m.r != lins[0].r or m.scaling != lins[0].scaling for m in lins[1:]):
+        raise NotImplementedError("the attn1 adapters of one block must share rank and scaling")
     return lins
 
 
@@ -448,18 +547,35 @@ class _BlockFn(torch.autograd.Function):
         W = blk.packed()
         a1, a2, ff = blk.attn1, blk.attn2, blk.ff
         ldm = mods.stride(0)
-        has_lora = len(lora_ab) > 0
-        lora = _lora_params(blk) if has_lora else None
+        # lora_ab = the attn2 adapters' 8 tensors (_lora_ab), then the attn1 adapters' 8 (_lora_ab1)
+        lora = _lora_params(blk) if len(lora_ab) > 0 else None
+        has_lora = lora is not None
+        lora1 = _lora_params1(blk) if len(lora_ab) > (8 if has_lora else 0) else None
+        has1 = lora1 is not None
+        ab1 = lora_ab[8:] if has_lora else lora_ab
+        lora_ab = lora_ab[:8] if has_lora else ()
         r = lora[0].r if has_lora else 0
         s = lora[0].scaling if has_lora else 1.0
+        full = sh.full and keep
+        if (has_lora or has1) and full:  # before the block's first launch
+            raise NotImplementedError("train_mode='full' trains the base weights without LoRA")
         # ---- 1. norm1 + AdaLN(msa) -> fused QKV -> q/k RMSNorm + RoPE -> SDPA -> gated residual
         x1, rstd1 = ops.rmsnorm_modulate_fwd(h, mods[:, 0], onep[:, 1], ldm, rpm, blk.norm_eps)
-        qkv = ops.gemm(x1, W["qkv_w"], bias=W["qkv_b"])
+        if has1:
+            # the q / k / v adapters ride the packed QKV GEMM: their u rows side by side as one
+            # [M, 3 K2] operand, column group g of the output reading its own K2 columns
+            r1 = lora1[0].r
+            u1, su1 = _qkv_lora_down(x1, lora1, ab1, r1)
+            ext_w, grouped, _ = _qkv_ext(blk, lora1[0], lora1[1], lora1[2])
+            qkv = ops.gemm(x1, W["qkv_w"], bias=W["qkv_b"], ext=(su1, ext_w),
+                           ext_group=(D, ops.lora_k2(r1)) if grouped else None)
+            del su1
+        else:
+            qkv = ops.gemm(x1, W["qkv_w"], bias=W["qkv_b"])
         strat = skip[1] if skip is not None else None
-        full = sh.full and keep
-        if has_lora and full:
-            raise NotImplementedError("train_mode='full' trains the base weights without LoRA")
-        if strat is not SkipLayerStrategy.AttentionSkip and not full:
+        # x1 is kept for the backward of the attn1 adapters (dA_g = w_g^T . x1), as full mode keeps it
+        keep_x1 = full or (has1 and keep)
+        if strat is not SkipLayerStrategy.AttentionSkip and not keep_x1:
             del x1
         qk = torch.empty(M, 2 * D, dtype=torch.bfloat16, device=h.device)
         _, _, rq1, rk1 = ops.qk_norm_rope_fwd(qkv[:, :D], qkv[:, D:2 * D], a1.q_norm.weight,
@@ -468,13 +584,21 @@ class _BlockFn(torch.autograd.Function):
         o1, lse1 = ops.attn_fwd(qk[:, :D], qk[:, D:], qkv[:, 2 * D:], B, H, d, a1.scale)
         if strat is SkipLayerStrategy.AttentionSkip:  # blend with the processor input
             o1 = ops.skip_blend(o1, x1, skip[0], N)
-            if not full:
+            if not keep_x1:
                 del x1
         elif strat is SkipLayerStrategy.AttentionValues:  # blend with to_v's output
             o1 = ops.skip_blend(o1, qkv[:, 2 * D:], skip[0], N)
         y1 = torch.empty(M, D, dtype=torch.bfloat16, device=h.device) if full else None
-        h1 = ops.gemm(o1, a1.to_out[0].weight, bias=a1.to_out[0].bias, epilogue="gated_residual",
-                      aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm)
+        if has1:  # to_out.0's adapter sees the (blended) o1, as the reference's to_out does
+            lo1 = lora1[3]
+            u_o1, su = ops.lora_down(o1, ab1[6], split=True, pieces=lambda: lo1.weight_pieces("A"))
+            h1 = ops.gemm(o1, lo1.base_layer.weight, bias=lo1.base_layer.bias, epilogue="gated_residual",
+                          aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm,
+                          ext=(su, lo1.weight_split("B")))
+            del su
+        else:
+            h1 = ops.gemm(o1, a1.to_out[0].weight, bias=a1.to_out[0].bias, epilogue="gated_residual",
+                          aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm)
         # ---- 2. attn2 on the un-normalised h1 (attention.py:273-285), LoRA fused into the GEMMs
         wq, bq, _ = _lin(a2.to_q)
         wo, bo, _ = _lin(a2.to_out[0])
@@ -523,10 +647,11 @@ class _BlockFn(torch.autograd.Function):
         if keep:
             lora_saved = (u_q, u_k, u_v, u_o) if has_lora else ()
             full_saved = (x1, y1, y3) if full else ()
+            lora1_saved = (*ab1, u1, u_o1, x1) if has1 else ()
             ctx.save_for_backward(h, enc2, mods, onep, rstd1, qkv, qk, rq1, rk1, o1, lse1, h1,
                                   q2raw, rq2, q2, k2raw, rk2, k2, v2, o2, lse2, h2, rstd2, fpre,
-                                  *lora_ab, *lora_saved, *full_saved)
-            ctx.blk, ctx.sh, ctx.has_lora, ctx.full = blk, sh, has_lora, full
+                                  *lora_ab, *lora_saved, *full_saved, *lora1_saved)
+            ctx.blk, ctx.sh, ctx.has_lora, ctx.full, ctx.has1 = blk, sh, has_lora, full, has1
         return h3
 
     @staticmethod
@@ -551,6 +676,13 @@ class _BlockFn(torch.autograd.Function):
             u_q, u_k, u_v, u_o = saved[32:36]
             lora = _lora_params(blk)
             r, s = lora[0].r, lora[0].scaling
+        has1 = ctx.has1
+        if has1:
+            o1s = 36 if has_lora else 24
+            ab1 = saved[o1s:o1s + 8]
+            u1, u_o1, x1 = saved[o1s + 8:o1s + 11]
+            lora1 = _lora_params1(blk)
+            r1, s1 = lora1[0].r, lora1[0].scaling
         # ---- FF: h3 = h2 + g_mlp * ff(x2)
         rpm = sh.rpm
         pre, sh.ffo_pre = sh.ffo_pre, None
@@ -710,7 +842,16 @@ class _BlockFn(torch.autograd.Function):
         delta1 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if _DELTA_FUSED else None
         rd = dict(epilogue="store_rowdot", aux0=o1, aux1=delta1, rank=d, rows_per_batch=N) \
             if _DELTA_FUSED else {}
-        do1 = ops.gemm(d_y1, W["out1_wT"], **rd)
+        if has1:
+            # to_out.0's adapter: dB_o, dA_o (x = o1) into .grad; w_o = s d_y1 B_o rides the dgrad's
+            # K extension with A_o's split
+            lo1 = lora1[3]
+            _, sw = _lora_backward(d_y1, u_o1, lo1, ab1[7], o1, r1, s1)
+            do1 = ops.gemm(d_y1, W["out1_wT"], ext=(sw, lo1.weight_split("A")), **rd)
+            del sw
+            grads_lora = grads_lora + [None] * 8
+        else:
+            do1 = ops.gemm(d_y1, W["out1_wT"], **rd)
         if full:  # gate_msa, attn1.to_out.0
             ops.colsum_into(dmods[:, 2], dh1, y1, mode=1, rows_per_group=rpm, sum_groups=False,
                             accumulate=False)
@@ -738,8 +879,13 @@ class _BlockFn(torch.autograd.Function):
             del dwqkv
         del dq1, dk1
         dh = None
+        if has1:  # dB / dA of the q / k / v adapters (one pass over dqkv, one over x1) and w's split
+            sw1 = _qkv_lora_backward(dqkv, u1, lora1, ab1, x1, r1, s1)
         if ctx.needs_input_grad[4] or full:  # (blk, sh, keep, skip, h, ...)
-            dx1 = ops.gemm(dqkv, W["qkv_wT"])
+            if has1:  # + sum_g w_g . A_g: a plain K extension of 3 K2
+                dx1 = ops.gemm(dqkv, W["qkv_wT"], ext=(sw1, _qkv_ext(blk, lora1[0], lora1[1], lora1[2])[2]))
+            else:
+                dx1 = ops.gemm(dqkv, W["qkv_wT"])
             g_prev = None if full else sh.ffgate.get(id(blk))
             if g_prev is not None:
                 dh, d_ffo_prev = ops.rmsnorm_modulate_bwd(dx1, h, rstd1, onep[:, 1], ldm, rpm,
@@ -791,6 +937,16 @@ class _CaptionProjFn(torch.autograd.Function):
 def _lora_ab(blk):
     """[A_q, B_q, A_k, B_k, A_v, B_v, A_o, B_o] adapter weights of attn2 (or [])."""
     lora = _lora_params(blk)
+    ab = []
+    if lora is not None:
+        for m in lora:
+            ab += _ab(m)
+    return ab
+
+
+def _lora_ab1(blk):
+    """[A_q, B_q, A_k, B_k, A_v, B_v, A_o, B_o] adapter weights of attn1 (or [])."""
+    lora = _lora_params1(blk)
     ab = []
     if lora is not None:
         for m in lora:
@@ -1246,8 +1402,10 @@ class Transformer3DModel(nn.Module):
         lins = [_lora_params(b) for b in blocks]
         if any(l is None for l in lins):
             return None
+        # (+ the identity of attn1.to_q: wrapping attn1 later changes the blocks' parameter lists)
         key = tuple((id(l[1]), id(l[2]), _base(l[1])._parameters["weight"].requires_grad,
-                     _base(l[2])._parameters["weight"].requires_grad) for l in lins)
+                     _base(l[2])._parameters["weight"].requires_grad,
+                     id(b._modules["attn1"]._modules["to_q"])) for l, b in zip(lins, blocks))
         c = getattr(self, "_tx_struct", None)
         if c is not None and c[0] == key:
             return c[1]
@@ -1505,7 +1663,7 @@ class Transformer3DModel(nn.Module):
                 with torch.no_grad():
                     mods, onep = ops.ada_modulation(blk.scale_shift_table, tmod,
                                                     (1 << 1) | (1 << 4))
-            ab = _lora_ab(blk)
+            ab = _lora_ab(blk) + _lora_ab1(blk)
             if fuse_gate:
                 if prev_gate is not None:
                     sh.ffgate[id(blk)] = prev_gate
