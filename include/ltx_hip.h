@@ -340,9 +340,13 @@ int ltx_lora_dy_workspace(int64_t M, int64_t N, int64_t r, int64_t* floats);
 /* ltx_lora_dy plus the same adapter's lora_A gradient (the rest of peft lora.Linear's backward,
  * training.py:50-68: dA = alpha_a * x^T . w with w the f32 term above, as ltx_lora_wgrad(x, w,
  * alpha_a) computes it): dwa[k*ona + j*oja] (+)= alpha_a * sum_m X[m,k] * w[m,j] (acc_a != 0 adds),
- * X bf16 [M,K] (ldx), K % 512 == 0, N <= 2048. Three launches instead of ltx_lora_dy's two plus
+ * X bf16 [M,K] (ldx), K % 512 == 0, any N % 512 == 0 (the feed-forward's 8192 included: the dA
+ * pass sums w from the N / 512 column partials of the dY pass in the finish kernel's order, four
+ * loads in flight at a time beyond N = 2048; calls with N <= 2048 run the code they always ran).
+ * Three launches instead of ltx_lora_dy's two plus
  * ltx_lora_wgrad's two; every output bitwise those calls' (dA where ltx_lora_wgrad takes its
- * token-sized path, M >= 2048; below, the same products in another f32 order).
+ * token-sized path, M >= 2048; below, the same products in another f32 order). The grouped form
+ * below keeps N <= 2048 per group.
  * workspace: ltx_lora_dy_dA_workspace. */
 int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_t ldu, const void* w3, int64_t ldw3,
                    const void* x, int64_t ldx, int64_t M, int64_t N, int64_t K, int64_t r, float alpha,

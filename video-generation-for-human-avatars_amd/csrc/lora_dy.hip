@@ -41,7 +41,7 @@ namespace ltx {
 namespace {
 constexpr int DY_NR = 4;     // ring slots per wave
 constexpr int DY_COLS = 512; // columns per block
-constexpr int DY_MAXCS = 4;  // column splits a MODE-6 pass sums its u from (N <= 2048)
+constexpr int DY_MAXCS = 4;  // column splits a MODE-6 pass sums its u from (N <= 2048; MODE 14: per loop trip)
 // A block works on one rank slice of DY_SW(r) <= 32 columns of the adapter: the whole rank up to
 // r = 32, so dY is streamed from HBM once; ranks 64 / 128 run 2 / 4 slices per dY tile as
 // consecutive blockIdx.x of the same launch, each streaming the tile again (at 6r FLOP/B those
@@ -62,6 +62,8 @@ constexpr bool dy_rank_ok(int64_t r) { return r == 8 || r == 16 || r == 32 || r 
 // Bit 2 (with bit 1, round 6): u is not read but summed from another pass's column-split w partials
 // part_u[c][j][m] (c < CSu, in c order) times alpha_u -- bitwise the w lora_dy_finish_kernel writes
 // from them -- so the dA pass of an adapter (dA = w^T . x) need not wait for that finish launch.
+// Bit 3 (with bits 2 and 1, MODE 14): the same from any number of partials (N > 2048, the feed-forward's
+// d_f [M, 8192]): a loop over groups of DY_MAXCS partials, one running sum in c order.
 template <int R, int MODE>
 __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__ y, int64_t ldy,
                                                       const float* __restrict__ u, int64_t ldu,
@@ -422,7 +424,8 @@ extern "C" int ltx_lora_dy_dA_workspace(int64_t M, int64_t N, int64_t K, int64_t
 // ltx_lora_dy + the adapter's dA = alpha_a . x^T . w ([K, r] or [r, K]) in three launches instead of
 // four: the dY pass (w and dB partials), the x pass reading w from those partials (lora_dy_kernel
 // MODE 6), and one finish for w / split, dB and dA. Every output is bitwise what ltx_lora_dy followed
-// by ltx_lora_wgrad(x, w, alpha_a) produces (dA: where that takes lora_wgrad_rows, M >= 2048).
+// by ltx_lora_wgrad(x, w, alpha_a) produces (dA: where that takes lora_wgrad_rows, M >= 2048). Any N
+// that is a multiple of 512: up to 2048 the x pass is MODE 6, beyond it MODE 14.
 extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_t ldu, const void* w3, int64_t ldw3,
                               const void* x, int64_t ldx, int64_t M, int64_t N, int64_t K, int64_t r, float alpha,
                               float* w, int64_t ldw_out, void* split, int64_t ld_split, int64_t K2, float* dw,
@@ -431,7 +434,6 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
   LTX_CHECK_ARG(y && u && w3 && x && w && split && dw && dwa && workspace, "lora_dy_dA: null operand");
   LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && K % DY_COLS == 0 && dy_rank_ok(r),
                 "lora_dy_dA: M % 32 == 0, N % 512 == 0, K % 512 == 0, rank 8, 16, 32, 64 or 128");
-  LTX_CHECK_ARG(N <= DY_MAXCS * DY_COLS, "lora_dy_dA: N <= 2048 (the dA pass sums w from <= 4 column splits)");
   LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldw3 % 8 == 0 && ((uintptr_t)w3 % 16) == 0 && ldw3 >= N,
                 "lora_dy_dA: 16-B aligned rows of dY and of the pieces");
   LTX_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldx >= K, "lora_dy_dA: 16-B aligned rows of x");
@@ -456,9 +458,14 @@ extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_
   hipLaunchKernelGGL((lora_dy_kernel<RR, 3>), dim3((unsigned)(CS * NSL), (unsigned)RS), dim3(512), 0, s, (const bf16_t*)y, \
                      ldy, u, ldu, (const bf16_t*)w3, ldw3, pw, pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f);  \
   LTX_LAUNCH_CHECK();                                                                                              \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 6>), dim3((unsigned)(CSx * NSL), (unsigned)RS), dim3(512), 0, s,         \
-                     (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr, (int64_t)0, \
-                     (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, CS, alpha);                             \
+  if (CS <= DY_MAXCS)                                                                                              \
+    hipLaunchKernelGGL((lora_dy_kernel<RR, 6>), dim3((unsigned)(CSx * NSL), (unsigned)RS), dim3(512), 0, s,       \
+                       (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr,           \
+                       (int64_t)0, (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, CS, alpha);              \
+  else                                                                                                             \
+    hipLaunchKernelGGL((lora_dy_kernel<RR, 14>), dim3((unsigned)(CSx * NSL), (unsigned)RS), dim3(512), 0, s,      \
+                       (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr,           \
+                       (int64_t)0, (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, CS, alpha);              \
   LTX_LAUNCH_CHECK();                                                                                              \
   hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), dim3((unsigned)(nwb + nbb + nba)), dim3(256), 0, s, pw, CS, pb,  \
                      RS, (int)M, (int)N, alpha, w, ldw_out, (bf16_t*)split, ld_split, (int)K2, dw, on, oj,         \

@@ -79,7 +79,41 @@
   // rolled loop waited out one load round trip per element, ~2 us per block)
   constexpr int UPT = (DY_G * 32 * SW + 511) / 512;
   float uv[UPT];
-  if constexpr ((MODE & 4) != 0) {  // u from the w partials: e -> (j, row), rows fastest (coalesced)
+  if constexpr ((MODE & 8) != 0) {
+    // u from more than DY_MAXCS w partials (the dY pass ran on N > 2048 columns, e.g. the feed-forward's
+    // 8192): DY_MAXCS partials per element in flight at a time, added in c order from 0 into one running
+    // sum -- the order of lora_dy_finish_kernel, so u is bitwise the w that kernel writes. A separate
+    // branch: the MODE-6 instantiations (CSu <= DY_MAXCS) keep their code
+    float accu[UPT];
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) accu[i] = 0.f;
+    for (int cb = 0; cb < CSu; cb += DY_MAXCS) {
+      float pv[UPT][DY_MAXCS];
+#pragma unroll
+      for (int i = 0; i < UPT; ++i) {
+        const int e = tid + 512 * i, j = j0 + e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
+        const bool ok = e < DY_G * 32 * SW && m < M && j < R;
+#pragma unroll
+        for (int c = 0; c < DY_MAXCS; ++c)
+          pv[i][c] = part_u[((int64_t)(cb + c < CSu ? cb + c : 0) * RP + (ok ? j : 0)) * M + (ok ? m : 0)];
+      }
+#pragma unroll
+      for (int i = 0; i < UPT; ++i)
+#pragma unroll
+        for (int c = 0; c < DY_MAXCS; ++c)
+          if (cb + c < CSu) accu[i] += pv[i][c];
+    }
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+      const int e = tid + 512 * i, j = j0 + e / (DY_G * 32), rr = e % (DY_G * 32), m = mb + rr;
+      uv[i] = (e < DY_G * 32 * SW && m < M && j < R) ? accu[i] * alpha_u : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+      const int e = tid + 512 * i;
+      if (e < DY_G * 32 * SW) ut[(e / (DY_G * 32)) * DY_UPAD + e % (DY_G * 32)] = uv[i];
+    }
+  } else if constexpr ((MODE & 4) != 0) {  // u from the w partials: e -> (j, row), rows fastest (coalesced)
     // every partial load in flight before the first add (CSu <= DY_MAXCS; loads past CSu or past the
     // block's rows read partial 0 / row 0 and are not added); then the sum in c order from 0
     float pv[UPT][DY_MAXCS];

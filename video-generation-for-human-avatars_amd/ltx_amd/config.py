@@ -117,4 +117,8 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     if "lora_targets" in t:
         v = t["lora_targets"]
         setattr(config, "lora_targets", v if isinstance(v, str) else tuple(v))
+    # likewise `train.lora_ff` (a bool, absent = False): adapters on both feed-forward linears of
+    # every block as well (ff.net.0.proj and ff.net.2), with lora_rank / lora_alpha
+    if "lora_ff" in t:
+        setattr(config, "lora_ff", bool(t["lora_ff"]))
     return config

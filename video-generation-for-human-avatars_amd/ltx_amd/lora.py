@@ -4,7 +4,8 @@
 0.17.1 parameter names and init: kaiming-uniform(a=sqrt(5)) A, zero B, f32 adapters on the bf16
 base, scaling = alpha / r) and makes only `lora_*` and `caption_projection` trainable.
 `config.lora_targets` ("attn2" by default; "attn1", "attn1+attn2" or a tuple of those names) also
-or instead wraps the same four projections of the self-attention attn1.
+or instead wraps the same four projections of the self-attention attn1. `config.lora_ff` (a bool,
+absent = False) also wraps both feed-forward linears of every block, ff.net.0.proj and ff.net.2.
 'full': the reference's substring rule (training.py:75-91); the fused block backward raises for
 it until the wgrad path (next row) lands.
 """
@@ -16,6 +17,7 @@ from .transformer3d import LoraLinear
 
 LORA_ATTENTIONS = ("attn1", "attn2")  # the attentions whose four projections can carry adapters
 _PROJECTIONS = ("to_q", "to_k", "to_v", "to_out.0")  # the reference's order (training.py:52-60)
+_FF_LINEARS = ("net.0.proj", "net.2")  # the feed-forward's two linears, in forward order
 
 
 def _attentions(attention):
@@ -37,15 +39,27 @@ def lora_target_modules(num_blocks, attention=("attn2",)):
     return out
 
 
-def _check_targets(model, targets):
+def lora_ff_target_modules(num_blocks):
+    """Both feed-forward linears of every block, in block order (config.lora_ff; inject_lora accepts
+    these names with feed_forward=True)."""
+    return [f"transformer_blocks.{i}.ff.{p}" for i in range(num_blocks) for p in _FF_LINEARS]
+
+
+def _check_targets(model, targets, feed_forward=False):
     """Before any module is replaced: every name is `transformer_blocks.<i>.<attn1|attn2>.<to_q|to_k|
     to_v|to_out.0>` of this model (ValueError naming the accepted set), and together with the
     adapters already present each attention ends up with none or all four of its projections
-    wrapped (NotImplementedError: the fused block has no path for a partly adapted attention)."""
+    wrapped (NotImplementedError: the fused block has no path for a partly adapted attention). With
+    feed_forward=True the names `transformer_blocks.<i>.ff.<net.0.proj|net.2>` are accepted as well,
+    under the same rule: both linears of a block's feed-forward or none."""
     n = len(model.transformer_blocks)
     want = set()
     for name in targets:
         parts = name.split(".", 3)
+        if (feed_forward and len(parts) == 4 and parts[0] == "transformer_blocks" and parts[1].isdigit()
+                and int(parts[1]) < n and parts[2] == "ff" and parts[3] in _FF_LINEARS):
+            want.add((int(parts[1]), "ff", parts[3]))
+            continue
         ok = (len(parts) == 4 and parts[0] == "transformer_blocks" and parts[1].isdigit() and int(parts[1]) < n
               and parts[2] in LORA_ATTENTIONS and parts[3] in _PROJECTIONS)
         if not ok:
@@ -60,12 +74,20 @@ def _check_targets(model, targets):
             if any(have) and not all(have):
                 raise NotImplementedError(f"LoRA must wrap all four projections of transformer_blocks.{i}.{a} "
                                           f"({', '.join(_PROJECTIONS)}) or none (training.py:52-60)")
+        net = blk.ff.net
+        have = [isinstance(net[0].proj, LoraLinear) or (i, "ff", _FF_LINEARS[0]) in want,
+                isinstance(net[2], LoraLinear) or (i, "ff", _FF_LINEARS[1]) in want]
+        if any(have) and not all(have):
+            raise NotImplementedError(f"LoRA must wrap both linears of transformer_blocks.{i}.ff "
+                                      f"({', '.join(_FF_LINEARS)}) or none")
 
 
-def inject_lora(model, targets, r, alpha):
+def inject_lora(model, targets, r, alpha, *, feed_forward=False):
+    """Wrap the named linears in LoraLinear. feed_forward=True also accepts the names of
+    lora_ff_target_modules; without it they are refused like any name outside the attentions."""
     ops.check_lora_rank(r)  # before the first module is replaced
     targets = list(targets)
-    _check_targets(model, targets)
+    _check_targets(model, targets, feed_forward)
     for name in targets:
         parent_name, _, child = name.rpartition(".")
         parent = model.get_submodule(parent_name)
@@ -85,8 +107,16 @@ def apply_training_strategy(model, config, train_mode: str):
         # the attentions that carry adapters: config.lora_targets, set with setattr as the reference
         # sets train_mode (not a TrainConfig field); default = the reference's attn2 (training.py:50-60)
         attention = getattr(config, "lora_targets", ("attn2",))
-        inject_lora(model, lora_target_modules(len(model.transformer_blocks), attention), config.lora_rank,
-                    config.lora_alpha)
+        targets = lora_target_modules(len(model.transformer_blocks), attention)
+        # config.lora_ff (setattr or train.lora_ff in the YAML; absent = False): both feed-forward
+        # linears of every block as well
+        ff = bool(getattr(config, "lora_ff", False))
+        if ff:
+            targets = targets + lora_ff_target_modules(len(model.transformer_blocks))
+        if ff:
+            inject_lora(model, targets, config.lora_rank, config.lora_alpha, feed_forward=True)
+        else:
+            inject_lora(model, targets, config.lora_rank, config.lora_alpha)
         for n, p in model.named_parameters():
             p.requires_grad = ("lora_" in n) or ("caption_projection" in n)
         return model
@@ -122,12 +152,13 @@ def merged_state_dict(model):
 @torch.no_grad()
 def unload_lora(model):
     """peft merge_and_unload in place: base_layer.weight += (B @ A) * scaling (promoted add
-    rounded to the base dtype), each LoraLinear replaced by its base nn.Linear."""
+    rounded to the base dtype), each LoraLinear replaced by its base nn.Linear. The sum is taken in
+    f32 and rounded once (LoraLinear.merged_weight), so the unloaded model holds bitwise the weights
+    of merged_state_dict on every device (torch's in-place bf16 += f32 on the GPU came out one bf16
+    step away from that on some elements)."""
     for name, mod in list(model.named_modules()):
         if isinstance(mod, LoraLinear):
-            a = mod.lora_A["default"].weight
-            b = mod.lora_B["default"].weight
-            mod.base_layer.weight.data += (b @ a) * mod.scaling
+            mod.base_layer.weight.data.copy_(mod.merged_weight())
             parent_name, _, child = name.rpartition(".")
             parent = model.get_submodule(parent_name)
             if child.isdigit():

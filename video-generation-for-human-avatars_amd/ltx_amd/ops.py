@@ -774,8 +774,9 @@ def lora_dy_da_enabled():
 def lora_dy_da_fits(y, x, r):
     """lora_dy(y, ..., x=x) applies (and LTX_LORA_DY_DA is not 0). Only at M >= 2048, where
     ltx_lora_wgrad takes the same token-sized path, so the merged call is bitwise the separate ones
-    (below it ltx_lora_wgrad runs the f32-MFMA kernel: another rounding of dA)."""
-    return (lora_dy_da_enabled() and lora_dy_fits(x, r) and y.shape[1] <= 2048 and x.shape[0] == y.shape[0]
+    (below it ltx_lora_wgrad runs the f32-MFMA kernel: another rounding of dA). Any dY width that is
+    a multiple of 512 (the feed-forward's 8192 included)."""
+    return (lora_dy_da_enabled() and lora_dy_fits(x, r) and y.shape[1] % 512 == 0 and x.shape[0] == y.shape[0]
             and y.shape[0] >= 2048)
 
 
@@ -857,7 +858,7 @@ def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=
     """One pass over dY (ltx_lora_dy): returns (w, split) as lora_down(y, B, transposed=True,
     split=True) does, and adds alpha * y^T . u into dB_out ([N, r], or [r, N] with transpose_out)
     as lora_wgrad(y, u, alpha, out=dB_out, accumulate=accumulate) does. With x ([M, K] bf16,
-    lora_dy_fits; N <= 2048) and dA_out ([r, K] f32): also dA_out (+)= x^T . w as lora_wgrad(x, w,
+    lora_dy_fits; any N % 512 == 0) and dA_out ([r, K] f32): also dA_out (+)= x^T . w as lora_wgrad(x, w,
     transpose_out=True, out=dA_out, accumulate=dA_accumulate) does, bitwise, with one launch fewer
     than the two calls (ltx_lora_dy_dA). w_out / split_out: [M, r] f32 / [M, K2] bf16 column views of
     the caller's wider buffers to write w and its split into."""
@@ -872,7 +873,7 @@ def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=
     n = ctypes.c_int64(0)
     if x is not None:
         K = x.shape[1]
-        assert x.shape[0] == M and x.dtype == BF16 and lora_dy_fits(x, r) and N <= 2048
+        assert x.shape[0] == M and x.dtype == BF16 and lora_dy_fits(x, r) and N % 512 == 0
         assert tuple(dA_out.shape) == (r, K) and dA_out.dtype == F32 and dA_out.is_contiguous()
         call("ltx_lora_dy_dA_workspace", M, N, K, r, ctypes.byref(n))
         ws = torch.empty(n.value, dtype=F32, device=y.device)

@@ -378,11 +378,12 @@ def _qkv_lora_down(x1, lora1, ab1, r):
     return u, su
 
 
-def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None):
+def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da=True):
     """One adapter's backward: dB and dA into .grad, returns (w = s dY B, its split operand). The
-    one-pass forms where they apply (ops.lora_dy), else lora_wgrad + lora_down."""
+    one-pass forms where they apply (ops.lora_dy), else lora_wgrad + lora_down. merge_da=False keeps
+    dA a separate lora_wgrad call even where the merged ltx_lora_dy_dA applies (bitwise the same)."""
     dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dy, r)
-    if dy_ok and ops.lora_dy_da_fits(dy, x, r):
+    if dy_ok and merge_da and ops.lora_dy_da_fits(dy, x, r):
         # one pass over dY, one over x (dA), one finish for w / split, dB and dA
         return ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), x=x,
                            dA_out=_grad_buf(lin, "A"), w_out=w_out, split_out=split_out)
@@ -517,6 +518,36 @@ def _lora_params1(blk):
     return lins
 
 
+def _lora_params_ff(blk):
+    """The LoraLinear of the feed-forward's two linears (ff.net.0.proj, ff.net.2; config.lora_ff), or
+    None (no adapters). Both or none, and one rank and scaling for the two."""
+    net = blk._modules["ff"]._modules["net"]._modules
+    lins = (net["0"]._modules["proj"], net["2"])
+    kinds = [type(m) is LoraLinear for m in lins]
+    if not all(kinds):
+        if any(kinds):
+            raise NotImplementedError("LoRA must wrap both feed-forward linears (ff.net.0.proj, ff.net.2) or none")
+        return None
+    if lins[0].r != lins[1].r or lins[0].scaling != lins[1].scaling:
+        raise NotImplementedError("the feed-forward adapters of one block must share rank and scaling")
+    return lins
+
+
+# the backward of the ff.net.0.proj adapter needs the modulated norm output x2 (dA1 = w1^T . x2): kept
+# from the forward by default (one [M, D] bf16 more per block), LTX_LORA_FF_KEEP_X2=0 recomputes it
+# from h2 / rstd2 instead (rmsnorm_modulate_fwd, bitwise the forward's; 0.8 ms per step slower at
+# config A, profiles/lora_ff_bench.md)
+def _ff_keep_x2():
+    return os.environ.get("LTX_LORA_FF_KEEP_X2", "1") != "0"
+
+
+# the feed-forward adapters' backward keeps dA a separate ltx_lora_wgrad call: at their widths
+# (dY = d_f [M, 8192], or x = act [M, 8192]) the merged ltx_lora_dy_dA measured 3 - 35 us per launch
+# slower (profiles/lora_ff_bench.md). LTX_LORA_FF_DY_DA=1 selects the merged form, bitwise the same
+def _ff_merge_da():
+    return os.environ.get("LTX_LORA_FF_DY_DA", "0") == "1"
+
+
 def _ab(m):
     """(lora_A weight, lora_B weight) of a LoraLinear, by direct lookup."""
     return (m._modules["lora_A"]._modules["default"]._parameters["weight"],
@@ -547,17 +578,23 @@ class _BlockFn(torch.autograd.Function):
         W = blk.packed()
         a1, a2, ff = blk.attn1, blk.attn2, blk.ff
         ldm = mods.stride(0)
-        # lora_ab = the attn2 adapters' 8 tensors (_lora_ab), then the attn1 adapters' 8 (_lora_ab1)
+        # lora_ab = the attn2 adapters' 8 tensors (_lora_ab), then the attn1 adapters' 8 (_lora_ab1),
+        # then the feed-forward adapters' 4 (_lora_abf): A1, B1 of ff.net.0.proj, A2, B2 of ff.net.2
         lora = _lora_params(blk) if len(lora_ab) > 0 else None
         has_lora = lora is not None
-        lora1 = _lora_params1(blk) if len(lora_ab) > (8 if has_lora else 0) else None
+        n_rest = len(lora_ab) - (8 if has_lora else 0)
+        lora1 = _lora_params1(blk) if n_rest >= 8 else None
         has1 = lora1 is not None
-        ab1 = lora_ab[8:] if has_lora else lora_ab
+        loraf = _lora_params_ff(blk) if n_rest % 8 == 4 else None
+        hasf = loraf is not None
+        o1 = 8 if has_lora else 0
+        abf = lora_ab[o1 + (8 if has1 else 0):] if hasf else ()
+        ab1 = lora_ab[o1:o1 + 8] if has1 else ()
         lora_ab = lora_ab[:8] if has_lora else ()
         r = lora[0].r if has_lora else 0
         s = lora[0].scaling if has_lora else 1.0
         full = sh.full and keep
-        if (has_lora or has1) and full:  # before the block's first launch
+        if (has_lora or has1 or hasf) and full:  # before the block's first launch
             raise NotImplementedError("train_mode='full' trains the base weights without LoRA")
         # ---- 1. norm1 + AdaLN(msa) -> fused QKV -> q/k RMSNorm + RoPE -> SDPA -> gated residual
         x1, rstd1 = ops.rmsnorm_modulate_fwd(h, mods[:, 0], onep[:, 1], ldm, rpm, blk.norm_eps)
@@ -635,23 +672,45 @@ class _BlockFn(torch.autograd.Function):
         # fpre: rint(32767 gelu_tanh'(pre-activation) / 2) (int16), kept by the GELU epilogue for the
         # backward's multiply (ltx_hip.h LTX_EPI_GELU)
         fpre = torch.empty(M, ff.net[0].proj.out_features, dtype=torch.int16, device=h.device)
-        act = ops.gemm(x2, ff.net[0].proj.weight, bias=ff.net[0].proj.bias, epilogue="gelu",
-                       aux0=fpre)
-        del x2
         y3 = torch.empty(M, D, dtype=torch.bfloat16, device=h.device) if full else None
-        h3 = ops.gemm(act, ff.net[2].weight, bias=ff.net[2].bias, epilogue="gated_residual",
-                      aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm)
-        del act
+        if hasf:
+            # the feed-forward adapters ride the two GEMMs' K extension: u1 = x2 . A1^T with s B1 under
+            # the GELU epilogue (fpre is then the derivative at the adapted pre-activation), u2 =
+            # act . A2^T (K = 8192) with s B2 under the gated residual
+            lf1, lf2 = loraf
+            u_f1, su = ops.lora_down(x2, abf[0], split=True, pieces=lambda: lf1.weight_pieces("A"))
+            act = ops.gemm(x2, lf1.base_layer.weight, bias=lf1.base_layer.bias, epilogue="gelu", aux0=fpre,
+                           ext=(su, lf1.weight_split("B")))
+            if not (keep and _ff_keep_x2()):
+                del x2
+            u_f2, su = ops.lora_down(act, abf[2], split=True, pieces=lambda: lf2.weight_pieces("A"))
+            h3 = ops.gemm(act, lf2.base_layer.weight, bias=lf2.base_layer.bias, epilogue="gated_residual",
+                          aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm,
+                          ext=(su, lf2.weight_split("B")))
+            del su
+            if not keep:
+                del act
+        else:
+            act = ops.gemm(x2, ff.net[0].proj.weight, bias=ff.net[0].proj.bias, epilogue="gelu",
+                           aux0=fpre)
+            del x2
+            h3 = ops.gemm(act, ff.net[2].weight, bias=ff.net[2].bias, epilogue="gated_residual",
+                          aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm)
+            del act
         if strat is SkipLayerStrategy.TransformerBlock:
             h3 = ops.skip_blend(h3, h, skip[0], N)
         if keep:
             lora_saved = (u_q, u_k, u_v, u_o) if has_lora else ()
             full_saved = (x1, y1, y3) if full else ()
             lora1_saved = (*ab1, u1, u_o1, x1) if has1 else ()
+            # the feed-forward adapters keep the GELU output (dA2 = w2^T . act; [M, 4D] bf16) and
+            # their two u, and x2 unless LTX_LORA_FF_KEEP_X2=0
+            loraf_saved = (*abf, u_f1, u_f2, act, *((x2,) if _ff_keep_x2() else ())) if hasf else ()
             ctx.save_for_backward(h, enc2, mods, onep, rstd1, qkv, qk, rq1, rk1, o1, lse1, h1,
                                   q2raw, rq2, q2, k2raw, rk2, k2, v2, o2, lse2, h2, rstd2, fpre,
-                                  *lora_ab, *lora_saved, *full_saved, *lora1_saved)
+                                  *lora_ab, *lora_saved, *full_saved, *lora1_saved, *loraf_saved)
             ctx.blk, ctx.sh, ctx.has_lora, ctx.full, ctx.has1 = blk, sh, has_lora, full, has1
+            ctx.hasf = hasf
         return h3
 
     @staticmethod
@@ -683,6 +742,14 @@ class _BlockFn(torch.autograd.Function):
             u1, u_o1, x1 = saved[o1s + 8:o1s + 11]
             lora1 = _lora_params1(blk)
             r1, s1 = lora1[0].r, lora1[0].scaling
+        hasf = ctx.hasf
+        if hasf:
+            of = 24 + (12 if has_lora else 0) + (11 if has1 else 0)
+            abf = saved[of:of + 4]
+            u_f1, u_f2, act = saved[of + 4:of + 7]
+            x2 = saved[of + 7] if len(saved) > of + 7 else None
+            lf1, lf2 = _lora_params_ff(blk)
+            rf, sf = lf1.r, lf1.scaling
         # ---- FF: h3 = h2 + g_mlp * ff(x2)
         rpm = sh.rpm
         pre, sh.ffo_pre = sh.ffo_pre, None
@@ -697,10 +764,24 @@ class _BlockFn(torch.autograd.Function):
         if full:  # gate_mlp: sum over the batch's rows of bf16(dh3 * y3) (attention.py:305-308)
             ops.colsum_into(dmods[:, 5], dh3, y3, mode=1, rows_per_group=rpm, sum_groups=False,
                             accumulate=False)
-        d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre)
-        del d_ffo
-        dx2 = ops.gemm(d_f, W["ff1_wT"])
-        del d_f
+        if hasf:
+            # ff.net.2's adapter: dY = d_ffo, x = act (K = 8192); w2 = s d_ffo B2 rides the GELU-backward
+            # GEMM's K extension with A2's split. ff.net.0.proj's: dY = d_f [M, 4D], x = x2; w1 rides dx2's
+            _, sw = _lora_backward(d_ffo, u_f2, lf2, abf[3], act, rf, sf, merge_da=_ff_merge_da())
+            d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre, ext=(sw, lf2.weight_split("A")))
+            del d_ffo, act, sw
+            if x2 is None:  # bitwise the forward's x2
+                x2, _ = ops.rmsnorm_modulate_fwd(h2, mods[:, 3], onep[:, 4], ldm, rpm, blk.norm_eps)
+            _, sw = _lora_backward(d_f, u_f1, lf1, abf[1], x2, rf, sf, merge_da=_ff_merge_da())
+            del x2
+            dx2 = ops.gemm(d_f, W["ff1_wT"], ext=(sw, lf1.weight_split("A")))
+            del d_f, sw
+            grads_lora = [None] * 4
+        else:
+            d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre)
+            del d_ffo
+            dx2 = ops.gemm(d_f, W["ff1_wT"])
+            del d_f
         dh2 = ops.rmsnorm_modulate_bwd(dx2, h2, rstd2, onep[:, 4], ldm, rpm, dres=dh3)
         if full:  # shift_mlp / scale_mlp (attention.py:287-290)
             ops.colsum_into(dmods[:, 3], dx2, rows_per_group=rpm, sum_groups=False, accumulate=False)
@@ -831,7 +912,7 @@ class _BlockFn(torch.autograd.Function):
                 del swkv
             # the adapter gradients went straight into .grad (accumulated across micro-steps by
             # the kernels' atomics); autograd gets None for them
-            grads_lora = [None] * 8
+            grads_lora = grads_lora + [None] * 8
         else:
             dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2, **gated)
             if tx is None:
@@ -947,6 +1028,16 @@ def _lora_ab(blk):
 def _lora_ab1(blk):
     """[A_q, B_q, A_k, B_k, A_v, B_v, A_o, B_o] adapter weights of attn1 (or [])."""
     lora = _lora_params1(blk)
+    ab = []
+    if lora is not None:
+        for m in lora:
+            ab += _ab(m)
+    return ab
+
+
+def _lora_abf(blk):
+    """[A_1, B_1, A_2, B_2] adapter weights of ff.net.0.proj and ff.net.2 (or [])."""
+    lora = _lora_params_ff(blk)
     ab = []
     if lora is not None:
         for m in lora:
@@ -1402,10 +1493,12 @@ class Transformer3DModel(nn.Module):
         lins = [_lora_params(b) for b in blocks]
         if any(l is None for l in lins):
             return None
-        # (+ the identity of attn1.to_q: wrapping attn1 later changes the blocks' parameter lists)
+        # (+ the identity of attn1.to_q and of ff.net.2: wrapping attn1 or the feed-forward later
+        # changes the blocks' parameter lists)
         key = tuple((id(l[1]), id(l[2]), _base(l[1])._parameters["weight"].requires_grad,
                      _base(l[2])._parameters["weight"].requires_grad,
-                     id(b._modules["attn1"]._modules["to_q"])) for l, b in zip(lins, blocks))
+                     id(b._modules["attn1"]._modules["to_q"]),
+                     id(b._modules["ff"]._modules["net"]._modules["2"])) for l, b in zip(lins, blocks))
         c = getattr(self, "_tx_struct", None)
         if c is not None and c[0] == key:
             return c[1]
@@ -1663,7 +1756,7 @@ class Transformer3DModel(nn.Module):
                 with torch.no_grad():
                     mods, onep = ops.ada_modulation(blk.scale_shift_table, tmod,
                                                     (1 << 1) | (1 << 4))
-            ab = _lora_ab(blk) + _lora_ab1(blk)
+            ab = _lora_ab(blk) + _lora_ab1(blk) + _lora_abf(blk)
             if fuse_gate:
                 if prev_gate is not None:
                     sh.ffgate[id(blk)] = prev_gate
