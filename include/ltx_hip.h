@@ -383,6 +383,27 @@ int ltx_lora_dy_dA_grouped(const void* y, int64_t ldy, const float* const* u, in
 int ltx_lora_dy_dA_grouped_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups,
                                      int64_t* floats);
 
+/* ---- LoRA dropout (peft lora_dropout; DESIGN.md "LoRA dropout") -------------------------------
+ * The mask is a pure function of (key, sid, row m, column k): Philox4x32-10 with counter
+ * (m, k / 8, sid, 0) and key (key & 0xffffffff, key >> 32) gives four words o[0..3]; element k uses
+ * the 16-bit lane j = k % 8 (low half of o[j / 2] for even j, high half for odd j) and is KEPT iff
+ * lane >= T (T = round(p * 65536) clamped to [1, 65535]). One Philox call serves 8 columns. */
+/* xd[m,k] = keep(m,k) ? x[m,k] : 0 (bf16 [M,K], row strides ldx / ldo in elements, K % 8 == 0,
+ * 16-B aligned rows; exact: the 1 / (1 - T / 65536) scale is the consumer's alpha). */
+int ltx_lora_dropout_apply(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t M, int64_t K,
+                           uint64_t key, int64_t sid, int64_t T, void* stream);
+/* The masked input-gradient term of `groups` (1..3) dropped-out adapters that share an output:
+ * dx[m,k] = bf16(f32(dx[m,k]) + t), t = c * sum_g keep_g(m,k) * sum_j w[m, g*r + j] * A_g[j*lda + k]
+ * (f32: the j sum an fma chain in j order on the exact-f32 matrix core, the g sum in g order, then
+ * the multiply by c); with gq != null (int16 [M,K], ldg: the GELU epilogue's derivative store)
+ * t = (t * gq[m,k]) * (2 / 32767). dx bf16 [M,K] (lddx) in place, w f32 [M, groups*r] (ldw), A = host
+ * array of `groups` device pointers to f32 [r, K] (row stride lda), sids = host array of the groups'
+ * mask streams. K % 8 == 0, rank 8, 16, 32, 64 or 128. Deterministic, no atomics. */
+int ltx_lora_up_masked_add(void* dx, int64_t lddx, const float* w, int64_t ldw, const float* const* A,
+                           int64_t lda, const int64_t* sids, int64_t groups, int64_t M, int64_t K,
+                           int64_t r, uint64_t key, int64_t T, float c, const void* gq, int64_t ldg,
+                           void* stream);
+
 /* ---- small ops -------------------------------------------------------------------------------- */
 /* AdaLayerNormSingle sinusoid: out[b,:] = bf16([cos(s*t*f), sin(s*t*f)]) (256 ch), s = scale */
 int ltx_timestep_embedding(const float* t, float scale, void* out, int64_t B, int64_t dim,

@@ -121,4 +121,8 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     # every block as well (ff.net.0.proj and ff.net.2), with lora_rank / lora_alpha
     if "lora_ff" in t:
         setattr(config, "lora_ff", bool(t["lora_ff"]))
+    # and `train.lora_dropout` (a float in [0, 1), absent = 0.0): peft's lora_dropout, one rate for
+    # every adapter of the model
+    if "lora_dropout" in t:
+        setattr(config, "lora_dropout", float(t["lora_dropout"]))
     return config

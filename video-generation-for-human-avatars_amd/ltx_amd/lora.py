@@ -6,18 +6,73 @@ base, scaling = alpha / r) and makes only `lora_*` and `caption_projection` trai
 `config.lora_targets` ("attn2" by default; "attn1", "attn1+attn2" or a tuple of those names) also
 or instead wraps the same four projections of the self-attention attn1. `config.lora_ff` (a bool,
 absent = False) also wraps both feed-forward linears of every block, ff.net.0.proj and ff.net.2.
+`config.lora_dropout` (a float in [0, 1), absent = 0.0) is peft's lora_dropout on every adapter; the
+keep mask is this build's own counter-based stream (lora_dropout_mask_reference states it in numpy).
 'full': the reference's substring rule (training.py:75-91); the fused block backward raises for
 it until the wgrad path (next row) lands.
 """
 import torch
 
 from . import ops
-from .transformer3d import LoraLinear
+from .transformer3d import LoraLinear, check_lora_dropout
 
 
 LORA_ATTENTIONS = ("attn1", "attn2")  # the attentions whose four projections can carry adapters
 _PROJECTIONS = ("to_q", "to_k", "to_v", "to_out.0")  # the reference's order (training.py:52-60)
 _FF_LINEARS = ("net.0.proj", "net.2")  # the feed-forward's two linears, in forward order
+
+
+# the mask streams of one block's adapters (sid = 16 * block index + slot), in this order: every wrapped
+# linear owns its own dropout module in peft, so q / k / v get independent masks on their shared input
+LORA_DROPOUT_SLOTS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0",
+                      "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0",
+                      "ff.net.0.proj", "ff.net.2")
+
+
+def lora_dropout_stream(module_name):
+    """The mask stream sid of the adapter on `transformer_blocks.<i>.<slot>` (a leading prefix such as
+    'base_model.model.' is accepted): 16 * i + the slot's index in LORA_DROPOUT_SLOTS."""
+    _, sep, rest = module_name.rpartition("transformer_blocks.")
+    idx, _, slot = rest.partition(".")
+    if not sep or not idx.isdigit() or slot not in LORA_DROPOUT_SLOTS:
+        raise ValueError(f"{module_name!r}: expected transformer_blocks.<i>.<{'|'.join(LORA_DROPOUT_SLOTS)}>")
+    return 16 * int(idx) + LORA_DROPOUT_SLOTS.index(slot)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Random123) in numpy: counter = four uint32 arrays (or ints) of one shape, key =
+    two; returns the four output words as uint32 arrays."""
+    import numpy as np
+    c = [np.asarray(v, dtype=np.uint64) & np.uint64(0xFFFFFFFF) for v in counter]
+    c = list(np.broadcast_arrays(*c))
+    k0, k1 = (int(v) & 0xFFFFFFFF for v in key)
+    m0, m1, mask = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0xFFFFFFFF)
+    sh = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]  # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> sh) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> sh) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return [v.astype(np.uint32) for v in c]
+
+
+def lora_dropout_mask_reference(key, sid, M, K, p):
+    """The keep mask (numpy bool [M, K]) of adapter stream sid under the 64-bit key at rate p, as the
+    kernels regenerate it (DESIGN.md "LoRA dropout"): Philox4x32-10 on the counter (m, k // 8, sid, 0)
+    with the key (key & 0xffffffff, key >> 32); element k takes the 16-bit lane j = k % 8 (low half of
+    o[j // 2] for even j, high half for odd j) and is kept iff lane >= T = round(p * 65536) clamped to
+    [1, 65535]. CPU only: the tests' and the golden tool's statement of the mask."""
+    import numpy as np
+    if K % 8:
+        raise ValueError("lora_dropout_mask_reference: K must be a multiple of 8")
+    T, _ = ops.lora_dropout_threshold(p)
+    key = int(key) & 0xFFFFFFFFFFFFFFFF
+    m = np.arange(M, dtype=np.uint64)[:, None]
+    kg = np.arange(K // 8, dtype=np.uint64)[None, :]
+    o = philox4x32_10((m, kg, int(sid), 0), (key & 0xFFFFFFFF, key >> 32))
+    lanes = np.empty((M, K // 8, 8), dtype=np.uint32)
+    for j in range(8):
+        lanes[:, :, j] = (o[j // 2] >> np.uint32(16 * (j % 2))) & np.uint32(0xFFFF)
+    return (lanes >= T).reshape(M, K)
 
 
 def _attentions(attention):
@@ -82,19 +137,36 @@ def _check_targets(model, targets, feed_forward=False):
                                       f"({', '.join(_FF_LINEARS)}) or none")
 
 
-def inject_lora(model, targets, r, alpha, *, feed_forward=False):
+def _check_dropout(model, targets, dropout):
+    """Before any module is replaced: the rate is in [0, 1) (ValueError), and no block ends up with
+    adapters of different rates (NotImplementedError: one key, threshold and scale per block)."""
+    p = check_lora_dropout(dropout)
+    for i in sorted({int(name.split(".")[1]) for name in targets}):
+        blk = model.transformer_blocks[i]
+        have = {getattr(m, "lora_dropout_p", 0.0) for m in blk.modules() if isinstance(m, LoraLinear)}
+        new = any(not isinstance(model.get_submodule(name), LoraLinear) for name in targets
+                  if name.startswith(f"transformer_blocks.{i}."))
+        if new and have - {p}:
+            raise NotImplementedError(f"transformer_blocks.{i} already has adapters with lora_dropout "
+                                      f"{sorted(have)}: the adapters of one block must share one rate, got {p}")
+    return p
+
+
+def inject_lora(model, targets, r, alpha, *, feed_forward=False, dropout=0.0):
     """Wrap the named linears in LoraLinear. feed_forward=True also accepts the names of
-    lora_ff_target_modules; without it they are refused like any name outside the attentions."""
+    lora_ff_target_modules; without it they are refused like any name outside the attentions.
+    dropout = peft's lora_dropout, one rate for every adapter created here."""
     ops.check_lora_rank(r)  # before the first module is replaced
     targets = list(targets)
     _check_targets(model, targets, feed_forward)
+    dropout = _check_dropout(model, targets, dropout)
     for name in targets:
         parent_name, _, child = name.rpartition(".")
         parent = model.get_submodule(parent_name)
         base = getattr(parent, child) if not child.isdigit() else parent[int(child)]
         if isinstance(base, LoraLinear):
             continue
-        wrapped = LoraLinear(base, r, alpha)
+        wrapped = LoraLinear(base, r, alpha, dropout)
         if child.isdigit():
             parent[int(child)] = wrapped
         else:
@@ -113,10 +185,15 @@ def apply_training_strategy(model, config, train_mode: str):
         ff = bool(getattr(config, "lora_ff", False))
         if ff:
             targets = targets + lora_ff_target_modules(len(model.transformer_blocks))
+        # config.lora_dropout (setattr or train.lora_dropout in the YAML; absent = 0.0): peft's
+        # lora_dropout, one rate for every adapter of the model (the reference fixes 0.0, training.py:65)
+        extra = {}
         if ff:
-            inject_lora(model, targets, config.lora_rank, config.lora_alpha, feed_forward=True)
-        else:
-            inject_lora(model, targets, config.lora_rank, config.lora_alpha)
+            extra["feed_forward"] = True
+        p = float(getattr(config, "lora_dropout", 0.0))
+        if p != 0.0:
+            extra["dropout"] = p
+        inject_lora(model, targets, config.lora_rank, config.lora_alpha, **extra)
         for n, p in model.named_parameters():
             p.requires_grad = ("lora_" in n) or ("caption_projection" in n)
         return model

@@ -6,6 +6,7 @@ stride, any row stride that is a multiple of 8 elements), so fused buffers such 
 [M, 6144] QKV projection are consumed in place without copies.
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -854,8 +855,9 @@ def lora_dy_grouped(y, us, w3s, r, alpha, dB_outs, x, dA_outs, accumulate=True, 
 
 
 def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=None, dA_out=None,
-            dA_accumulate=True, w_out=None, split_out=None):
-    """One pass over dY (ltx_lora_dy): returns (w, split) as lora_down(y, B, transposed=True,
+            dA_accumulate=True, w_out=None, split_out=None, dA_alpha=1.0):
+    """One pass over dY (ltx_lora_dy; dA_alpha = the alpha_a of ltx_lora_dy_dA, the dropout scale of a
+    dropped-out adapter whose x is the masked xd): returns (w, split) as lora_down(y, B, transposed=True,
     split=True) does, and adds alpha * y^T . u into dB_out ([N, r], or [r, N] with transpose_out)
     as lora_wgrad(y, u, alpha, out=dB_out, accumulate=accumulate) does. With x ([M, K] bf16,
     lora_dy_fits; any N % 512 == 0) and dA_out ([r, K] f32): also dA_out (+)= x^T . w as lora_wgrad(x, w,
@@ -879,7 +881,7 @@ def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=
         ws = torch.empty(n.value, dtype=F32, device=y.device)
         call("ltx_lora_dy_dA", _p(y), _rows(y, "y"), _p(u), _rows(u, "u"), _p(w3), _rows(w3, "w3"),
              _p(x), _rows(x, "x"), M, N, K, r, float(alpha), _p(w), _rows(w, "w"), _p(sp),
-             _rows(sp, "split"), K2, _p(dB_out), on, oj, 1 if accumulate else 0, 1.0, _p(dA_out), 1,
+             _rows(sp, "split"), K2, _p(dB_out), on, oj, 1 if accumulate else 0, float(dA_alpha), _p(dA_out), 1,
              K, 1 if dA_accumulate else 0, _p(ws), _s())
         return w, sp
     call("ltx_lora_dy_workspace", M, N, r, ctypes.byref(n))
@@ -888,6 +890,69 @@ def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=
          float(alpha), _p(w), _rows(w, "w"), _p(sp), _rows(sp, "split"), K2, _p(dB_out), on, oj,
          1 if accumulate else 0, _p(ws), _s())
     return w, sp
+
+
+@functools.lru_cache(maxsize=64)
+def lora_dropout_threshold(p):
+    """(T, c) of a LoRA dropout rate 0 < p < 1: an element is kept iff its 16-bit mask lane >= T,
+    T = round(p * 65536) clamped to [1, 65535]; kept elements are scaled by c = 1 / (1 - T / 65536),
+    the f32 value of the realised keep rate's inverse (the estimator stays unbiased)."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"LoRA dropout rate {p!r}: expected 0 < p < 1")
+    T = min(max(int(round(p * 65536.0)), 1), 65535)
+    c = float(torch.tensor(1.0, dtype=F32) / (torch.tensor(1.0, dtype=F32) - torch.tensor(T / 65536.0, dtype=F32)))
+    return T, c
+
+
+def lora_dropout_apply(x, key, sid, T, out=None):
+    """xd = keep ? x : 0 under the mask of stream sid and the 64-bit key (ltx_lora_dropout_apply; the
+    numpy statement of the mask is lora.lora_dropout_mask_reference). x bf16 [M, K], K % 8 == 0. Exact:
+    the scale c of ops.lora_dropout_threshold is the consumer's alpha."""
+    _need(x, BF16, "lora_dropout_apply x")
+    M, K = x.shape
+    out = torch.empty(M, K, dtype=BF16, device=x.device) if out is None else out
+    timer = _timer
+    label = "ltx::lora_dropout_apply_kernel"
+    timer = timer if (timer is not None and timer.wants(label)) else None
+    ev0 = timer.start() if timer is not None else None
+    call("ltx_lora_dropout_apply", _p(x), _rows(x, "x"), _p(out), _rows(out, "out"), M, K,
+         ctypes.c_uint64(int(key) & 0xFFFFFFFFFFFFFFFF), int(sid), int(T), _s())
+    if timer is not None:
+        timer.stop(label, 0.0, ev0, 4.0 * M * K)  # x read once, xd written once
+    return out
+
+
+def lora_up_masked_add(dx, w, As, sids, key, T, c, g=None):
+    """dx += g * c * sum_i keep_i * (w_i . A_i) in place (ltx_lora_up_masked_add): the masked
+    input-gradient term of len(As) (1..3) dropped-out adapters that share the output dx bf16 [M, K].
+    w f32 [M, G r] holds the adapters' w_i = s dY B_i side by side, As[i] = lora_A f32 [r, K], sids[i]
+    the adapter's mask stream; g = the int16 GELU-derivative store (ff.net.2's site) or None."""
+    _need(dx, BF16, "lora_up_masked_add dx")
+    _need(w, F32, "lora_up_masked_add w")
+    M, K = dx.shape
+    G = len(As)
+    r = As[0].shape[0]
+    if w.shape != (M, G * r) or len(sids) != G:
+        raise ValueError(f"lora_up_masked_add: w must be [M, G r] = {(M, G * r)}, got {tuple(w.shape)}")
+    for a in As:
+        _need(a, F32, "lora_up_masked_add A")
+        if tuple(a.shape) != (r, K) or a.stride(1) != 1 or a.stride(0) != As[0].stride(0):
+            raise ValueError("lora_up_masked_add: every A must be [r, K] f32 with one row stride")
+    if g is not None:
+        _need(g, torch.int16, "lora_up_masked_add g (int16 snorm of gelu_tanh' / 2)")
+    timer = _timer
+    label = f"ltx::lora_up_masked_add_kernel<{r}>"
+    timer = timer if (timer is not None and timer.wants(label)) else None
+    ev0 = timer.start() if timer is not None else None
+    call("ltx_lora_up_masked_add", _p(dx), _rows(dx, "dx"), _p(w), _rows(w, "w"), _ptr_array(As),
+         As[0].stride(0), (ctypes.c_int64 * G)(*[int(s) for s in sids]), G, M, K, r,
+         ctypes.c_uint64(int(key) & 0xFFFFFFFFFFFFFFFF), int(T), float(c), _p(g),
+         _rows(g, "g") if g is not None else 0, _s())
+    if timer is not None:  # dx read and written, w and A (and g) read once
+        nb = 4.0 * M * K + 4.0 * G * r * (M + K) + (2.0 * M * K if g is not None else 0.0)
+        timer.stop(label, 2.0 * M * K * G * r, ev0, nb)
+    return dx
 
 
 # ---------------------------------------------------------------------------------------------

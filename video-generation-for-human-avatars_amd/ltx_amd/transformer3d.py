@@ -93,16 +93,28 @@ class RMSNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(dim)) if elementwise_affine else None
 
 
-class LoraLinear(nn.Module):
-    """peft 0.17.1 lora.Linear naming: base_layer, lora_A/lora_B ModuleDicts keyed 'default';
-    f32 adapters on a bf16 base (autocast_adapter_dtype). The math is fused into the GEMMs."""
+def check_lora_dropout(p):
+    """A LoRA dropout rate as a float; ValueError outside [0, 1)."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"lora_dropout {p!r}: expected a rate in [0, 1)")
+    return float(p)
 
-    def __init__(self, base_layer: nn.Linear, r: int, lora_alpha: int):
+
+class LoraLinear(nn.Module):
+    """peft 0.17.1 lora.Linear naming: base_layer, lora_A/lora_B ModuleDicts keyed 'default', and
+    lora_dropout = {'default': nn.Dropout(p) | nn.Identity()} (no parameters: state dicts are those of
+    p = 0); f32 adapters on a bf16 base (autocast_adapter_dtype). The math is fused into the GEMMs;
+    the dropout module only names the rate, the mask is the block's own (DESIGN.md "LoRA dropout")."""
+
+    def __init__(self, base_layer: nn.Linear, r: int, lora_alpha: int, dropout: float = 0.0):
         super().__init__()
         self.base_layer = base_layer
         self.r = ops.check_lora_rank(r)
         self.lora_alpha = lora_alpha
         self.scaling = lora_alpha / r
+        self.lora_dropout_p = check_lora_dropout(dropout)
+        self.lora_dropout = nn.ModuleDict({"default": nn.Dropout(self.lora_dropout_p) if self.lora_dropout_p > 0.0
+                                           else nn.Identity()})
         dev = base_layer.weight.device
         self.lora_A = nn.ModuleDict({"default": nn.Linear(base_layer.in_features, r, bias=False,
                                                           device=dev, dtype=torch.float32)})
@@ -364,29 +376,68 @@ def _qkv_grouped():
     return os.environ.get("LTX_LORA_QKV_GROUPED", "1") != "0"
 
 
-def _qkv_lora_down(x1, lora1, ab1, r):
-    """u_g = x1 . A_g^T of the q / k / v adapters side by side: (u [M, 3r] f32, split [M, 3 K2] bf16)."""
+def _qkv_lora_down(x1, lora1, ab1, r, dp=None):
+    """u_g = x1 . A_g^T of the q / k / v adapters side by side: (u [M, 3r] f32, split [M, 3 K2] bf16).
+    Under LoRA dropout (dp) each adapter reads its own masked x1 (slots 0 - 2), scaled by c: the
+    one-adapter calls."""
     M, K = x1.shape
     K2 = ops.lora_k2(r)
-    if _qkv_grouped() and ops._LORA_ROWS and M >= 8192 and K % 256 == 0:  # lora_down's token-sized gate
+    if dp is None and _qkv_grouped() and ops._LORA_ROWS and M >= 8192 and K % 256 == 0:  # lora_down's token-sized gate
         return ops.lora_rows_grouped(x1, [m.weight_pieces("A") for m in lora1[:3]], r, split=True)
     u = torch.empty(M, 3 * r, dtype=torch.float32, device=x1.device)
     su = torch.empty(M, 3 * K2, dtype=torch.bfloat16, device=x1.device)
     for g in range(3):
-        ops.lora_down(x1, ab1[2 * g], split=True, out=u[:, g * r:(g + 1) * r],
+        ops.lora_down(x1 if dp is None else _drop_x(x1, dp, g), ab1[2 * g], alpha=1.0 if dp is None else dp[2],
+                      split=True, out=u[:, g * r:(g + 1) * r],
                       split_out=su[:, g * K2:(g + 1) * K2], pieces=lambda m=lora1[g]: m.weight_pieces("A"))
     return u, su
 
 
-def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da=True):
+# ---- LoRA dropout (peft lora_dropout; DESIGN.md "LoRA dropout") ----
+# dp = (key, T, c, sid0) of a block whose adapters drop out in this forward, else None: the model
+# forward's 64-bit key, the keep threshold and scale of the block's rate (ops.lora_dropout_threshold)
+# and the block's first mask stream 16 * block index; slot = the adapter's place in
+# lora.LORA_DROPOUT_SLOTS. The masked inputs xd are regenerated wherever they are needed (forward,
+# checkpoint recompute, backward), never kept.
+def _drop_x(x, dp, slot):
+    """xd = keep ? x : 0 of the block's adapter `slot` (the scale c is the consumer's alpha)."""
+    return ops.lora_dropout_apply(x, dp[0], dp[3] + slot, dp[1])
+
+
+def _masked_add(dx, w, As, dp, slots, g=None):
+    """dx += g * c * sum_i keep_i * (w_i . A_i): the adapters' input-gradient term, which under a
+    mask cannot ride the dgrad GEMM's K extension (ltx_lora_up_masked_add)."""
+    return ops.lora_up_masked_add(dx, w, As, [dp[3] + sl for sl in slots], dp[0], dp[1], dp[2], g=g)
+
+
+def _block_lora_linears(blk):
+    """The LoraLinear modules among the block's ten adapter slots (direct lookups, as _frozen)."""
+    a1, a2 = blk._modules["attn1"]._modules, blk._modules["attn2"]._modules
+    net = blk._modules["ff"]._modules["net"]._modules
+    ms = (a1["to_q"], a1["to_k"], a1["to_v"], a1["to_out"]._modules["0"], a2["to_q"], a2["to_k"], a2["to_v"],
+          a2["to_out"]._modules["0"], net["0"]._modules["proj"], net["2"])
+    return [m for m in ms if type(m) is LoraLinear]
+
+
+def _block_dropout(blk):
+    """The LoRA dropout rate of the block's adapters (0.0 without adapters); the adapters of one
+    block share one rate, like one rank per attention."""
+    ps = {getattr(m, "lora_dropout_p", 0.0) for m in _block_lora_linears(blk)}
+    if len(ps) > 1:
+        raise NotImplementedError(f"the adapters of one block must share one lora_dropout, got {sorted(ps)}")
+    return ps.pop() if ps else 0.0
+
+
+def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da=True, da_alpha=1.0):
     """One adapter's backward: dB and dA into .grad, returns (w = s dY B, its split operand). The
     one-pass forms where they apply (ops.lora_dy), else lora_wgrad + lora_down. merge_da=False keeps
-    dA a separate lora_wgrad call even where the merged ltx_lora_dy_dA applies (bitwise the same)."""
+    dA a separate lora_wgrad call even where the merged ltx_lora_dy_dA applies (bitwise the same).
+    da_alpha scales dA: the dropout scale c when x is a masked xd (dA = c w^T xd)."""
     dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dy, r)
     if dy_ok and merge_da and ops.lora_dy_da_fits(dy, x, r):
         # one pass over dY, one over x (dA), one finish for w / split, dB and dA
         return ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), x=x,
-                           dA_out=_grad_buf(lin, "A"), w_out=w_out, split_out=split_out)
+                           dA_out=_grad_buf(lin, "A"), w_out=w_out, split_out=split_out, dA_alpha=da_alpha)
     if dy_ok:  # one pass over dY
         w, sw = ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), w_out=w_out,
                             split_out=split_out)
@@ -394,7 +445,7 @@ def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da
         ops.lora_wgrad(dy, u, alpha=s, out=_grad_buf(lin, "B"), accumulate=True)
         w, sw = ops.lora_down(dy, Bw, alpha=s, transposed=True, split=True, out=w_out, split_out=split_out,
                               pieces=lambda: lin.weight_pieces("Bt"))
-    ops.lora_wgrad(x, w, transpose_out=True, out=_grad_buf(lin, "A"), accumulate=True)
+    ops.lora_wgrad(x, w, alpha=da_alpha, transpose_out=True, out=_grad_buf(lin, "A"), accumulate=True)
     return w, sw
 
 
@@ -479,6 +530,18 @@ class _Shared:
         # handed over in ffo_pre = (dh, d_ffo) (LTX_FFGATE_FUSED=0: separate gate_mul launches)
         self.ffgate = {}
         self.ffo_pre = None
+        # LoRA dropout: the forward's 64-bit mask key (None: no adapter drops out in this forward) and
+        # block id -> (T, c, first mask stream) of the blocks that do. The forward, a checkpoint
+        # recompute and the backward regenerate the same masks from them.
+        self.drop_key = None
+        self.drop = {}
+
+    def block_drop(self, blk):
+        """dp = (key, T, c, sid0) of a block under LoRA dropout, else None."""
+        if self.drop_key is None:
+            return None
+        d = self.drop.get(id(blk))
+        return None if d is None else (self.drop_key, *d)
 
 
 _LORA_KEYS = ("q", "k", "v", "o")
@@ -596,13 +659,18 @@ class _BlockFn(torch.autograd.Function):
         full = sh.full and keep
         if (has_lora or has1 or hasf) and full:  # before the block's first launch
             raise NotImplementedError("train_mode='full' trains the base weights without LoRA")
+        # LoRA dropout (training forwards of a model whose adapters have lora_dropout > 0): every
+        # adapter's lora_A reads its own masked input xd, scaled by c (the down-projection's alpha);
+        # the s u B^T term rides the GEMM K extension as without dropout
+        dp = sh.block_drop(blk) if keep else None
+        ca = 1.0 if dp is None else dp[2]
         # ---- 1. norm1 + AdaLN(msa) -> fused QKV -> q/k RMSNorm + RoPE -> SDPA -> gated residual
         x1, rstd1 = ops.rmsnorm_modulate_fwd(h, mods[:, 0], onep[:, 1], ldm, rpm, blk.norm_eps)
         if has1:
             # the q / k / v adapters ride the packed QKV GEMM: their u rows side by side as one
             # [M, 3 K2] operand, column group g of the output reading its own K2 columns
             r1 = lora1[0].r
-            u1, su1 = _qkv_lora_down(x1, lora1, ab1, r1)
+            u1, su1 = _qkv_lora_down(x1, lora1, ab1, r1, dp)
             ext_w, grouped, _ = _qkv_ext(blk, lora1[0], lora1[1], lora1[2])
             qkv = ops.gemm(x1, W["qkv_w"], bias=W["qkv_b"], ext=(su1, ext_w),
                            ext_group=(D, ops.lora_k2(r1)) if grouped else None)
@@ -628,7 +696,8 @@ class _BlockFn(torch.autograd.Function):
         y1 = torch.empty(M, D, dtype=torch.bfloat16, device=h.device) if full else None
         if has1:  # to_out.0's adapter sees the (blended) o1, as the reference's to_out does
             lo1 = lora1[3]
-            u_o1, su = ops.lora_down(o1, ab1[6], split=True, pieces=lambda: lo1.weight_pieces("A"))
+            u_o1, su = ops.lora_down(o1 if dp is None else _drop_x(o1, dp, 3), ab1[6], alpha=ca, split=True,
+                                     pieces=lambda: lo1.weight_pieces("A"))
             h1 = ops.gemm(o1, lo1.base_layer.weight, bias=lo1.base_layer.bias, epilogue="gated_residual",
                           aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm,
                           ext=(su, lo1.weight_split("B")))
@@ -643,7 +712,8 @@ class _BlockFn(torch.autograd.Function):
         if has_lora:
             # peft LoRA fused into the K loop: [x | split(x.A^T)] . [W | split(s*B)]^T
             Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo = lora_ab
-            u_q, su = ops.lora_down(h1, Aq, split=True, pieces=lambda: lora[0].weight_pieces("A"))
+            u_q, su = ops.lora_down(h1 if dp is None else _drop_x(h1, dp, 4), Aq, alpha=ca, split=True,
+                                    pieces=lambda: lora[0].weight_pieces("A"))
             q2raw = ops.gemm(h1, wq, bias=bq, ext=(su, lora[0].weight_split("B")))
             del su
         else:
@@ -653,14 +723,15 @@ class _BlockFn(torch.autograd.Function):
         if sh.text_stack is not None:  # computed for every block at once (_TextStack.forward)
             k2raw, k2, rk2, v2, u_k, u_v = sh.text_stack.block_kv(blk, sh)
         elif pre is None:
-            k2raw, k2, rk2, v2, u_k, u_v = _text_kv(blk, sh, enc2, lora_ab)
+            k2raw, k2, rk2, v2, u_k, u_v = _text_kv(blk, sh, enc2, lora_ab, dp)
         else:  # computed on the text side stream one block ahead (_forward_tokens)
             (k2raw, k2, rk2, v2, u_k, u_v), ev = pre
             torch.cuda.current_stream().wait_event(ev)
         o2, lse2 = ops.attn_fwd(q2, k2, v2, B, H, d, a2.scale, key_bias=sh.enc_bias,
                                 kv_shared=sh.text_shared)
         if has_lora:
-            u_o, su = ops.lora_down(o2, Ao, split=True, pieces=lambda: lora[3].weight_pieces("A"))
+            u_o, su = ops.lora_down(o2 if dp is None else _drop_x(o2, dp, 7), Ao, alpha=ca, split=True,
+                                    pieces=lambda: lora[3].weight_pieces("A"))
             h2 = ops.gemm(o2, wo, bias=bo, epilogue="accum", aux0=h1,
                           ext=(su, lora[3].weight_split("B")))
             del su
@@ -678,12 +749,14 @@ class _BlockFn(torch.autograd.Function):
             # the GELU epilogue (fpre is then the derivative at the adapted pre-activation), u2 =
             # act . A2^T (K = 8192) with s B2 under the gated residual
             lf1, lf2 = loraf
-            u_f1, su = ops.lora_down(x2, abf[0], split=True, pieces=lambda: lf1.weight_pieces("A"))
+            u_f1, su = ops.lora_down(x2 if dp is None else _drop_x(x2, dp, 8), abf[0], alpha=ca, split=True,
+                                     pieces=lambda: lf1.weight_pieces("A"))
             act = ops.gemm(x2, lf1.base_layer.weight, bias=lf1.base_layer.bias, epilogue="gelu", aux0=fpre,
                            ext=(su, lf1.weight_split("B")))
             if not (keep and _ff_keep_x2()):
                 del x2
-            u_f2, su = ops.lora_down(act, abf[2], split=True, pieces=lambda: lf2.weight_pieces("A"))
+            u_f2, su = ops.lora_down(act if dp is None else _drop_x(act, dp, 9), abf[2], alpha=ca, split=True,
+                                     pieces=lambda: lf2.weight_pieces("A"))
             h3 = ops.gemm(act, lf2.base_layer.weight, bias=lf2.base_layer.bias, epilogue="gated_residual",
                           aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm,
                           ext=(su, lf2.weight_split("B")))
@@ -711,6 +784,7 @@ class _BlockFn(torch.autograd.Function):
                                   *lora_ab, *lora_saved, *full_saved, *lora1_saved, *loraf_saved)
             ctx.blk, ctx.sh, ctx.has_lora, ctx.full, ctx.has1 = blk, sh, has_lora, full, has1
             ctx.hasf = hasf
+            ctx.dp = dp
         return h3
 
     @staticmethod
@@ -764,7 +838,31 @@ class _BlockFn(torch.autograd.Function):
         if full:  # gate_mlp: sum over the batch's rows of bf16(dh3 * y3) (attention.py:305-308)
             ops.colsum_into(dmods[:, 5], dh3, y3, mode=1, rows_per_group=rpm, sum_groups=False,
                             accumulate=False)
-        if hasf:
+        # LoRA dropout: dB and w as without it, dA = c w^T xd on the regenerated xd, and every dgrad
+        # GEMM of a dropped-out adapter runs WITHOUT its K extension (the plain classes of the
+        # no-adapter path); the masked term c keep (w . A) is added afterwards (_masked_add)
+        dp = ctx.dp
+        ca = 1.0 if dp is None else dp[2]
+        if hasf and dp is not None:
+            # ff.net.2: the GELU-backward GEMM without the extension, then the masked term times the
+            # kept derivative; ff.net.0.proj: a plain add into dx2
+            xd = _drop_x(act, dp, 9)
+            w2, _ = _lora_backward(d_ffo, u_f2, lf2, abf[3], xd, rf, sf, merge_da=_ff_merge_da(), da_alpha=ca)
+            del xd
+            d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre)
+            _masked_add(d_f, w2, [abf[2]], dp, (9,), g=fpre)
+            del d_ffo, act, w2
+            if x2 is None:  # bitwise the forward's x2
+                x2, _ = ops.rmsnorm_modulate_fwd(h2, mods[:, 3], onep[:, 4], ldm, rpm, blk.norm_eps)
+            xd = _drop_x(x2, dp, 8)
+            del x2
+            w1, _ = _lora_backward(d_f, u_f1, lf1, abf[1], xd, rf, sf, merge_da=_ff_merge_da(), da_alpha=ca)
+            del xd
+            dx2 = ops.gemm(d_f, W["ff1_wT"])
+            _masked_add(dx2, w1, [abf[0]], dp, (8,))
+            del d_f, w1
+            grads_lora = [None] * 4
+        elif hasf:
             # ff.net.2's adapter: dY = d_ffo, x = act (K = 8192); w2 = s d_ffo B2 rides the GELU-backward
             # GEMM's K extension with A2's split. ff.net.0.proj's: dY = d_f [M, 4D], x = x2; w1 rides dx2's
             _, sw = _lora_backward(d_ffo, u_f2, lf2, abf[3], act, rf, sf, merge_da=_ff_merge_da())
@@ -790,10 +888,21 @@ class _BlockFn(torch.autograd.Function):
         del dx2
         # ---- attn2: h2 = h1 + to_out(o2)   (LoRA grads: peft f32 adapters)
         # dO of the cross-attention + its delta rowsum(dO*O) in the GEMM epilogue
-        delta2 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if _DELTA_FUSED else None
+        # (under LoRA dropout dO is complete only after the masked add: delta then comes from the
+        # attention backward's own row-sum pass, as with LTX_DELTA_FUSED=0)
+        fused2 = _DELTA_FUSED and not (has_lora and dp is not None)
+        delta2 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if fused2 else None
         rd = dict(epilogue="store_rowdot", aux0=o2, aux1=delta2, rank=d, rows_per_batch=N) \
-            if _DELTA_FUSED else {}
-        if has_lora:
+            if fused2 else {}
+        if has_lora and dp is not None:
+            lq, lk, lv, lo = lora
+            xd = _drop_x(o2, dp, 7)
+            w_o, _ = _lora_backward(dh2, u_o, lo, Bo, xd, r, s, da_alpha=ca)
+            del xd
+            do2 = ops.gemm(dh2, W["o2_wT"])
+            _masked_add(do2, w_o, [Ao], dp, (7,))
+            del w_o
+        elif has_lora:
             lq, lk, lv, lo = lora
             dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dh2, r)
             if dy_ok and ops.lora_dy_da_fits(dh2, o2, r):
@@ -879,7 +988,31 @@ class _BlockFn(torch.autograd.Function):
         # dh1 = dh2 + dq2raw . W_q2 (+ LoRA) and, from the same epilogue, d_y1 = bf16(dh1 * g_msa)
         d_y1 = torch.empty_like(dh2)
         gated = dict(aux1=mods[:, 2], aux2=d_y1, rows_per_batch=rpm)
-        if has_lora:
+        if has_lora and dp is not None:
+            # to_q into the residual-stream gradient, to_k / to_v into the encoder gradient: the masked
+            # terms are added after the accumulation, and d_y1 = bf16(dh1 * g_msa) is taken from the
+            # completed dh1
+            xd = _drop_x(h1, dp, 4)
+            w_q, _ = _lora_backward(dq2raw, u_q, lq, Bq, xd, r, s, da_alpha=ca)
+            del xd
+            dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2)
+            _masked_add(dh1, w_q, [Aq], dp, (4,))
+            del w_q
+            d_y1 = ops.gate_mul(dh1, mods[:, 2], rpm)
+            # (the per-sample text path: under dropout there is no shared prompt and no text stack)
+            w_kv = torch.empty(dkv.shape[0], 2 * r, dtype=torch.float32, device=h.device)
+            for i, (dy, u_t, lt, Bt_) in enumerate(((dk2raw, u_k, lk, Bk), (dv2, u_v, lv, Bv))):
+                ops.lora_wgrad(dy, u_t, alpha=s, out=_grad_buf(lt, "B"), accumulate=True)
+                ops.lora_down(dy, Bt_, alpha=s, transposed=True, out=w_kv[:, i * r:(i + 1) * r])
+                xd = _drop_x(enc2, dp, 5 + i)
+                ops.lora_wgrad(xd, w_kv[:, i * r:(i + 1) * r], alpha=ca, transpose_out=True,
+                               out=_grad_buf(lt, "A"), accumulate=True)
+                del xd
+            denc = ops.gemm(dkv, W["kv2_wT"])
+            _masked_add(denc, w_kv, [Ak, Av], dp, (5, 6))
+            del w_kv
+            grads_lora = grads_lora + [None] * 8
+        elif has_lora:
             dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dq2raw, r)
             if dy_ok and ops.lora_dy_da_fits(dq2raw, h1, r):
                 w_q, sw = ops.lora_dy(dq2raw, u_q, lq.weight_pieces("Bt"), r, s, _grad_buf(lq, "B"),
@@ -920,10 +1053,20 @@ class _BlockFn(torch.autograd.Function):
         del dq2raw, dk2raw, dv2, dh2, dkv
         # ---- attn1: h1 = h + g_msa * to_out(sdpa(rope(qn(q)), rope(kn(k)), v))
         # (d_y1 = bf16(dh1 * g_msa) came out of the dh1 GEMM's epilogue: `gated` above)
-        delta1 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if _DELTA_FUSED else None
+        fused1 = _DELTA_FUSED and not (has1 and dp is not None)  # as fused2 above
+        delta1 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if fused1 else None
         rd = dict(epilogue="store_rowdot", aux0=o1, aux1=delta1, rank=d, rows_per_batch=N) \
-            if _DELTA_FUSED else {}
-        if has1:
+            if fused1 else {}
+        if has1 and dp is not None:
+            lo1 = lora1[3]
+            xd = _drop_x(o1, dp, 3)
+            w_o1, _ = _lora_backward(d_y1, u_o1, lo1, ab1[7], xd, r1, s1, da_alpha=ca)
+            del xd
+            do1 = ops.gemm(d_y1, W["out1_wT"])
+            _masked_add(do1, w_o1, [ab1[6]], dp, (3,))
+            del w_o1
+            grads_lora = grads_lora + [None] * 8
+        elif has1:
             # to_out.0's adapter: dB_o, dA_o (x = o1) into .grad; w_o = s d_y1 B_o rides the dgrad's
             # K extension with A_o's split
             lo1 = lora1[3]
@@ -960,10 +1103,22 @@ class _BlockFn(torch.autograd.Function):
             del dwqkv
         del dq1, dk1
         dh = None
-        if has1:  # dB / dA of the q / k / v adapters (one pass over dqkv, one over x1) and w's split
+        if has1 and dp is not None:
+            # q / k / v have three different xd: the one-adapter calls for dB / dA, their w side by side
+            # for the G = 3 masked add into dx1
+            w1 = torch.empty(M, 3 * r1, dtype=torch.float32, device=h.device)
+            for g in range(3):
+                xd = _drop_x(x1, dp, g)
+                _lora_backward(dqkv[:, g * D:(g + 1) * D], u1[:, g * r1:(g + 1) * r1], lora1[g], ab1[2 * g + 1],
+                               xd, r1, s1, w_out=w1[:, g * r1:(g + 1) * r1], da_alpha=ca)
+                del xd
+        elif has1:  # dB / dA of the q / k / v adapters (one pass over dqkv, one over x1) and w's split
             sw1 = _qkv_lora_backward(dqkv, u1, lora1, ab1, x1, r1, s1)
         if ctx.needs_input_grad[4] or full:  # (blk, sh, keep, skip, h, ...)
-            if has1:  # + sum_g w_g . A_g: a plain K extension of 3 K2
+            if has1 and dp is not None:
+                dx1 = ops.gemm(dqkv, W["qkv_wT"])
+                _masked_add(dx1, w1, [ab1[0], ab1[2], ab1[4]], dp, (0, 1, 2))
+            elif has1:  # + sum_g w_g . A_g: a plain K extension of 3 K2
                 dx1 = ops.gemm(dqkv, W["qkv_wT"], ext=(sw1, _qkv_ext(blk, lora1[0], lora1[1], lora1[2])[2]))
             else:
                 dx1 = ops.gemm(dqkv, W["qkv_wT"])
@@ -1045,10 +1200,11 @@ def _lora_abf(blk):
     return ab
 
 
-def _text_kv(blk, sh, enc2, lora_ab):
+def _text_kv(blk, sh, enc2, lora_ab, dp=None):
     """attn2 K / V of the text tokens (attention.py:1004-1014 with the peft adapters of
     training.py:50-68, then the k RMSNorm): they depend only on enc2 and the block's weights, so
-    _forward_tokens can compute them on a side stream one block ahead."""
+    _forward_tokens can compute them on a side stream one block ahead. Under LoRA dropout (dp) the
+    to_k / to_v adapters read their own masked per-sample text rows (slots 5 and 6)."""
     a2 = blk.attn2
     W = blk.packed()
     D = sh.D
@@ -1057,8 +1213,11 @@ def _text_kv(blk, sh, enc2, lora_ab):
         _, _, Ak, _, Av, _, _, _ = lora_ab
         K2 = ops.lora_k2(lora[1].r)
         su = torch.empty(enc2.shape[0], 2 * K2, dtype=torch.bfloat16, device=enc2.device)
-        u_k, _ = ops.lora_down(enc2, Ak, split=True, split_out=su[:, :K2])
-        u_v, _ = ops.lora_down(enc2, Av, split=True, split_out=su[:, K2:])
+        ca = 1.0 if dp is None else dp[2]
+        u_k, _ = ops.lora_down(enc2 if dp is None else _drop_x(enc2, dp, 5), Ak, alpha=ca, split=True,
+                               split_out=su[:, :K2])
+        u_v, _ = ops.lora_down(enc2 if dp is None else _drop_x(enc2, dp, 6), Av, alpha=ca, split=True,
+                               split_out=su[:, K2:])
         kv = ops.gemm(enc2, W["kv2_w"], bias=W["kv2_b"], ext=(su, _kv_ext(blk, lora[1], lora[2])[0]))
     else:
         u_k = u_v = None
@@ -1412,6 +1571,10 @@ class Transformer3DModel(nn.Module):
         if caption_channels is not None:
             self.caption_projection = PixArtAlphaTextProjection(caption_channels, inner_dim)
         self.gradient_checkpointing = False
+        # LoRA dropout: an int here fixes the mask key of every training forward (else one is drawn per
+        # forward); last_lora_dropout_key = the key the last such forward used
+        self.lora_dropout_key = None
+        self.last_lora_dropout_key = None
 
     # ---- construction ----------------------------------------------------------------------
     @classmethod
@@ -1520,6 +1683,26 @@ class Transformer3DModel(nn.Module):
                   "text_ids": text_ids, "r": r, "s": sc, "D": blocks[0].attn2.inner_dim}
         self._tx_struct = (key, st)
         return st
+
+    def _lora_dropout_plan(self):
+        """(key, {block id: (T, c, first mask stream)}) of a training forward with LoRA dropout, or
+        None when no adapter has lora_dropout > 0 (then nothing is drawn and every launch is the
+        no-dropout one). The key: model.lora_dropout_key when it is an int (reproducible runs), else 64
+        bits from torch's default CPU generator; kept in model.last_lora_dropout_key."""
+        plan = {}
+        for i, blk in enumerate(self.transformer_blocks):
+            p = _block_dropout(blk)
+            if p > 0.0:
+                plan[id(blk)] = (*ops.lora_dropout_threshold(p), 16 * i)
+        if not plan:
+            return None
+        key = getattr(self, "lora_dropout_key", None)
+        if isinstance(key, bool) or not isinstance(key, int):
+            hi, lo = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
+            key = (hi << 32) | lo
+        key &= 0xFFFFFFFFFFFFFFFF
+        self.last_lora_dropout_key = key
+        return key, plan
 
     def _text_batchable(self):
         """The batched text side (_TextStack) applies with LoRA on every block's attn2 and frozen
@@ -1650,7 +1833,14 @@ class Transformer3DModel(nn.Module):
         # one prompt expanded over the batch (stride-0 views, as train_step passes it): run the
         # text side once; the cross-attention reads the shared K/V for every sample
         m = encoder_attention_mask
-        text_shared = (B > 1 and encoder_hidden_states.stride(0) == 0
+        # LoRA dropout: with any adapter at p > 0, in training mode with grad enabled, this forward
+        # draws one 64-bit mask key (model.lora_dropout_key when it is an int, else torch's default CPU
+        # generator: no device sync, and no draw without dropout); model.last_lora_dropout_key holds it
+        drop = self._lora_dropout_plan() if (self.training and torch.is_grad_enabled()) else None
+        # peft masks the expanded [B L, D] prompt per sample, so K / V differ per sample: under dropout
+        # neither the shared-prompt shortcut nor the batched _TextStack, but the per-block, per-sample
+        # text path of un-shared prompts
+        text_shared = (B > 1 and encoder_hidden_states.stride(0) == 0 and drop is None
                        and (m is None or m.shape[0] == 1 or m.stride(0) == 0))
         if text_shared:
             encoder_hidden_states = encoder_hidden_states[:1]
@@ -1698,11 +1888,13 @@ class Transformer3DModel(nn.Module):
         sh = _Shared(B, N, L, H, self.attention_head_dim, rope, enc_bias, eps, text_shared,
                      per_token)
         sh.full = full
+        if drop is not None:
+            sh.drop_key, sh.drop = drop
         ckpt = self.training and self.gradient_checkpointing and keep
         # the stack's backward (adapter grads of every to_k / to_v) runs as the backward of enc2,
         # so it needs enc2 in the graph: with a frozen caption_projection the per-block text path
         # computes those adapter grads instead
-        if keep and not full and enc2.requires_grad and self._text_batchable():
+        if keep and not full and enc2.requires_grad and drop is None and self._text_batchable():
             sh.text_stack = _TextStack(self, enc2)
             enc2 = _TextStackFn.apply(enc2, sh.text_stack)
         strat = None
