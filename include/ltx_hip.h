@@ -404,6 +404,32 @@ int ltx_lora_up_masked_add(void* dx, int64_t lddx, const float* w, int64_t ldw, 
                            int64_t r, uint64_t key, int64_t T, float c, const void* gq, int64_t ldg,
                            void* stream);
 
+/* ---- DoRA (peft use_dora; DESIGN.md "DoRA (use_dora)"; csrc/dora.hip) --------------------------
+ * y = c (.) (x W^T + s (x A^T) B^T) + b with c_j = m_j / ||W[j,:] + s (B A)[j,:]||_2 (the norm takes
+ * no gradient). The column scale is folded into the operands of the unchanged GEMMs. */
+/* Per output row j of W bf16 [N,K] (ldw), A f32 [r,K] (lda, unit column stride), B f32 [N,r] (element
+ * (j,i) at B[j*brs + i*bcs]) and m f32 [N]: norm[j] = ||V[j,:]||_2 of V = f32(W) + (s B) A (f32, the
+ * rank sum an fma chain in rank order; V is not stored), c[j] = m[j] / norm[j] (0 where norm[j] == 0),
+ * w_eff[j,:] = bf16(c[j] * f32(W[j,:])) (bf16 [N,K], ldo; one rounding) and sb_eff[j,:] = c[j] * (s *
+ * B[j,:]) (dense f32 [N,r]: the src of ltx_lora_split_bf16 / ltx_lora_pieces with scale 1). K % 8 == 0,
+ * any N, r in {8, 16, 32, 64, 128}. Deterministic, no atomics. */
+int ltx_dora_fold(const void* W, int64_t ldw, const float* A, int64_t lda, const float* B, int64_t brs,
+                  int64_t bcs, const float* m, float s, int64_t N, int64_t K, int64_t r, float* norm,
+                  float* c, void* w_eff, int64_t ldo, float* sb_eff, void* stream);
+/* The magnitude gradient: out[n] (+)= m[n] != 0 ? (1 / m[n]) * sum_rows f32(dY[row,n]) * (f32(Y[row,n])
+ * - f32(bias[n])) : 0. dY, Y bf16 [M,N] with their own leading dimensions (column blocks of packed
+ * buffers), bias bf16 [N] or null, m and out f32 [N]. Any M, N % 8 == 0. Products and sums in f32, in
+ * two fixed-order levels: row-split partials in the caller's workspace (ltx_dora_mag_grad_workspace
+ * floats), then the splits in order. One pass over dY and Y (4 M N bytes). */
+int ltx_dora_mag_grad(const void* dY, int64_t lddy, const void* Y, int64_t ldy, const void* bias,
+                      const float* m, int64_t M, int64_t N, float* out, int accumulate,
+                      float* workspace, void* stream);
+int ltx_dora_mag_grad_workspace(int64_t M, int64_t N, int64_t* splits, int64_t* floats);
+/* out[j*on + i*oj] += (alpha * c[j]) * src[j*r + i] for src dense f32 [N,r]: the c_j row scale of a
+ * lora_B gradient that the plain dB kernels wrote (unscaled, accumulate = 0) into a scratch. */
+int ltx_dora_rowscale_add(const float* src, const float* c, float alpha, int64_t N, int64_t r,
+                          float* out, int64_t on, int64_t oj, void* stream);
+
 /* ---- small ops -------------------------------------------------------------------------------- */
 /* AdaLayerNormSingle sinusoid: out[b,:] = bf16([cos(s*t*f), sin(s*t*f)]) (256 ch), s = scale */
 int ltx_timestep_embedding(const float* t, float scale, void* out, int64_t B, int64_t dim,

@@ -90,6 +90,10 @@ _SIGNATURES = {
     "ltx_lora_dropout_apply": [_p, _i64, _p, _i64, _i64, _i64, ctypes.c_uint64, _i64, _i64, _p],
     "ltx_lora_up_masked_add": [_p, _i64, _p, _i64, ctypes.POINTER(_p), _i64, ctypes.POINTER(_i64), _i64, _i64,
                                _i64, _i64, ctypes.c_uint64, _i64, _f32, _p, _i64, _p],
+    "ltx_dora_fold": [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _f32, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p],
+    "ltx_dora_mag_grad": [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _i32, _p, _p],
+    "ltx_dora_mag_grad_workspace": [_i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "ltx_dora_rowscale_add": [_p, _p, _f32, _i64, _i64, _p, _i64, _i64, _p],
     "ltx_lora_split_bf16": [_p, _i64, _i64, _f32, _i64, _i64, _i32, _p, _i64, _i64, _p],
     "ltx_lora_down": [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _f32, _p, _i64, _i64,
                       _p],

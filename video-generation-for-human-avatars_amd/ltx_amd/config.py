@@ -125,4 +125,8 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     # every adapter of the model
     if "lora_dropout" in t:
         setattr(config, "lora_dropout", float(t["lora_dropout"]))
+    # and `train.use_dora` (a bool, absent = False): peft's use_dora, weight-decomposed LoRA on the
+    # attn2 projections
+    if "use_dora" in t:
+        setattr(config, "use_dora", bool(t["use_dora"]))
     return config

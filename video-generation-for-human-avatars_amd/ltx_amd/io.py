@@ -186,8 +186,13 @@ def merged_state_dict_cpu(model):
             a = mod.lora_A["default"].weight.detach().cpu()
             b = mod.lora_B["default"].weight.detach().cpu()
             delta = (b @ a) * mod.scaling
-            merged = w.clone()
-            merged += delta
+            if mod.use_dora:  # LoraLinear.merged_weight's statement on the CPU copies
+                v = w.float() + mod.scaling * (b @ a)
+                m = mod.lora_magnitude_vector["default"].weight.detach().cpu()
+                merged = ((m / torch.linalg.norm(v, dim=1)).view(-1, 1) * v).to(w.dtype)
+            else:
+                merged = w.clone()
+                merged += delta
             out[name + ".weight"] = merged
             if mod.base_layer.bias is not None:
                 out[name + ".bias"] = mod.base_layer.bias.detach().cpu().clone()

@@ -8,6 +8,9 @@ or instead wraps the same four projections of the self-attention attn1. `config.
 absent = False) also wraps both feed-forward linears of every block, ff.net.0.proj and ff.net.2.
 `config.lora_dropout` (a float in [0, 1), absent = 0.0) is peft's lora_dropout on every adapter; the
 keep mask is this build's own counter-based stream (lora_dropout_mask_reference states it in numpy).
+`config.use_dora` (a bool, absent = False) is peft's use_dora, weight-decomposed LoRA: every wrapped
+linear also holds the f32 magnitude `lora_magnitude_vector.default.weight` (DESIGN.md "DoRA (use_dora)").
+It is built for the reference's own targets, the four attn2 projections, without dropout.
 'full': the reference's substring rule (training.py:75-91); the fused block backward raises for
 it until the wgrad path (next row) lands.
 """
@@ -152,21 +155,41 @@ def _check_dropout(model, targets, dropout):
     return p
 
 
-def inject_lora(model, targets, r, alpha, *, feed_forward=False, dropout=0.0):
+def _check_dora(model, targets, dora, dropout):
+    """Before any module is replaced (NotImplementedError): DoRA adapters go on attn2 only and take no
+    dropout, and no block ends up with DoRA and plain adapters side by side."""
+    if dora and dropout > 0.0:
+        raise NotImplementedError("use_dora with lora_dropout > 0 is not supported")
+    if dora and any(name.split(".", 3)[2] != "attn2" for name in targets):
+        raise NotImplementedError("use_dora is supported on the attn2 projections only (lora_targets 'attn2', "
+                                  "no lora_ff)")
+    for i in sorted({int(name.split(".")[1]) for name in targets}):
+        blk = model.transformer_blocks[i]
+        have = {m.use_dora for m in blk.modules() if isinstance(m, LoraLinear)}
+        new = any(not isinstance(model.get_submodule(name), LoraLinear) for name in targets
+                  if name.startswith(f"transformer_blocks.{i}."))
+        if new and have - {bool(dora)}:
+            raise NotImplementedError(f"transformer_blocks.{i} already has {'plain' if dora else 'DoRA'} adapters: "
+                                      f"DoRA and plain LoRA adapters cannot be mixed within one block")
+
+
+def inject_lora(model, targets, r, alpha, *, feed_forward=False, dropout=0.0, dora=False):
     """Wrap the named linears in LoraLinear. feed_forward=True also accepts the names of
     lora_ff_target_modules; without it they are refused like any name outside the attentions.
-    dropout = peft's lora_dropout, one rate for every adapter created here."""
+    dropout = peft's lora_dropout, one rate for every adapter created here. dora=True = peft's
+    use_dora: the adapters created here are DoRA adapters (attn2 only, no dropout)."""
     ops.check_lora_rank(r)  # before the first module is replaced
     targets = list(targets)
     _check_targets(model, targets, feed_forward)
     dropout = _check_dropout(model, targets, dropout)
+    _check_dora(model, targets, dora, dropout)
     for name in targets:
         parent_name, _, child = name.rpartition(".")
         parent = model.get_submodule(parent_name)
         base = getattr(parent, child) if not child.isdigit() else parent[int(child)]
         if isinstance(base, LoraLinear):
             continue
-        wrapped = LoraLinear(base, r, alpha, dropout)
+        wrapped = LoraLinear(base, r, alpha, dropout, use_dora=bool(dora))
         if child.isdigit():
             parent[int(child)] = wrapped
         else:
@@ -193,6 +216,9 @@ def apply_training_strategy(model, config, train_mode: str):
         p = float(getattr(config, "lora_dropout", 0.0))
         if p != 0.0:
             extra["dropout"] = p
+        # config.use_dora (setattr or train.use_dora in the YAML; absent = False): peft's use_dora
+        if bool(getattr(config, "use_dora", False)):
+            extra["dora"] = True
         inject_lora(model, targets, config.lora_rank, config.lora_alpha, **extra)
         for n, p in model.named_parameters():
             p.requires_grad = ("lora_" in n) or ("caption_projection" in n)
@@ -209,8 +235,9 @@ def trainable_parameters(model):
 
 @torch.no_grad()
 def merged_state_dict(model):
-    """peft merge_and_unload(): W + s*B@A folded into each wrapped base weight, adapter keys
-    dropped (what save_training_checkpoint exports, torch_utils.py:66-102)."""
+    """peft merge_and_unload(): W + s*B@A (under DoRA (m / norm)[:, None] times it) folded into each
+    wrapped base weight, adapter and magnitude keys dropped (what save_training_checkpoint exports,
+    torch_utils.py:66-102)."""
     out = {}
     skip = set()
     for name, mod in model.named_modules():
@@ -246,4 +273,5 @@ def unload_lora(model):
     # QKV, W^T copies) so the next forward packs the merged weights
     for blk in getattr(model, "transformer_blocks", ()):
         blk._pack = blk._pack_key = None
+        blk._dora_pack = None
     return model

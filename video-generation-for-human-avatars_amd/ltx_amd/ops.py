@@ -955,6 +955,84 @@ def lora_up_masked_add(dx, w, As, sids, key, T, c, g=None):
     return dx
 
 
+def _timed(label):
+    """(timer, ev0) of a launch that bench.py's LaunchTimer times under `label`, else (None, None)."""
+    timer = _timer
+    if timer is None or not timer.wants(label):
+        return None, None
+    return timer, timer.start()
+
+
+def dora_fold(W, A, B, m, s, transposed=True):
+    """DoRA's per-weight-version operands (ltx_dora_fold; DESIGN.md "DoRA (use_dora)"): for W bf16
+    [N, K], A f32 [r, K], B f32 [N, r], m f32 [N] returns (norm f32 [N] = the row norms of W + s B A,
+    c = m / norm (0 where the norm is 0), W_eff = bf16(c W) [N, K], W_eff^T [K, N] (ltx_transpose_bf16;
+    None with transposed=False), sB_eff = c (.) s B f32 [N, r])."""
+    _need(W, BF16, "dora_fold W")
+    for t, name in ((A, "A"), (B, "B"), (m, "m")):
+        _need(t, F32, "dora_fold " + name)
+    N, K = W.shape
+    r = check_lora_rank(A.shape[0])
+    if tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r) or tuple(m.shape) != (N,) or A.stride(1) != 1 \
+            or not m.is_contiguous():
+        raise ValueError(f"dora_fold: expected A [r, K], B [N, r], m [N] for W {tuple(W.shape)}, got "
+                         f"{tuple(A.shape)}, {tuple(B.shape)}, {tuple(m.shape)}")
+    dev = W.device
+    norm = torch.empty(N, dtype=F32, device=dev)
+    c = torch.empty(N, dtype=F32, device=dev)
+    w_eff = torch.empty(N, K, dtype=BF16, device=dev)
+    sb = torch.empty(N, r, dtype=F32, device=dev)
+    label = f"ltx::dora_fold_kernel<{r}>"
+    timer, ev0 = _timed(label)
+    call("ltx_dora_fold", _p(W), _rows(W, "W"), _p(A), A.stride(0), _p(B), B.stride(0), B.stride(1), _p(m),
+         float(s), N, K, r, _p(norm), _p(c), _p(w_eff), K, _p(sb), _s())
+    if timer is not None:  # W read twice (the second time from L2) and written once, A, B read once
+        timer.stop(label, 2.0 * N * K * r, ev0, 4.0 * N * K + 4.0 * r * (N + K) + 8.0 * N * r + 12.0 * N)
+    return norm, c, w_eff, (transpose(w_eff) if transposed else None), sb
+
+
+def dora_mag_grad(dy, y, bias, m, out, accumulate=True):
+    """out[n] (+)= m[n] != 0 ? (1 / m[n]) sum_rows dy[row, n] (y[row, n] - bias[n]) : 0, the DoRA
+    magnitude gradient (ltx_dora_mag_grad): dy, y bf16 [M, N] row views (column blocks of wider buffers
+    are fine), bias bf16 [N] or None, m and out f32 [N]."""
+    _need(dy, BF16, "dora_mag_grad dy")
+    _need(y, BF16, "dora_mag_grad y")
+    _need(m, F32, "dora_mag_grad m")
+    _need(out, F32, "dora_mag_grad out")
+    M, N = dy.shape
+    if tuple(y.shape) != (M, N) or tuple(m.shape) != (N,) or tuple(out.shape) != (N,) or not out.is_contiguous() \
+            or not m.is_contiguous() or (bias is not None and (bias.dtype != BF16 or tuple(bias.shape) != (N,)
+                                                                or not bias.is_contiguous())):
+        raise ValueError(f"dora_mag_grad: dy / y [M, N], bias / m / out [N] expected, got {tuple(dy.shape)}, "
+                         f"{tuple(y.shape)}, {tuple(m.shape)}, {tuple(out.shape)}")
+    S, n = ctypes.c_int64(0), ctypes.c_int64(0)
+    call("ltx_dora_mag_grad_workspace", M, N, ctypes.byref(S), ctypes.byref(n))
+    ws = torch.empty(n.value, dtype=F32, device=dy.device)
+    label = "ltx::dora_mag_grad_kernel"
+    timer, ev0 = _timed(label)
+    call("ltx_dora_mag_grad", _p(dy), _rows(dy, "dy"), _p(y), _rows(y, "y"), _p(bias), _p(m), M, N, _p(out),
+         1 if accumulate else 0, _p(ws), _s())
+    if timer is not None:
+        timer.stop(label, 2.0 * M * N, ev0, 4.0 * M * N)
+    return out
+
+
+def dora_rowscale_add(out, src, c, alpha=1.0, transpose_out=False):
+    """out[j, :] += alpha * c[j] * src[j, :] (ltx_dora_rowscale_add): src dense f32 [N, r], out the dense
+    f32 [N, r] gradient buffer (or [r, N] with transpose_out)."""
+    N, r = src.shape
+    shape = (r, N) if transpose_out else (N, r)
+    assert src.dtype == F32 and src.is_contiguous() and c.dtype == F32 and tuple(c.shape) == (N,) and c.is_contiguous()
+    assert tuple(out.shape) == shape and out.dtype == F32 and out.is_contiguous()
+    on, oj = (1, N) if transpose_out else (r, 1)
+    label = "ltx::dora_rowscale_add_kernel"
+    timer, ev0 = _timed(label)
+    call("ltx_dora_rowscale_add", _p(src), _p(c), float(alpha), N, r, _p(out), on, oj, _s())
+    if timer is not None:
+        timer.stop(label, 2.0 * N * r, ev0, 12.0 * N * r)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # small ops
 # ---------------------------------------------------------------------------------------------

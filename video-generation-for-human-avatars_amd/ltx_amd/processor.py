@@ -36,6 +36,10 @@ def _linear_parts(m):
         drop = getattr(m, "lora_dropout", None)
         if drop is not None and "default" in drop and getattr(drop["default"], "p", 0.0) > 0 and m.training:
             raise NotImplementedError("HipAttnProcessor: LoRA dropout > 0 is not supported")
+        mag = getattr(m, "lora_magnitude_vector", None)
+        if mag is not None and len(mag) > 0:
+            raise NotImplementedError("HipAttnProcessor: DoRA adapters (use_dora) are not supported; the fused "
+                                      "block runs them (Transformer3DModel.forward)")
         sc = m.scaling["default"] if isinstance(m.scaling, dict) else m.scaling
         ops.check_lora_rank(int(m.lora_A["default"].weight.shape[0]))
         return base.weight, base.bias, m.lora_A["default"].weight, m.lora_B["default"].weight, float(sc)

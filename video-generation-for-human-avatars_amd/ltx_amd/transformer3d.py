@@ -100,13 +100,31 @@ def check_lora_dropout(p):
     return float(p)
 
 
+class DoraMagnitude(nn.Module):
+    """peft's DoraLinearLayer as a parameter holder: `weight` f32 [out_features], the magnitude m of
+    <target>.lora_magnitude_vector.default.weight."""
+
+    def __init__(self, weight):
+        super().__init__()
+        self.weight = nn.Parameter(weight, requires_grad=True)
+
+
+def dora_weight_norm(weight, lora_a, lora_b, scaling):
+    """peft 0.17.1 DoraLinearLayer.get_weight_norm in torch: the row norms of W + s B A, f32."""
+    v = weight.float() + scaling * (lora_b.float() @ lora_a.float())
+    return torch.linalg.norm(v, dim=1).to(torch.float32)
+
+
 class LoraLinear(nn.Module):
     """peft 0.17.1 lora.Linear naming: base_layer, lora_A/lora_B ModuleDicts keyed 'default', and
     lora_dropout = {'default': nn.Dropout(p) | nn.Identity()} (no parameters: state dicts are those of
     p = 0); f32 adapters on a bf16 base (autocast_adapter_dtype). The math is fused into the GEMMs;
-    the dropout module only names the rate, the mask is the block's own (DESIGN.md "LoRA dropout")."""
+    the dropout module only names the rate, the mask is the block's own (DESIGN.md "LoRA dropout").
+    use_dora=True (peft use_dora, DESIGN.md "DoRA (use_dora)") adds lora_magnitude_vector =
+    {'default': DoraMagnitude}, the f32 magnitude m initialised to the row norms of W + s B A."""
 
-    def __init__(self, base_layer: nn.Linear, r: int, lora_alpha: int, dropout: float = 0.0):
+    def __init__(self, base_layer: nn.Linear, r: int, lora_alpha: int, dropout: float = 0.0,
+                 use_dora: bool = False):
         super().__init__()
         self.base_layer = base_layer
         self.r = ops.check_lora_rank(r)
@@ -122,37 +140,80 @@ class LoraLinear(nn.Module):
                                                           device=dev, dtype=torch.float32)})
         nn.init.kaiming_uniform_(self.lora_A["default"].weight, a=math.sqrt(5))
         nn.init.zeros_(self.lora_B["default"].weight)
+        self.use_dora = bool(use_dora)
+        if self.use_dora:
+            if self.lora_dropout_p > 0.0:
+                raise NotImplementedError("use_dora with lora_dropout > 0 is not supported")
+            with torch.no_grad():
+                m = dora_weight_norm(base_layer.weight, self.lora_A["default"].weight,
+                                     self.lora_B["default"].weight, self.scaling)
+            self.lora_magnitude_vector = nn.ModuleDict({"default": DoraMagnitude(m)})
         self._split_cache = {}
+        self._dora_cache = None
+
+    def dora_operands(self):
+        """DoRA's per-weight-version operands (ops.dora_fold), cached like weight_split: a dict with
+        'norm', 'c' (f32 [out]), 'w' = W_eff = bf16(c W), 'wT' = its transpose and 'sB' = c (.) s B
+        (f32 [out, r]). Rebuilt (a new dict) when A, B, m or the base weight change: new storage, an
+        in-place torch update or a FusedAdamW step (ops.weight_generation())."""
+        a, b = _ab(self)
+        m = self._modules["lora_magnitude_vector"]._modules["default"]._parameters["weight"]
+        w = self._modules["base_layer"]._parameters["weight"]
+        key = (a.data_ptr(), a._version, b.data_ptr(), b._version, m.data_ptr(), m._version, w.data_ptr(),
+               w._version, ops.weight_generation())
+        hit = self._dora_cache
+        if hit is None or hit[0] != key:
+            self._dora_cache = None  # drop the old W_eff / W_eff^T before building the new ones
+            with torch.no_grad():
+                norm, c, w_eff, w_effT, sb = ops.dora_fold(w, a, b, m, self.scaling)
+            hit = (key, {"norm": norm, "c": c, "w": w_eff, "wT": w_effT, "sB": sb})
+            self._dora_cache = hit
+        return hit[1]
 
     def weight_split(self, which):
         """Cached K-extension weight operands (3-term bf16 split, ltx_lora_split_bf16):
         'B' -> s*B for the forward GEMM, 'A' -> A^T for the input-gradient GEMM. Rebuilt when
         the adapter changes: new storage, an in-place torch update (version counter) or a
-        FusedAdamW step (ops.weight_generation())."""
+        FusedAdamW step (ops.weight_generation()). Under DoRA 'B' is the split of c (.) s B
+        (dora_operands), rebuilt with it."""
         p = _ab(self)[1 if which == "B" else 0]
         key = (p.data_ptr(), p._version, ops.weight_generation())
+        dora = self.use_dora and which == "B"
+        if dora:
+            dop = self.dora_operands()
+            key = id(dop)  # the dict is replaced when an operand changes, and held below
         hit = self._split_cache.get(which)
         if hit is None or hit[0] != key:
             with torch.no_grad():
-                t = (ops.lora_split(p, "weight", self.scaling) if which == "B"
-                     else ops.lora_split(p, "weight", transposed=True))
+                if dora:
+                    t = (ops.lora_split(dop["sB"], "weight", 1.0), dop)
+                else:
+                    t = (ops.lora_split(p, "weight", self.scaling) if which == "B"
+                         else ops.lora_split(p, "weight", transposed=True))
             hit = (key, t)
             self._split_cache[which] = hit
-        return hit[1]
+        return hit[1][0] if dora else hit[1]
 
     def weight_pieces(self, which):
         """Cached bf16 pieces (ops.lora_pieces) of 'A' (lora_A) or 'Bt' (lora_B^T): the weight
         operand of the token-sized adapter contractions (ltx_lora_rows); same keys as
-        weight_split."""
+        weight_split. Under DoRA 'Bt' holds the pieces of (c (.) s B)^T: its callers pass alpha 1."""
         p = _ab(self)[1 if which == "Bt" else 0]
         key = (p.data_ptr(), p._version, ops.weight_generation())
+        dora = self.use_dora and which == "Bt"
+        if dora:
+            dop = self.dora_operands()
+            key = id(dop)
         hit = self._split_cache.get("pieces_" + which)
         if hit is None or hit[0] != key:
             with torch.no_grad():
-                t = ops.lora_pieces(p, transposed=(which == "Bt"))
+                if dora:
+                    t = (ops.lora_pieces(dop["sB"], transposed=True), dop)
+                else:
+                    t = ops.lora_pieces(p, transposed=(which == "Bt"))
             hit = (key, t)
             self._split_cache["pieces_" + which] = hit
-        return hit[1]
+        return hit[1][0] if dora else hit[1]
 
     @property
     def weight(self):
@@ -172,10 +233,15 @@ class LoraLinear(nn.Module):
 
     @torch.no_grad()
     def merged_weight(self):
-        """W + s * B A (peft merge_and_unload), in the base dtype."""
+        """W + s * B A (peft merge_and_unload), in the base dtype; under DoRA (m / norm)[:, None] * that
+        sum, with norm its row norms (dora_weight_norm), rounded once."""
         a = self.lora_A["default"].weight
         b = self.lora_B["default"].weight
-        return (self.base_layer.weight.float() + self.scaling * (b @ a)).to(self.base_layer.weight.dtype)
+        v = self.base_layer.weight.float() + self.scaling * (b @ a)
+        if self.use_dora:
+            m = self.lora_magnitude_vector["default"].weight
+            v = (m / torch.linalg.norm(v, dim=1)).view(-1, 1) * v
+        return v.to(self.base_layer.weight.dtype)
 
 
 def _lin(m):
@@ -308,17 +374,54 @@ class BasicTransformerBlock(nn.Module):
         p["qkv_b"] = torch.cat([a1.to_q.bias, a1.to_k.bias, a1.to_v.bias], 0).contiguous()
         p["qkv_wT"] = ops.transpose(p["qkv_w"])
         p["out1_wT"] = ops.transpose(a1.to_out[0].weight)
-        for name, lin in (("q2", a2.to_q), ("k2", a2.to_k), ("v2", a2.to_v), ("o2", a2.to_out[0])):
-            p[name + "_wT"] = ops.transpose(_lin(lin)[0])
-        # text K and V as one [2D, D] projection (they share enc2): one GEMM each way
-        p["kv2_w"] = torch.cat([_lin(a2.to_k)[0], _lin(a2.to_v)[0]], 0).contiguous()
         p["kv2_b"] = torch.cat([_lin(a2.to_k)[1], _lin(a2.to_v)[1]], 0).contiguous()
-        p["kv2_wT"] = torch.cat([p["k2_wT"], p["v2_wT"]], 1).contiguous()
+        if not _is_dora(a2.to_q):  # under DoRA the attn2 weights are the effective ones of weights()
+            for name, lin in (("q2", a2.to_q), ("k2", a2.to_k), ("v2", a2.to_v), ("o2", a2.to_out[0])):
+                p[name + "_w"] = _lin(lin)[0]
+                p[name + "_wT"] = ops.transpose(_lin(lin)[0])
+            # text K and V as one [2D, D] projection (they share enc2): one GEMM each way
+            p["kv2_w"] = torch.cat([_lin(a2.to_k)[0], _lin(a2.to_v)[0]], 0).contiguous()
+            p["kv2_wT"] = torch.cat([p["k2_wT"], p["v2_wT"]], 1).contiguous()
         self._kv_ext = None
         p["ff1_wT"] = ops.transpose(ff.net[0].proj.weight)
         p["ff2_wT"] = ops.transpose(ff.net[2].weight)
         self._pack, self._pack_key = p, key
         return p
+
+    @torch.no_grad()
+    def weights(self):
+        """packed(), and under DoRA on attn2 the effective attn2 weights beside it: q2 / k2 / v2 / o2
+        `_w` = W_eff = bf16(c W) and `_wT` from each projection's dora_operands(), kv2_w / kv2_wT their
+        K | V concatenations. This second pack is rebuilt when an adapter or a magnitude changes (the
+        four operand dicts are replaced then); the frozen pack is not."""
+        p = self.packed()
+        if not _block_dora(self):
+            return p
+        a2 = self._modules["attn2"]._modules
+        lins = (a2["to_q"], a2["to_k"], a2["to_v"], a2["to_out"]._modules["0"])
+        dops = [m.dora_operands() for m in lins]
+        key = (id(p), *(id(d) for d in dops))
+        hit = getattr(self, "_dora_pack", None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        self._dora_pack = None  # drop the old concatenations before building the new ones
+        q = dict(p)
+        for name, d in zip(("q2", "k2", "v2", "o2"), dops):
+            q[name + "_w"], q[name + "_wT"] = d["w"], d["wT"]
+        q["kv2_w"] = torch.cat([dops[1]["w"], dops[2]["w"]], 0).contiguous()
+        q["kv2_wT"] = torch.cat([dops[1]["wT"], dops[2]["wT"]], 1).contiguous()
+        # to_k's and to_v's own copies become views of the concatenations (one copy of each in memory)
+        D = dops[1]["w"].shape[0]
+        for i, name in ((1, "k2"), (2, "v2")):
+            dops[i]["w"] = q[name + "_w"] = q["kv2_w"][(i - 1) * D:i * D]
+            dops[i]["wT"] = q[name + "_wT"] = q["kv2_wT"][:, (i - 1) * D:i * D]
+        self._dora_pack = (key, q, dops)  # hold the operand dicts: ids stay unique
+        return q
+
+
+def _is_dora(m):
+    """a LoraLinear with a DoRA magnitude (peft use_dora)"""
+    return type(m) is LoraLinear and m.use_dora
 
 
 def _kv_ext(blk, lk, lv):
@@ -428,24 +531,56 @@ def _block_dropout(blk):
     return ps.pop() if ps else 0.0
 
 
-def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da=True, da_alpha=1.0):
+def _block_dora(blk):
+    """True when the block's adapters are DoRA adapters (peft use_dora): then they are the four attn2
+    projections and nothing else, without dropout. NotImplementedError for DoRA mixed with plain
+    adapters in one block, or on attn1 / the feed-forward."""
+    ms = _block_lora_linears(blk)
+    n = sum(m.use_dora for m in ms)
+    if n == 0:
+        return False
+    if n != len(ms):
+        raise NotImplementedError("DoRA and plain LoRA adapters cannot be mixed within one block")
+    a2 = blk._modules["attn2"]._modules
+    want = (a2["to_q"], a2["to_k"], a2["to_v"], a2["to_out"]._modules["0"])
+    if len(ms) != 4 or any(a is not b for a, b in zip(ms, want)):
+        raise NotImplementedError("use_dora is supported on the four attn2 projections only")
+    if any(m.lora_dropout_p > 0.0 for m in ms):
+        raise NotImplementedError("use_dora with lora_dropout > 0 is not supported")
+    return True
+
+
+def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da=True, da_alpha=1.0,
+                   dora=False):
     """One adapter's backward: dB and dA into .grad, returns (w = s dY B, its split operand). The
     one-pass forms where they apply (ops.lora_dy), else lora_wgrad + lora_down. merge_da=False keeps
     dA a separate lora_wgrad call even where the merged ltx_lora_dy_dA applies (bitwise the same).
-    da_alpha scales dA: the dropout scale c when x is a masked xd (dA = c w^T xd)."""
+    da_alpha scales dA: the dropout scale c when x is a masked xd (dA = c w^T xd).
+    dora=True (a DoRA adapter; Bw is ignored): the same kernels on the effective up-projection
+    B_eff = c (.) s B with alpha 1, so w = dY B_eff is already the w of dA and dx; they write dY^T u
+    into a scratch (accumulate = 0) and dB[j, :] += s c_j scratch[j, :] follows (ops.dora_rowscale_add)."""
+    if dora:
+        dop = lin.dora_operands()
+        Bw, sa, acc = dop["sB"], 1.0, False
+        dB = torch.empty(dy.shape[1], r, dtype=torch.float32, device=dy.device)
+    else:
+        sa, acc, dB = s, True, _grad_buf(lin, "B")
     dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dy, r)
     if dy_ok and merge_da and ops.lora_dy_da_fits(dy, x, r):
         # one pass over dY, one over x (dA), one finish for w / split, dB and dA
-        return ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), x=x,
-                           dA_out=_grad_buf(lin, "A"), w_out=w_out, split_out=split_out, dA_alpha=da_alpha)
-    if dy_ok:  # one pass over dY
-        w, sw = ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, s, _grad_buf(lin, "B"), w_out=w_out,
-                            split_out=split_out)
+        w, sw = ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, sa, dB, accumulate=acc, x=x,
+                            dA_out=_grad_buf(lin, "A"), w_out=w_out, split_out=split_out, dA_alpha=da_alpha)
     else:
-        ops.lora_wgrad(dy, u, alpha=s, out=_grad_buf(lin, "B"), accumulate=True)
-        w, sw = ops.lora_down(dy, Bw, alpha=s, transposed=True, split=True, out=w_out, split_out=split_out,
-                              pieces=lambda: lin.weight_pieces("Bt"))
-    ops.lora_wgrad(x, w, alpha=da_alpha, transpose_out=True, out=_grad_buf(lin, "A"), accumulate=True)
+        if dy_ok:  # one pass over dY
+            w, sw = ops.lora_dy(dy, u, lin.weight_pieces("Bt"), r, sa, dB, accumulate=acc, w_out=w_out,
+                                split_out=split_out)
+        else:
+            ops.lora_wgrad(dy, u, alpha=sa, out=dB, accumulate=acc)
+            w, sw = ops.lora_down(dy, Bw, alpha=sa, transposed=True, split=True, out=w_out, split_out=split_out,
+                                  pieces=lambda: lin.weight_pieces("Bt"))
+        ops.lora_wgrad(x, w, alpha=da_alpha, transpose_out=True, out=_grad_buf(lin, "A"), accumulate=True)
+    if dora:
+        ops.dora_rowscale_add(_grad_buf(lin, "B"), dB, dop["c"], s)
     return w, sw
 
 
@@ -617,10 +752,15 @@ def _ab(m):
             m._modules["lora_B"]._modules["default"]._parameters["weight"])
 
 
+def _dora_m(m):
+    """the magnitude parameter of a DoRA LoraLinear, by direct lookup"""
+    return m._modules["lora_magnitude_vector"]._modules["default"]._parameters["weight"]
+
+
 def _grad_buf(lin, which):
-    """The .grad of a LoraLinear adapter weight ('A' or 'B'), created zeroed on first use: the
-    LoRA wgrad kernels add into it directly (no per-micro-step buffer, memset or add)."""
-    p = _ab(lin)[0 if which == "A" else 1]
+    """The .grad of a LoraLinear adapter weight ('A' or 'B'; 'm' = the DoRA magnitude), created zeroed
+    on first use: the LoRA wgrad kernels add into it directly (no per-micro-step buffer, memset or add)."""
+    p = _dora_m(lin) if which == "m" else _ab(lin)[0 if which == "A" else 1]
     if p.grad is None:
         p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
     return p.grad
@@ -638,7 +778,7 @@ class _BlockFn(torch.autograd.Function):
         rpm = sh.rpm
         if skip is not None and keep:
             raise NotImplementedError("skip-layer masks are an inference (forward-only) feature")
-        W = blk.packed()
+        W = blk.weights()
         a1, a2, ff = blk.attn1, blk.attn2, blk.ff
         ldm = mods.stride(0)
         # lora_ab = the attn2 adapters' 8 tensors (_lora_ab), then the attn1 adapters' 8 (_lora_ab1),
@@ -706,8 +846,10 @@ class _BlockFn(torch.autograd.Function):
             h1 = ops.gemm(o1, a1.to_out[0].weight, bias=a1.to_out[0].bias, epilogue="gated_residual",
                           aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm)
         # ---- 2. attn2 on the un-normalised h1 (attention.py:273-285), LoRA fused into the GEMMs
-        wq, bq, _ = _lin(a2.to_q)
-        wo, bo, _ = _lin(a2.to_out[0])
+        # (W["q2_w"] / W["o2_w"]: the base weights, or under DoRA the effective bf16(c W); the s u B^T
+        # term then rides the K extension with split(c (.) s B), LoraLinear.weight_split)
+        wq, bq = W["q2_w"], _lin(a2.to_q)[1]
+        wo, bo = W["o2_w"], _lin(a2.to_out[0])[1]
         pre = sh.text_pre.pop(id(blk), None) if sh.text_pre is not None else None
         if has_lora:
             # peft LoRA fused into the K loop: [x | split(x.A^T)] . [W | split(s*B)]^T
@@ -795,7 +937,7 @@ class _BlockFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         (h, enc2, mods, onep, rstd1, qkv, qk, rq1, rk1, o1, lse1, h1, q2raw, rq2, q2, k2raw, rk2,
          k2, v2, o2, lse2, h2, rstd2, fpre) = saved[:24]
-        W = blk.packed()
+        W = blk.weights()
         a1, a2 = blk.attn1, blk.attn2
         ldm = mods.stride(0)
         dh3 = dh3.contiguous()
@@ -809,6 +951,10 @@ class _BlockFn(torch.autograd.Function):
             u_q, u_k, u_v, u_o = saved[32:36]
             lora = _lora_params(blk)
             r, s = lora[0].r, lora[0].scaling
+        # DoRA on attn2 (DESIGN.md "DoRA (use_dora)"): W holds the effective weights, the adapters'
+        # backward runs on B_eff = c (.) s B (_lora_backward dora=True), and the four magnitude gradients
+        # dm = (1 / m) sum_rows dY (y - b) go straight into .grad
+        dora = has_lora and lora[0].use_dora
         has1 = ctx.has1
         if has1:
             o1s = 36 if has_lora else 24
@@ -902,6 +1048,15 @@ class _BlockFn(torch.autograd.Function):
             do2 = ops.gemm(dh2, W["o2_wT"])
             _masked_add(do2, w_o, [Ao], dp, (7,))
             del w_o
+        elif dora:
+            lq, lk, lv, lo = lora
+            _, sw = _lora_backward(dh2, u_o, lo, None, o2, r, s, dora=True)
+            do2 = ops.gemm(dh2, W["o2_wT"], ext=(sw, lo.weight_split("A")), **rd)
+            # to_out.0's output went into the residual and was never stored: y - b is recomputed with
+            # one store GEMM (o2 . W_eff^T plus the K extension from the kept u_o, no bias)
+            yo = ops.gemm(o2, W["o2_w"], ext=(ops.lora_split(u_o, "act"), lo.weight_split("B")))
+            ops.dora_mag_grad(dh2, yo, None, _dora_m(lo), _grad_buf(lo, "m"))
+            del yo
         elif has_lora:
             lq, lk, lv, lo = lora
             dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dh2, r)
@@ -1011,6 +1166,26 @@ class _BlockFn(torch.autograd.Function):
             denc = ops.gemm(dkv, W["kv2_wT"])
             _masked_add(denc, w_kv, [Ak, Av], dp, (5, 6))
             del w_kv
+            grads_lora = grads_lora + [None] * 8
+        elif dora:
+            # (the per-block text path: a DoRA model has no text stack; with a shared prompt dk2raw / dv2
+            # are the batch-summed text gradients, the right dY of the shared rows' magnitudes too)
+            _, sw = _lora_backward(dq2raw, u_q, lq, None, h1, r, s, dora=True)
+            dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2,
+                           ext=(sw, lq.weight_split("A")), **gated)
+            ops.dora_mag_grad(dq2raw, q2raw, _lin(lq)[1], _dora_m(lq), _grad_buf(lq, "m"))
+            K2 = ops.lora_k2(r)
+            swkv = torch.empty(dkv.shape[0], 2 * K2, dtype=torch.bfloat16, device=h.device)
+            for i, (dy, y_t, u_t, lt) in enumerate(((dk2raw, k2raw, u_k, lk), (dv2, v2, u_v, lv))):
+                dop = lt.dora_operands()
+                dB = ops.lora_wgrad(dy, u_t)
+                ops.dora_rowscale_add(_grad_buf(lt, "B"), dB, dop["c"], s)
+                w_t, _ = ops.lora_down(dy, dop["sB"], transposed=True, split=True,
+                                       split_out=swkv[:, i * K2:(i + 1) * K2])
+                ops.lora_wgrad(enc2, w_t, transpose_out=True, out=_grad_buf(lt, "A"), accumulate=True)
+                ops.dora_mag_grad(dy, y_t, _lin(lt)[1], _dora_m(lt), _grad_buf(lt, "m"))
+            denc = ops.gemm(dkv, W["kv2_wT"], ext=(swkv, _kv_ext(blk, lk, lv)[1]))
+            del swkv
             grads_lora = grads_lora + [None] * 8
         elif has_lora:
             dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dq2raw, r)
@@ -1206,7 +1381,7 @@ def _text_kv(blk, sh, enc2, lora_ab, dp=None):
     _forward_tokens can compute them on a side stream one block ahead. Under LoRA dropout (dp) the
     to_k / to_v adapters read their own masked per-sample text rows (slots 5 and 6)."""
     a2 = blk.attn2
-    W = blk.packed()
+    W = blk.weights()
     D = sh.D
     if lora_ab:
         lora = _lora_params(blk)
@@ -1656,6 +1831,10 @@ class Transformer3DModel(nn.Module):
         lins = [_lora_params(b) for b in blocks]
         if any(l is None for l in lins):
             return None
+        # a model with DoRA adapters takes the per-block text path (its effective K/V weights change
+        # with the adapters; folding them into the grouped launches is not built)
+        if any(m.use_dora for l in lins for m in l):
+            return None
         # (+ the identity of attn1.to_q and of ff.net.2: wrapping attn1 or the feed-forward later
         # changes the blocks' parameter lists)
         key = tuple((id(l[1]), id(l[2]), _base(l[1])._parameters["weight"].requires_grad,
@@ -1914,7 +2093,7 @@ class Transformer3DModel(nn.Module):
             def prep(j):
                 bj = blocks[j]
                 with torch.no_grad():  # weight caches are built on the main stream
-                    bj.packed()
+                    bj.weights()
                     lj = _lora_params(bj)
                     if lj is not None:
                         _kv_ext(bj, lj[1], lj[2])
