@@ -1,0 +1,50 @@
+"""Merge an adapter checkpoint directory into its base checkpoint.
+
+train_loop with config.save_adapters writes <output_dir>/adapter_epoch_{E}/ (ltx_amd.io.
+save_adapter_checkpoint): at LTX-2B 80 to 206 MiB of weights against the merged single-file
+checkpoint's 3.8 GB (profiles/adapter_checkpoint.md). This tool makes
+the merged file on demand, through the same export train_loop uses (io.export_merged_safetensors:
+W + s B A, or DoRA's (m / norm) (W + s B A), rounded once to the base dtype; adapter keys dropped), so
+the small directories are all that has to be kept. Runs on the CPU; nothing in either input is executed.
+
+    python tools/merge_adapter.py BASE.safetensors ADAPTER_DIR OUT.safetensors
+"""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "video-generation-for-human-avatars_amd"))
+
+
+def merge(base, adapter_dir, out):
+    """The base checkpoint (anything Transformer3DModel.from_pretrained reads) with the adapters,
+    magnitudes and caption_projection of `adapter_dir` folded in, written to `out`; returns `out`."""
+    from ltx_amd import io
+    from ltx_amd.transformer3d import Transformer3DModel
+    model = Transformer3DModel.from_pretrained(base)
+    state = io.load_adapter_checkpoint(model, adapter_dir)
+    meta = {"epoch": str(state["epoch"]), "global_step": str(state["global_step"]), "source": "merge_adapter"}
+    if os.path.isfile(base):  # a single-file base carries its scheduler config along
+        import json
+
+        from safetensors import safe_open
+        with safe_open(base, framework="pt", device="cpu") as f:
+            scheduler = json.loads((f.metadata() or {}).get("config", "{}")).get("scheduler")
+        if scheduler is not None:
+            meta["scheduler"] = scheduler
+    io.export_merged_safetensors(model, out, meta)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("base", help="base checkpoint: a single-file safetensors or a diffusers-style directory")
+    ap.add_argument("adapter_dir", help="an adapter_epoch_{E} directory")
+    ap.add_argument("out", help="the merged single-file safetensors to write")
+    a = ap.parse_args(argv)
+    print(merge(a.base, a.adapter_dir, a.out))
+
+
+if __name__ == "__main__":
+    main()

@@ -129,4 +129,11 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     # attn2 projections
     if "use_dora" in t:
         setattr(config, "use_dora", bool(t["use_dora"]))
+    # and the two keys training.train_loop reads: `train.save_adapters` (a bool, absent = False):
+    # <output_dir>/adapter_epoch_{E}/ beside every merged checkpoint; `train.resume_from` (such a
+    # directory, or "auto" for the highest complete one in output_dir)
+    if "save_adapters" in t:
+        setattr(config, "save_adapters", bool(t["save_adapters"]))
+    if "resume_from" in t:
+        setattr(config, "resume_from", str(t["resume_from"]))
     return config

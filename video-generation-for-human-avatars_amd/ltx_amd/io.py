@@ -15,9 +15,16 @@
   Transformer3DModel.from_pretrained / RectifiedFlowScheduler.from_pretrained read them.
   lora_audio checkpoints export the peft merge (W + (B @ A) * scaling, rounded to the base dtype,
   adapters dropped); full checkpoints save the state dict.
+* Adapter checkpoints (save_adapter_checkpoint / load_adapter_checkpoint): a directory of
+  safetensors and JSON files only -- the trainable tensors under peft's saved names, peft's
+  adapter_config.json, the FusedAdamW moments and the RNG states, and train_state.json, written
+  last. What train_loop resumes from; nothing in it is executed on load.
 """
 import json
+import math
 import os
+import re
+import shutil
 from pathlib import Path
 from typing import Dict, List, Optional
 
@@ -215,3 +222,412 @@ def save_training_checkpoint(model, target_path, train_mode, metadata: Optional[
     else:
         save_module_safetensors(model, target_path, metadata)
     return target_path
+
+
+# ---------------------------------------------------------------------------------------------
+# adapter checkpoints
+# ---------------------------------------------------------------------------------------------
+ADAPTER_FORMAT_VERSION = 1
+ADAPTER_WEIGHTS = "adapter_model.safetensors"
+ADAPTER_CONFIG = "adapter_config.json"
+ADAPTER_OPTIMIZER = "optimizer.safetensors"
+ADAPTER_TRAIN_STATE = "train_state.json"
+_PEFT_PREFIX = "base_model.model."
+_ADAPTER_HOLDERS = ("lora_A", "lora_B", "lora_magnitude_vector")  # ModuleDicts keyed by the adapter name
+_ADAPTER_GROUPS = ("attn1", "attn2", "ff")
+_GROUP_FIELDS = ("r", "lora_alpha", "scaling", "lora_dropout", "use_dora")
+_ADAPTER_DIR = re.compile(r"adapter_epoch_(\d+)$")
+
+
+def adapter_key(name, to_model=False):
+    """The one mapping between this model's parameter names and the keys of adapter_model.safetensors.
+
+    Model -> file: the prefix 'base_model.model.' is put in front, and the adapter name 'default' is
+    removed where it is the key of a lora_A / lora_B / lora_magnitude_vector ModuleDict:
+      transformer_blocks.0.attn2.to_q.lora_A.default.weight
+        -> base_model.model.transformer_blocks.0.attn2.to_q.lora_A.weight
+      ....lora_magnitude_vector.default.weight -> base_model.model.....lora_magnitude_vector.weight
+      caption_projection.linear_1.weight -> base_model.model.caption_projection.linear_1.weight
+    to_model=True is the inverse (ValueError for a key without the prefix).
+
+    This is what peft 0.17.1's get_peft_model_state_dict writes for a LoraConfig model (the keys of
+    PeftModel.state_dict() that contain 'lora_', with '.default' removed). It is pinned to peft's
+    published behaviour only: peft is not a dependency of this project and the oracle's peft shim has
+    no save path, so no test compares against a file peft wrote. The caption_projection keys are an
+    extension: peft would not save a trainable base parameter."""
+    if to_model:
+        if not name.startswith(_PEFT_PREFIX):
+            raise ValueError(f"adapter key {name!r}: expected the prefix {_PEFT_PREFIX!r}")
+        parts = name[len(_PEFT_PREFIX):].split(".")
+        if len(parts) >= 2 and parts[-2] in _ADAPTER_HOLDERS:
+            parts.insert(len(parts) - 1, "default")
+        return ".".join(parts)
+    parts = name.split(".")
+    if len(parts) >= 3 and parts[-2] == "default" and parts[-3] in _ADAPTER_HOLDERS:
+        del parts[-2]
+    return _PEFT_PREFIX + ".".join(parts)
+
+
+def _adapter_layout(model):
+    """(wrapped module names in module order, {group: {r, lora_alpha, scaling, lora_dropout, use_dora}})
+    of the model's LoraLinears; the groups are attn1, attn2 and ff. ValueError when the adapters of one
+    group differ among themselves (adapter_config.json states one description per group)."""
+    from .transformer3d import LoraLinear
+    targets, groups = [], {}
+    for name, mod in model.named_modules():
+        if not isinstance(mod, LoraLinear):
+            continue
+        parts = name.split(".")
+        group = parts[2] if len(parts) > 3 and parts[0] == "transformer_blocks" else None
+        if group not in _ADAPTER_GROUPS:
+            raise ValueError(f"adapter on {name!r}: expected transformer_blocks.<i>.<{'|'.join(_ADAPTER_GROUPS)}>.*")
+        desc = {"r": int(mod.r), "lora_alpha": mod.lora_alpha, "scaling": float(mod.scaling),
+                "lora_dropout": float(mod.lora_dropout_p), "use_dora": bool(mod.use_dora)}
+        if groups.setdefault(group, desc) != desc:
+            raise ValueError(f"adapter on {name!r} is {desc}, the other {group} adapters are {groups[group]}: "
+                             f"an adapter checkpoint holds one description per group")
+        targets.append(name)
+    return targets, groups
+
+
+def _layout_difference(have, want):
+    """The first difference between two _adapter_layout results as a sentence, or None."""
+    (have_t, have_g), (want_t, want_g) = have, want
+    have_set, want_set = set(have_t), set(want_t)
+    for name in want_t:
+        if name not in have_set:
+            return f"the checkpoint has an adapter on {name}, the model has none"
+    for name in have_t:
+        if name not in want_set:
+            return f"the model has an adapter on {name}, the checkpoint has none"
+    for group in _ADAPTER_GROUPS:
+        for field in _GROUP_FIELDS:
+            a, b = have_g.get(group, {}).get(field), want_g.get(group, {}).get(field)
+            if a != b:
+                return f"{group} {field}: the model has {a!r}, the checkpoint {b!r}"
+    return None
+
+
+def _dist_rank_world():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def _model_device(model):
+    return next(model.parameters()).device
+
+
+def _gathered_rng_states(device):
+    """{'rng.cpu.rank{r}', 'rng.device.rank{r}': uint8 state} of every rank (a collective when
+    torch.distributed is initialised): torch's CPU generator, the source of the LoRA-dropout keys,
+    and `device`'s generator (t and noise); no device entry for a CPU model."""
+    import torch.distributed as dist
+    rank, world = _dist_rank_world()
+    mine = {"cpu": torch.get_rng_state()}
+    if device.type == "cuda":
+        mine["device"] = torch.cuda.get_rng_state(device)
+    out = {}
+    for kind, t in mine.items():
+        if world == 1:
+            out[f"rng.{kind}.rank0"] = t.clone()
+            continue
+        on = device if dist.get_backend() == "nccl" else torch.device("cpu")
+        parts = [torch.empty(t.shape, dtype=t.dtype, device=on) for _ in range(world)]
+        dist.all_gather(parts, t.to(on))
+        for r, p in enumerate(parts):
+            out[f"rng.{kind}.rank{r}"] = p.cpu()
+    return out
+
+
+def _plain(v):
+    """A hyper-parameter as JSON holds it, or None when it is not a plain value."""
+    if isinstance(v, (bool, int, float, str)) or v is None:
+        return v
+    if isinstance(v, (tuple, list)) and all(isinstance(x, (bool, int, float, str)) for x in v):
+        return list(v)
+    return None
+
+
+def _write_json(path, obj):
+    with open(path, "w") as f:
+        json.dump(obj, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, loader=None,
+                            metadata: Optional[dict] = None):
+    """Write the adapter checkpoint directory `path` (safetensors and JSON only) and return it:
+
+    * adapter_model.safetensors: every parameter with requires_grad, in its own dtype, under
+      adapter_key's names; `metadata` becomes its string metadata;
+    * adapter_config.json: peft's LoraConfig fields that apply (r / lora_alpha / lora_dropout /
+      use_dora of the attn2 group, or of the first group present; base_model_name_or_path =
+      metadata['base_model_name_or_path'] when given) and an 'ltx_amd' block with the format version
+      and each group's own rank, alpha, scaling, dropout and DoRA flag;
+    * optimizer.safetensors (with `optimizer`): exp_avg.<parameter name> / exp_avg_sq.<parameter name>
+      in their stored dtype and every rank's RNG states (_gathered_rng_states);
+    * train_state.json, written last: the format version, `train_state`'s epoch / global_step /
+      best_loss, the world size, the optimizer's hyper-parameters and per-parameter step, and
+      `loader`'s seed.
+
+    Everything is written under `path`.tmp and moved into place with os.replace, so a checkpoint is
+    complete or absent. Under torch.distributed every rank calls this (the RNG states are gathered);
+    rank 0 writes."""
+    from safetensors.torch import save_file
+    path = os.fspath(path)
+    rank, world = _dist_rank_world()
+    targets, groups = _adapter_layout(model)
+    if not targets:
+        raise ValueError("save_adapter_checkpoint: the model has no LoRA adapters")
+    # the one collective, before rank 0 goes its own way
+    rng = _gathered_rng_states(_model_device(model)) if optimizer is not None else None
+    if rank != 0:
+        return path
+    named = list(model.named_parameters())
+    tensors = {adapter_key(n): p.detach().cpu().contiguous() for n, p in named if p.requires_grad}
+    state = {"format_version": ADAPTER_FORMAT_VERSION, "epoch": 0, "global_step": 0, "best_loss": None}
+    state.update(train_state or {})
+    best = state["best_loss"]
+    state["best_loss"] = float(best) if best is not None and math.isfinite(best) else None
+    state["world_size"] = world
+    opt_tensors = None
+    if optimizer is not None:
+        names = {id(p): n for n, p in named}
+        opt_tensors, steps = {}, {}
+        for group in optimizer.param_groups:
+            for p in group["params"]:
+                if id(p) not in names:
+                    raise ValueError("save_adapter_checkpoint: the optimizer holds a parameter that is not the model's")
+                st = optimizer.state.get(p)
+                if st:
+                    name = names[id(p)]
+                    steps[name] = int(st["step"])
+                    opt_tensors["exp_avg." + name] = st["exp_avg"].detach().cpu().contiguous()
+                    opt_tensors["exp_avg_sq." + name] = st["exp_avg_sq"].detach().cpu().contiguous()
+        opt_tensors.update(rng)
+        hyper = [{k: _plain(v) for k, v in g.items() if k != "params" and _plain(v) is not None}
+                 for g in optimizer.param_groups]
+        state["optimizer"] = {"class": type(optimizer).__name__, "param_groups": hyper, "step": steps}
+    if loader is not None and hasattr(loader, "seed"):
+        state["loader"] = {"seed": int(loader.seed)}
+    meta = dict(metadata or {})
+    main = groups.get("attn2") or next(groups[g] for g in _ADAPTER_GROUPS if g in groups)
+    config = {"peft_type": "LORA", "base_model_name_or_path": meta.get("base_model_name_or_path"),
+              "r": main["r"], "lora_alpha": main["lora_alpha"], "target_modules": targets,
+              "lora_dropout": main["lora_dropout"], "use_dora": main["use_dora"], "bias": "none",
+              "ltx_amd": {"format_version": ADAPTER_FORMAT_VERSION, "groups": groups}}
+    tmp = path.rstrip("/\\") + ".tmp"
+    if os.path.isdir(tmp):
+        shutil.rmtree(tmp)
+    os.makedirs(tmp)
+    meta = _string_meta({k: v for k, v in meta.items() if v is not None})
+    meta.setdefault("format", "pt")
+    save_file(tensors, os.path.join(tmp, ADAPTER_WEIGHTS), metadata=meta)
+    _write_json(os.path.join(tmp, ADAPTER_CONFIG), config)
+    if opt_tensors is not None:
+        save_file(opt_tensors, os.path.join(tmp, ADAPTER_OPTIMIZER))
+    _write_json(os.path.join(tmp, ADAPTER_TRAIN_STATE), state)
+    old = None
+    if os.path.isdir(path):  # os.replace does not move onto a directory that has files
+        old = path.rstrip("/\\") + ".old"
+        if os.path.isdir(old):
+            shutil.rmtree(old)
+        os.replace(path, old)
+    os.replace(tmp, path)
+    if old is not None:
+        shutil.rmtree(old)
+    return path
+
+
+def _inject_from_config(model, targets, groups):
+    """inject_lora per group of an adapter_config.json into a model without adapters, then the
+    lora_audio trainable set (lora.apply_training_strategy's rule)."""
+    from .lora import inject_lora
+    for group in _ADAPTER_GROUPS:
+        if group not in groups:
+            continue
+        d = groups[group]
+        names = [t for t in targets if t.split(".")[2] == group]
+        inject_lora(model, names, d["r"], d["lora_alpha"], feed_forward=(group == "ff"),
+                    dropout=d["lora_dropout"], dora=d["use_dora"])
+    for n, p in model.named_parameters():
+        p.requires_grad = ("lora_" in n) or ("caption_projection" in n)
+
+
+def _remove_adapters(model, requires_grad):
+    """Undo _inject_from_config after a refusal: every LoraLinear back to its base linear (no merge),
+    requires_grad as recorded."""
+    from .transformer3d import LoraLinear
+    for name, mod in list(model.named_modules()):
+        if isinstance(mod, LoraLinear):
+            parent_name, _, child = name.rpartition(".")
+            parent = model.get_submodule(parent_name)
+            if child.isdigit():
+                parent[int(child)] = mod.base_layer
+            else:
+                setattr(parent, child, mod.base_layer)
+    for p in model.parameters():
+        p.requires_grad = requires_grad[id(p)]
+
+
+def _read_json(path):
+    with open(path) as f:
+        return json.load(f)
+
+
+def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=True):
+    """Restore the directory save_adapter_checkpoint wrote and return its train_state dict
+    (best_loss = inf when none was recorded).
+
+    A model without adapters first gets them from adapter_config.json through lora.inject_lora (rank,
+    alpha, targets, feed_forward, dropout and dora per group, so every refusal of inject_lora
+    applies) and the lora_audio trainable set. A model with adapters must match the file: wrapped
+    set, ranks, alphas, scalings, dropout and DoRA flags. Every check runs before the first tensor is
+    written, and a refusal leaves the model as it was: ValueError naming the first difference, a
+    missing or unexpected key (strict=True), a shape or dtype that does not fit, or another world size.
+
+    Values are copied in place (copy_), so pointers held elsewhere (GradAllReduce buckets, the
+    FusedAdamW chunk table) stay valid; then ops.bump_weight_generation() and every block's packed
+    weights are dropped, as unload_lora does. With `optimizer` the moments, per-parameter steps
+    (state is created where the optimizer has not stepped yet), hyper-parameters and this rank's two
+    RNG states are restored; with `loader` its seed."""
+    from safetensors.torch import load_file
+
+    from . import ops
+    path = os.fspath(path)
+    if not os.path.isfile(os.path.join(path, ADAPTER_TRAIN_STATE)):
+        raise FileNotFoundError(f"{path}: no {ADAPTER_TRAIN_STATE} (not a complete adapter checkpoint)")
+    state = _read_json(os.path.join(path, ADAPTER_TRAIN_STATE))
+    config = _read_json(os.path.join(path, ADAPTER_CONFIG))
+    block = config.get("ltx_amd") or {}
+    for v in (state.get("format_version"), block.get("format_version")):
+        if v != ADAPTER_FORMAT_VERSION:
+            raise ValueError(f"{path}: adapter checkpoint format {v!r}, this build reads {ADAPTER_FORMAT_VERSION}")
+    rank, world = _dist_rank_world()
+    if state.get("world_size") != world:
+        raise ValueError(f"{path}: written by {state.get('world_size')} ranks, loaded by {world}: the RNG "
+                         f"states are per rank")
+    tensors = load_file(os.path.join(path, ADAPTER_WEIGHTS))
+    opt_tensors = None
+    if optimizer is not None:
+        if "optimizer" not in state or not os.path.isfile(os.path.join(path, ADAPTER_OPTIMIZER)):
+            raise ValueError(f"{path}: holds no optimizer state")
+        opt_tensors = load_file(os.path.join(path, ADAPTER_OPTIMIZER))
+    want = (list(config["target_modules"]), block["groups"])
+    have = _adapter_layout(model)
+    injected, requires_grad = False, {id(p): p.requires_grad for p in model.parameters()}
+    try:
+        if not have[0]:
+            injected = True
+            _inject_from_config(model, *want)
+            have = _adapter_layout(model)
+        diff = _layout_difference(have, want)
+        if diff is not None:
+            raise ValueError(f"{path}: {diff}")
+        named = list(model.named_parameters())
+        trainable = {adapter_key(n): p for n, p in named if p.requires_grad}
+        missing = [k for k in trainable if k not in tensors]
+        unexpected = [k for k in tensors if k not in trainable]
+        if strict and (missing or unexpected):
+            raise ValueError(f"{path}: {ADAPTER_WEIGHTS} missing keys {missing[:3]}, unexpected keys "
+                             f"{unexpected[:3]} ({len(missing)} / {len(unexpected)} in all)")
+        for k, p in trainable.items():
+            t = tensors.get(k)
+            if t is not None and (t.shape != p.shape or (strict and t.dtype != p.dtype)):
+                raise ValueError(f"{path}: {k} is {t.dtype} {tuple(t.shape)}, the model's parameter "
+                                 f"{p.dtype} {tuple(p.shape)}")
+        plan = None
+        if optimizer is not None:
+            plan = _optimizer_plan(path, optimizer, named, state["optimizer"], opt_tensors, rank, strict)
+    except Exception:
+        if injected:
+            _remove_adapters(model, requires_grad)
+        raise
+    with torch.no_grad():
+        for k, p in trainable.items():
+            if k in tensors:
+                p.copy_(tensors[k])
+    ops.bump_weight_generation()  # weight-derived caches (splits, pieces, DoRA operands, text stack)
+    for blk in getattr(model, "transformer_blocks", ()):
+        blk._pack = blk._pack_key = None
+        blk._dora_pack = None
+    if optimizer is not None:
+        _restore_optimizer(optimizer, state["optimizer"], opt_tensors, plan, rank, _model_device(model))
+    if loader is not None and "loader" in state and hasattr(loader, "seed"):
+        loader.seed = state["loader"]["seed"]
+    if state.get("best_loss") is None:
+        state["best_loss"] = float("inf")
+    return state
+
+
+def _optimizer_plan(path, optimizer, named, saved, opt_tensors, rank, strict):
+    """The checks of the optimizer restore, before anything is written: [(parameter, its name, saved
+    step or None)] in the optimizer's order."""
+    names = {id(p): n for n, p in named}
+    if len(saved["param_groups"]) != len(optimizer.param_groups):
+        raise ValueError(f"{path}: {len(saved['param_groups'])} optimizer parameter groups, the optimizer "
+                         f"has {len(optimizer.param_groups)}")
+    plan, seen = [], set()
+    for group in optimizer.param_groups:
+        for p in group["params"]:
+            name = names.get(id(p))
+            if name is None:
+                raise ValueError(f"{path}: the optimizer holds a parameter that is not the model's")
+            step = saved["step"].get(name)
+            for k in ("exp_avg.", "exp_avg_sq."):
+                t = opt_tensors.get(k + name)
+                if (t is None) != (step is None):
+                    raise ValueError(f"{path}: {k + name} and the step of {name} do not go together")
+                if t is not None and t.shape != p.shape:
+                    raise ValueError(f"{path}: {k + name} is {tuple(t.shape)}, the parameter {tuple(p.shape)}")
+            seen.add(name)
+            plan.append((p, name, step))
+    extra = [k for k in opt_tensors if not k.startswith("rng.") and k.split(".", 1)[1] not in seen]
+    extra += [n for n in saved["step"] if n not in seen]
+    if strict and extra:
+        raise ValueError(f"{path}: optimizer state for {extra[:3]}, which the optimizer does not hold "
+                         f"({len(extra)} in all)")
+    if f"rng.cpu.rank{rank}" not in opt_tensors:
+        raise ValueError(f"{path}: no RNG state of rank {rank}")
+    return plan
+
+
+@torch.no_grad()
+def _restore_optimizer(optimizer, saved, opt_tensors, plan, rank, device):
+    for group, hyper in zip(optimizer.param_groups, saved["param_groups"]):
+        for k, v in hyper.items():
+            group[k] = tuple(v) if isinstance(group.get(k), tuple) and isinstance(v, list) else v
+    for p, name, step in plan:
+        if step is None:
+            optimizer.state.pop(p, None)
+            continue
+        st = optimizer.state[p]
+        for k in ("exp_avg", "exp_avg_sq"):
+            src = opt_tensors[f"{k}.{name}"]
+            cur = st.get(k)
+            if torch.is_tensor(cur) and cur.shape == src.shape and cur.dtype == src.dtype:
+                cur.copy_(src)  # in place: the chunk table's pointers stay valid
+            else:
+                st[k] = src.to(p.device, copy=True)
+        cur = st.get("step")
+        st["step"] = cur.fill_(step) if torch.is_tensor(cur) else int(step)
+    torch.set_rng_state(opt_tensors[f"rng.cpu.rank{rank}"])
+    dev_state = opt_tensors.get(f"rng.device.rank{rank}")
+    if dev_state is not None and device.type == "cuda":
+        torch.cuda.set_rng_state(dev_state, device)
+
+
+def latest_adapter_checkpoint(output_dir):
+    """The complete `adapter_epoch_{E}` directory with the highest E in `output_dir` (complete: it
+    holds train_state.json, the file written last), or None."""
+    best = None
+    if output_dir and os.path.isdir(output_dir):
+        for entry in os.listdir(output_dir):
+            m = _ADAPTER_DIR.match(entry)
+            full = os.path.join(output_dir, entry)
+            if m and os.path.isfile(os.path.join(full, ADAPTER_TRAIN_STATE)):
+                if best is None or int(m.group(1)) > best[0]:
+                    best = (int(m.group(1)), full)
+    return None if best is None else best[1]

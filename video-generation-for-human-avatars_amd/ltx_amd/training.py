@@ -437,15 +437,32 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
 
 
 def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, device=None,
-               log_fn=None, rank=0):
+               log_fn=None, rank=0, val_dataloader=None, resume_from=None):
     """training.py:234-401 for precomputed prompt embeddings (the T5 encode of main() is out of
     scope): trainable set per config.train_mode, FusedAdamW(lr), per-epoch checkpoints every
     `save_every_n_epochs` (best_ prefix on a new best epoch loss) through
-    io.save_training_checkpoint, DP gradient averaging when torch.distributed is initialised."""
+    io.save_training_checkpoint, DP gradient averaging when torch.distributed is initialised.
+
+    `val_dataloader`: validation.validate_epoch after every epoch (training.py:341-353), logged as
+    {"val/loss", "val/epoch"} at the current global_step. `config.save_adapters` (a bool, absent =
+    False; setattr or train.save_adapters in the YAML, not a TrainConfig field): in lora_audio mode,
+    wherever the merged checkpoint is written, io.save_adapter_checkpoint also writes
+    <output_dir>/adapter_epoch_{E}/ (adapters, optimizer moments, RNG states), after that epoch's
+    validation pass. `resume_from` (or config.resume_from / train.resume_from): such a directory, or
+    "auto" for the highest complete adapter_epoch_* of output_dir (none: start from scratch); the
+    run continues at epoch E + 1, bitwise as the uninterrupted run would. Resume is per epoch."""
     import os
 
     from . import io
     from .scheduler import RectifiedFlowScheduler
+    train_mode = getattr(config, "train_mode", "full")
+    save_adapters = bool(getattr(config, "save_adapters", False))
+    if resume_from is None:
+        resume_from = getattr(config, "resume_from", None)
+    if train_mode != "lora_audio" and (save_adapters or resume_from):
+        raise NotImplementedError(f"save_adapters / resume_from with train_mode={train_mode!r}: adapter "
+                                  f"checkpoints exist in lora_audio mode only (a full-mode checkpoint is the "
+                                  f"whole model already, and its sharded optimizer state is not saved)")
     device = device or model.device
     patchifier = model.patchifier or SymmetricPatchifier(1)
     if getattr(config, "gradient_checkpointing", False):
@@ -463,16 +480,38 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
         reducer = GradAllReduce(params, order=order).install(model)
     best = float("inf")
     global_step = 0
-    for epoch in range(config.num_epochs or 0):
+    first_epoch = 0
+    if resume_from == "auto":
+        resume_from = io.latest_adapter_checkpoint(config.output_dir)
+    if resume_from:
+        # after the optimizer and the reducer exist: values land in place, their pointers stay valid
+        st = io.load_adapter_checkpoint(model, resume_from, optimizer=optimizer, loader=dataloader)
+        global_step, best, first_epoch = st["global_step"], st["best_loss"], st["epoch"]
+    for epoch in range(first_epoch, config.num_epochs or 0):
         if hasattr(dataloader, "set_epoch"):
             dataloader.set_epoch(epoch)
         global_step, epoch_loss = train_one_epoch(model, dataloader, optimizer, rf, patchifier,
                                                   device, config, prompt_embeds,
                                                   prompt_attention_mask, epoch, global_step,
                                                   reducer, log_fn)
+        if val_dataloader is not None:
+            from .validation import validate_epoch
+            val_loss = validate_epoch(model, val_dataloader, rf, patchifier, config, prompt_embeds,
+                                      prompt_attention_mask, device)
+            if log_fn is not None:
+                log_fn({"val/loss": val_loss, "val/epoch": epoch}, global_step)
         if log_fn is not None:
             log_fn({"train/epoch_loss": epoch_loss}, global_step)
-        if config.output_dir and rank == 0 and (epoch + 1) % config.save_every_n_epochs == 0:
+        saving = config.output_dir and (epoch + 1) % config.save_every_n_epochs == 0
+        if saving and save_adapters:
+            # every rank calls (the RNG states are gathered), rank 0 writes; after the validation
+            # pass, so the device generator's state is the one the next epoch starts from
+            io.save_adapter_checkpoint(
+                model, os.path.join(config.output_dir, f"adapter_epoch_{epoch + 1}"), optimizer=optimizer,
+                train_state={"epoch": epoch + 1, "global_step": global_step, "best_loss": best},
+                loader=dataloader, metadata={"base_model_name_or_path": config.checkpoint_path,
+                                             "epoch": str(epoch + 1), "global_step": str(global_step)})
+        if saving and rank == 0:
             os.makedirs(config.output_dir, exist_ok=True)
             path = os.path.join(config.output_dir, f"model_epoch_{epoch + 1}.safetensors")
             meta = {"epoch": str(epoch + 1), "global_step": str(global_step),
