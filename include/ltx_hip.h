@@ -462,6 +462,24 @@ int ltx_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_s
 int ltx_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int64_t step, void* stream);
 
+/* ---- global gradient-norm clip over the ltx_adamw_multi chunk table (csrc/optim.hip) ------------ */
+/* part[b] (device f64, b < nchunks) = sum of squares of row b's gradient elements, each converted to
+ * f64 and squared exactly; fixed order (strided per-thread sums, the wave shuffle tree, four wave sums
+ * in order), no atomics. is_bf16 is the dtype of the table's tensors. A second dtype's launch is given
+ * part + the first's nchunks. */
+int ltx_grad_sumsq_multi(const int64_t* table, int64_t nchunks, int is_bf16, double* part, void* stream);
+/* One block adds part[0 .. nparts) in a fixed order (strided sums, then a fixed-shape tree) and writes
+ * the 16-byte device record at out (8-byte aligned): { f64 sumsq; f32 norm = (float)sqrt(sumsq);
+ * f32 coef = min(1, max_norm / (norm + 1e-6f)) in f32 (max_norm <= 0: coef = 1, the norm is still
+ * written) }. torch.nn.utils.clip_grad_norm_'s coefficient with error_if_nonfinite=False, on an f64
+ * norm. */
+int ltx_grad_clip_coef(const double* part, int64_t nparts, float max_norm, void* out, void* stream);
+/* ltx_adamw_multi on g' = R(g * *coef) in place of g (R: round to bf16 for bf16 tensors, identity for
+ * f32 -- what grad.mul_(coef) would leave); coef is read from device memory (the record's third
+ * field), the gradients themselves are not written. */
+int ltx_adamw_multi_clip(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int64_t step, const float* coef, void* stream);
+
 /* ---- train_mode='full' parameter gradients (csrc/paramgrad.hip) --------- */
 /* Weight gradient of the q/k RMSNorm weights: partials[(which * splits + s) * D + d] (f32) =
  * sum over row split s of bf16(dn * bf16(x_raw * rstd)), dn = RoPE^T of the incoming gradient (the

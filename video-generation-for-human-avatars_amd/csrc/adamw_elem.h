@@ -1,0 +1,65 @@
+// The per-element AdamW update shared by the optimizer kernels (elementwise.hip: ltx_adamw_step /
+// ltx_adamw_multi; optim.hip: ltx_adamw_multi_clip), so every entry point runs one arithmetic.
+#pragma once
+#include <cmath>
+
+#include "common.h"
+
+namespace ltx {
+
+// torch.lerp's two-sided form (ATen lerp: w < 0.5 ? self + w (end - self) : end - (end - self)(1 - w))
+__device__ __forceinline__ float torch_lerp(float self, float end, float w) {
+  const float d = end - self;
+  return fabsf(w) < 0.5f ? fmaf(w, d, self) : fmaf(-d, 1.0f - w, end);
+}
+
+// torch.optim.AdamW, foreach implementation order (weight decay, lerp m, v*b2 + (1-b2) g g,
+// sqrt, / sqrt(bc2), + eps, p += step_size * m / den), rounding every op for bf16 tensors.
+// CLIP: the gradient is first scaled by `coef` and rounded to its dtype, which is what an in-place
+// grad.mul_(coef) would leave in memory (the global-norm clip; grad itself is not written).
+template <bool BF16, bool CLIP = false>
+__device__ __forceinline__ void adamw_elem(void* __restrict__ param, const void* __restrict__ grad,
+                                           void* __restrict__ m_, void* __restrict__ v_, int64_t i, float decay,
+                                           float w1, float b2, float w2, float step_size, float bc2_sqrt, float eps,
+                                           float coef = 1.0f) {
+  float p, g, m, v;
+  if (BF16) {
+    p = bf2f(((bf16_t*)param)[i]); g = bf2f(((const bf16_t*)grad)[i]);
+    m = bf2f(((bf16_t*)m_)[i]); v = bf2f(((bf16_t*)v_)[i]);
+  } else {
+    p = ((float*)param)[i]; g = ((const float*)grad)[i]; m = ((float*)m_)[i]; v = ((float*)v_)[i];
+  }
+  auto R = [](float x) { return BF16 ? rbf(x) : x; };
+  if (CLIP) g = R(g * coef);
+  p = R(p * decay);
+  m = R(torch_lerp(m, g, w1));
+  v = R(v * b2);
+  v = R(v + w2 * g * g);
+  float den = R(sqrtf(v));
+  den = R(den / bc2_sqrt);
+  den = R(den + eps);
+  p = R(p + step_size * (m / den));
+  if (BF16) {
+    ((bf16_t*)param)[i] = f2bf(p); ((bf16_t*)m_)[i] = f2bf(m); ((bf16_t*)v_)[i] = f2bf(v);
+  } else {
+    ((float*)param)[i] = p; ((float*)m_)[i] = m; ((float*)v_)[i] = v;
+  }
+}
+
+// the host half: the step's scalars from the hyper-parameters, in double as torch computes them
+struct AdamWScalars {
+  float decay, w1, w2, step_size, bc2_sqrt;
+};
+static inline AdamWScalars adamw_scalars(float lr, float beta1, float beta2, float weight_decay, int64_t step) {
+  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+  AdamWScalars s;
+  s.decay = (float)(1.0 - (double)lr * (double)weight_decay);
+  s.step_size = (float)(-((double)lr / bc1));
+  s.bc2_sqrt = (float)std::sqrt(bc2);
+  s.w1 = (float)(1.0 - (double)beta1);
+  s.w2 = (float)(1.0 - (double)beta2);
+  return s;
+}
+
+}  // namespace ltx

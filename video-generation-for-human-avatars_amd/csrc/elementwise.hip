@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "adamw_elem.h"
 #include "common.h"
 #include "ltx_hip.h"
 
@@ -115,11 +116,8 @@ __global__ void coords_kernel(int64_t* __restrict__ coords, int B, int F, int H,
 // MODE 0: fused train-step prep (latents channel-major -> x_t, in, v)
 // MODE 1: conditioning lerp only (tokens already token-major: in = lerp(tokens, ...))
 // ---------------------------------------------------------------------------------------------
-// ATen lerp (Lerp.h) as compiled for CPU/GPU: the weight branch of each side contracts to an FMA
-__device__ __forceinline__ float torch_lerp(float self, float end, float w) {
-  const float d = end - self;
-  return fabsf(w) < 0.5f ? fmaf(w, d, self) : fmaf(-d, 1.0f - w, end);
-}
+// ATen lerp (Lerp.h) as compiled for CPU/GPU: torch_lerp in adamw_elem.h (the weight branch of each
+// side contracts to an FMA)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void prep_tokens_kernel(const bf16_t* __restrict__ lat,
@@ -448,35 +446,7 @@ __global__ __launch_bounds__(256) void mse_finish_kernel(float* __restrict__ sta
   if (c == 0 && lane == 0) stats[3] = 0.f;
 }
 
-// torch.optim.AdamW, foreach implementation order (weight decay, lerp m, v*b2 + (1-b2) g g,
-// sqrt, / sqrt(bc2), + eps, p += step_size * m / den), rounding every op for bf16 tensors.
-template <bool BF16>
-__device__ __forceinline__ void adamw_elem(void* __restrict__ param, const void* __restrict__ grad,
-                                           void* __restrict__ m_, void* __restrict__ v_, int64_t i, float decay,
-                                           float w1, float b2, float w2, float step_size, float bc2_sqrt, float eps) {
-  float p, g, m, v;
-  if (BF16) {
-    p = bf2f(((bf16_t*)param)[i]); g = bf2f(((const bf16_t*)grad)[i]);
-    m = bf2f(((bf16_t*)m_)[i]); v = bf2f(((bf16_t*)v_)[i]);
-  } else {
-    p = ((float*)param)[i]; g = ((const float*)grad)[i]; m = ((float*)m_)[i]; v = ((float*)v_)[i];
-  }
-  auto R = [](float x) { return BF16 ? rbf(x) : x; };
-  p = R(p * decay);
-  m = R(torch_lerp(m, g, w1));
-  v = R(v * b2);
-  v = R(v + w2 * g * g);
-  float den = R(sqrtf(v));
-  den = R(den / bc2_sqrt);
-  den = R(den + eps);
-  p = R(p + step_size * (m / den));
-  if (BF16) {
-    ((bf16_t*)param)[i] = f2bf(p); ((bf16_t*)m_)[i] = f2bf(m); ((bf16_t*)v_)[i] = f2bf(v);
-  } else {
-    ((float*)param)[i] = p; ((float*)m_)[i] = m; ((float*)v_)[i] = v;
-  }
-}
-
+// torch.optim.AdamW: the per-element update is adamw_elem (adamw_elem.h), shared with optim.hip
 template <bool BF16>
 __global__ void adamw_kernel(void* __restrict__ param, const void* __restrict__ grad, void* __restrict__ m_,
                              void* __restrict__ v_, int64_t n, float decay, float w1, float b2, float w2,
@@ -730,18 +700,13 @@ int ltx_mse_fwd_bwd(const void* out, const void* v, void* dout, float* stats, in
 int ltx_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int64_t step, void* stream) {
   LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi: bad args");
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  const float step_size = (float)(-((double)lr / bc1));
-  const float bc2_sqrt = (float)std::sqrt(bc2);
-  const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
   if (is_bf16)
     hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
-                       decay, w1, beta2, w2, step_size, bc2_sqrt, eps);
+                       a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps);
   else
     hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
-                       decay, w1, beta2, w2, step_size, bc2_sqrt, eps);
+                       a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
@@ -749,18 +714,13 @@ int ltx_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr
 int ltx_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int is_bf16,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   LTX_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "adamw: bad args");
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  const float step_size = (float)(-((double)lr / bc1));
-  const float bc2_sqrt = (float)std::sqrt(bc2);
-  const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
   if (is_bf16)
     hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                       exp_avg, exp_avg_sq, n, decay, w1, beta2, w2, step_size, bc2_sqrt, eps);
+                       exp_avg, exp_avg_sq, n, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps);
   else
     hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                       exp_avg, exp_avg_sq, n, decay, w1, beta2, w2, step_size, bc2_sqrt, eps);
+                       exp_avg, exp_avg_sq, n, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

@@ -1,0 +1,146 @@
+// Global gradient-norm clipping for the multi-tensor optimizer step (ltx_amd/training.py FusedAdamW with
+// max_grad_norm): the LoRA gradients are hundreds of separate tensors of two dtypes (f32 adapters and DoRA
+// magnitudes, the bf16 caption projection), so the norm walks the chunk table the AdamW launch already has --
+// rows of (param, grad, exp_avg, exp_avg_sq, first element, count <= 2048), one block per row -- instead of
+// one reduction per tensor:
+//   1. grad_sumsq_multi_kernel: block b -> part[b], the f64 sum of squares of its row's gradient elements
+//      (one launch per dtype, the second dtype's partials behind the first's);
+//   2. grad_clip_coef_kernel: one block adds all partials and writes the record {sumsq, norm, coef};
+//   3. adamw_multi_clip_kernel: adamw_multi_kernel on g' = R(g * coef), coef read from the record.
+// Every sum has a fixed order and there are no atomics, so the record is bitwise reproducible; nothing here
+// reads a value back to the host.
+#include <cmath>
+
+#include "adamw_elem.h"
+#include "common.h"
+#include "ltx_hip.h"
+
+namespace ltx {
+
+// the device record of ltx_grad_clip_coef (16 bytes; the host views it as one f64 and two f32)
+struct ClipRecord {
+  double sumsq;  // sum of squares of every gradient element, f64
+  float norm;    // (float)sqrt(sumsq): the pre-clip global norm
+  float coef;    // min(1, max_norm / (norm + 1e-6f)); 1 when max_norm <= 0
+};
+static_assert(sizeof(ClipRecord) == 16, "ClipRecord layout");
+
+// Every element converts to f64 and squares exactly (24- or 8-bit significands: the square has at most 48
+// bits). Order within the block, as sumsq_kernel (zero.hip): each thread adds its strided elements, the wave's
+// shuffle tree, then the four wave sums in order.
+template <bool BF16>
+__global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const int64_t* __restrict__ table,
+                                                               double* __restrict__ part) {
+  const int64_t* e = table + (int64_t)blockIdx.x * 6;
+  const void* grad = (const void*)e[1];
+  const int64_t start = e[4], end = e[4] + e[5];
+  double s = 0.0;
+  for (int64_t i = start + threadIdx.x; i < end; i += 256) {
+    const double v = BF16 ? (double)bf2f(((const bf16_t*)grad)[i]) : (double)((const float*)grad)[i];
+    s += v * v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// 256 threads add strided partials in a fixed order, then a fixed-shape tree (as sumsq_finish_kernel); the
+// coefficient is clip_coef_kernel's f32 arithmetic with inv_world = 1
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ part, int nparts,
+                                                             float max_norm, ClipRecord* __restrict__ out) {
+  double s = 0.0;
+  // eight strided loads in flight at a time, added in the strided order (a partial past the end reads as 0):
+  // one block walks ~10^4 partials, and with one load per add it took 11 us against 4.7 us this way
+  for (int64_t base = threadIdx.x; base < nparts; base += 8 * 256) {
+    double v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = base + k * 256;
+      v[k] = i < nparts ? part[i] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += v[k];
+  }
+  __shared__ double red[256];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double sumsq = red[0];
+    const float norm = (float)sqrt(sumsq);
+    float c = 1.0f;
+    if (max_norm > 0.f) {
+      const float cc = max_norm / (norm + 1e-6f);
+      if (cc < 1.0f) c = cc;
+    }
+    out->sumsq = sumsq;
+    out->norm = norm;
+    out->coef = c;
+  }
+}
+
+// adamw_multi_kernel (elementwise.hip) with the gradient scaled by *coef on the way in
+template <bool BF16>
+__global__ __launch_bounds__(256) void adamw_multi_clip_kernel(const int64_t* __restrict__ table, float decay,
+                                                               float w1, float b2, float w2, float step_size,
+                                                               float bc2_sqrt, float eps,
+                                                               const float* __restrict__ coef) {
+  const int64_t* e = table + (int64_t)blockIdx.x * 6;
+  void* param = (void*)e[0];
+  const void* grad = (const void*)e[1];
+  void* m = (void*)e[2];
+  void* v = (void*)e[3];
+  const int64_t start = e[4], end = e[4] + e[5];
+  const float c = *coef;
+  for (int64_t i = start + threadIdx.x; i < end; i += 256)
+    adamw_elem<BF16, true>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c);
+}
+
+}  // namespace ltx
+
+using namespace ltx;
+
+extern "C" {
+
+int ltx_grad_sumsq_multi(const int64_t* table, int64_t nchunks, int is_bf16, double* part, void* stream) {
+  LTX_CHECK_ARG(table && part && nchunks > 0 && nchunks < (1LL << 31), "grad_sumsq_multi: bad args");
+  if (is_bf16)
+    hipLaunchKernelGGL(grad_sumsq_multi_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
+                       table, part);
+  else
+    hipLaunchKernelGGL(grad_sumsq_multi_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
+                       table, part);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_grad_clip_coef(const double* part, int64_t nparts, float max_norm, void* out, void* stream) {
+  LTX_CHECK_ARG(part && out && nparts > 0 && nparts < (1LL << 31), "grad_clip_coef: bad args");
+  LTX_CHECK_ARG(((uintptr_t)out & 7) == 0, "grad_clip_coef: out must be 8-byte aligned");
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int)nparts, max_norm,
+                     (ClipRecord*)out);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_adamw_multi_clip(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int64_t step, const float* coef, void* stream) {
+  LTX_CHECK_ARG(table && coef && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_clip: bad args");
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
+  if (is_bf16)
+    hipLaunchKernelGGL(adamw_multi_clip_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
+                       table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef);
+  else
+    hipLaunchKernelGGL(adamw_multi_clip_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
+                       table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+}  // extern "C"

@@ -136,4 +136,17 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
         setattr(config, "save_adapters", bool(t["save_adapters"]))
     if "resume_from" in t:
         setattr(config, "resume_from", str(t["resume_from"]))
+    # and the optimizer-step keys training.schedule_from_config reads (and validates):
+    # `train.max_grad_norm` (a float, absent or 0 = no clipping): the global gradient-norm clip of the
+    # LoRA step; `train.lr_scheduler` ("constant", "constant_with_warmup", "linear" or "cosine", absent
+    # = "constant"), `train.lr_warmup_steps` (absent = 0) and `train.lr_total_steps` (absent = the
+    # optimizer steps of the run: num_epochs * (batches per epoch // gradient_accumulation_steps))
+    if "max_grad_norm" in t:
+        setattr(config, "max_grad_norm", float(t["max_grad_norm"]))
+    if "lr_scheduler" in t:
+        setattr(config, "lr_scheduler", str(t["lr_scheduler"]))
+    if "lr_warmup_steps" in t:
+        setattr(config, "lr_warmup_steps", int(t["lr_warmup_steps"]))
+    if "lr_total_steps" in t:
+        setattr(config, "lr_total_steps", int(t["lr_total_steps"]))
     return config

@@ -13,6 +13,7 @@ Differences that are deliberate and documented:
     quantile clamp takes the bounds as 0-dim device tensors instead of `float(t_low)`, which gives
     the same f32 result without the device->host round trip in every micro-step.
 """
+import ctypes
 import functools
 import math
 
@@ -103,22 +104,123 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
     return loss, rel_mse, nrmse, {"transformer_mse": mse, "_mse_f32": stats[0] / n}
 
 
+class LRSchedule:
+    """Learning rate as a pure function of the optimizer steps already taken: `at(s)` is
+    base_lr * factor(s), the factors those of transformers.get_scheduler (so with warm-up the first
+    step runs at lr 0, as it does there). With W = warmup_steps and T = total_steps:
+      s < W                             s / max(1, W)
+      constant, constant_with_warmup    1
+      linear                            max(0, (T - s) / max(1, T - W))
+      cosine                            max(0, 0.5 (1 + cos(pi (s - W) / max(1, T - W))))
+    in Python float arithmetic. Nothing is stored between steps, so a resumed run needs only its
+    global_step."""
+
+    NAMES = ("constant", "constant_with_warmup", "linear", "cosine")
+    DECAYING = ("linear", "cosine")
+
+    def __init__(self, name, base_lr, warmup_steps=0, total_steps=None):
+        if name not in self.NAMES:
+            raise ValueError(f"lr_scheduler {name!r} is not one of {', '.join(self.NAMES)}")
+        warmup_steps = int(warmup_steps)
+        if warmup_steps < 0:
+            raise ValueError(f"lr_warmup_steps must be >= 0, got {warmup_steps}")
+        if name in self.DECAYING:
+            if total_steps is None:
+                raise ValueError(f"lr_scheduler {name!r} decays over lr_total_steps, which is not set")
+            if int(total_steps) < 0:
+                raise ValueError(f"lr_total_steps must be >= 0, got {total_steps}")
+        self.name = name
+        self.base_lr = float(base_lr)
+        self.warmup_steps = warmup_steps
+        self.total_steps = None if total_steps is None else int(total_steps)
+
+    def factor(self, s):
+        W, T = self.warmup_steps, self.total_steps
+        if s < W:
+            return float(s) / float(max(1, W))
+        if self.name == "linear":
+            return max(0.0, float(T - s) / float(max(1, T - W)))
+        if self.name == "cosine":
+            progress = float(s - W) / float(max(1, T - W))
+            return max(0.0, 0.5 * (1.0 + math.cos(math.pi * progress)))
+        return 1.0
+
+    def at(self, s):
+        return self.base_lr * self.factor(s)
+
+
+def schedule_from_config(config, dataloader=None):
+    """(max_grad_norm or None, LRSchedule or None) from the optional config keys (setattr, or
+    train.<key> in the YAML; not TrainConfig fields): `max_grad_norm` (absent / 0: no clipping),
+    `lr_scheduler` (absent = "constant"), `lr_warmup_steps` (absent = 0), `lr_total_steps` (absent =
+    num_epochs * (len(dataloader) // gradient_accumulation_steps)). The schedule is None for a
+    constant rate without warm-up. ValueError for an unknown scheduler, a negative warm-up or norm,
+    and for a decaying schedule with neither lr_total_steps nor a sized loader."""
+    max_norm = getattr(config, "max_grad_norm", None)
+    if max_norm is not None:
+        max_norm = float(max_norm)
+        if not max_norm >= 0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {max_norm}")
+    name = getattr(config, "lr_scheduler", None) or "constant"
+    warmup = int(getattr(config, "lr_warmup_steps", 0) or 0)
+    total = getattr(config, "lr_total_steps", None)
+    if total is None and name in LRSchedule.DECAYING:
+        try:
+            per_epoch = len(dataloader)
+        except TypeError:
+            raise ValueError(f"lr_scheduler {name!r} needs lr_total_steps: the dataloader has no "
+                             f"length to derive it from") from None
+        accum = max(1, int(getattr(config, "gradient_accumulation_steps", 1)))
+        total = int(config.num_epochs or 0) * (per_epoch // accum)
+    schedule = LRSchedule(name, config.learning_rate or 0.0, warmup, total)
+    if name in ("constant", "constant_with_warmup") and warmup == 0:
+        schedule = None
+    return (max_norm or None), schedule
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW (defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2; the
     reference constructs AdamW(trainable, lr) at training.py:270-271) with one ltx_adamw_step
-    kernel per tensor; f32 LoRA adapters and bf16 caption-projection params keep their dtype."""
+    kernel per tensor; f32 LoRA adapters and bf16 caption-projection params keep their dtype.
+
+    `max_grad_norm` (None or 0: off, and step() is the unclipped path call for call): the global
+    gradient norm over every parameter group's parameters that have a gradient is clipped to it
+    (torch.nn.utils.clip_grad_norm_ with an f64 norm), on the device and without a host sync:
+    ltx_grad_sumsq_multi per (dtype, step) group over the chunk table, one ltx_grad_clip_coef, then
+    ltx_adamw_multi_clip per group, which scales the gradient on the way in -- .grad itself stays
+    unscaled. After such a step `grad_norm` (the pre-clip norm) and `clip_coef` are 0-dim f32 device
+    tensors; reading them syncs only at float()."""
 
     CHUNK = 2048  # elements per block of the multi-tensor kernel
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 multi_tensor=True):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+                 multi_tensor=True, max_grad_norm=None):
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      max_grad_norm=max_grad_norm))
         self.multi_tensor = multi_tensor
         self._tables = []  # pinned host tables of the last builds (alive until their H2D lands)
         self._table_cache = {}  # dtype -> (buffer pointers, device table, rows)
+        self._clip_part = None  # f64 per-row partial sums of the norm pass
+        # the last clipped step's device record: f64 sum of squares, f32 pre-clip norm, f32 coefficient
+        self.clip_sumsq = self.grad_norm = self.clip_coef = None
+
+    def _max_grad_norm(self):
+        vals = {float(g.get("max_grad_norm") or 0.0) for g in self.param_groups}
+        if len(vals) > 1:
+            raise ValueError(f"max_grad_norm differs between parameter groups ({sorted(vals)}): the "
+                             f"norm is global, so it takes one value")
+        v = vals.pop() if vals else 0.0
+        if v < 0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {v}")
+        return v
 
     @torch.no_grad()
     def step(self, closure=None):
+        max_norm = self._max_grad_norm()
+        if max_norm > 0:
+            return self._step_clipped(max_norm)
         for group in self.param_groups:
             b1, b2 = group["betas"]
             todo = []
@@ -145,31 +247,104 @@ class FusedAdamW(torch.optim.Optimizer):
                                    group["eps"], group["weight_decay"], st["step"])
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
-    def _multi(self, items, dtype, group, b1, b2, step):
-        """One ltx_adamw_multi launch for all tensors of a dtype (bitwise the per-tensor math).
-        The chunk table (~10^4 rows at LTX-2B: milliseconds of host time) is built once per set
-        of buffers and reused while the parameter / grad / state storages stay the same."""
+    def _table(self, items, dtype, slot=None):
+        """(device chunk table, rows) of `items`: int64 rows of (param, grad, exp_avg, exp_avg_sq,
+        first element, count <= CHUNK). The table (~10^4 rows at LTX-2B: milliseconds of host time)
+        is built once per set of buffers and reused while the parameter / grad / state storages
+        stay the same; `slot` is the cache entry (the dtype, for the one group the LoRA path has)."""
+        slot = dtype if slot is None else slot
         ptrs = [(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                  p.numel()) for p, g, st in items]
         key = (dtype, tuple(ptrs))
-        hit = self._table_cache.get(dtype)
+        hit = self._table_cache.get(slot)
         if hit is not None and hit[0] == key:
-            dev, nrows = hit[1], hit[2]
-        else:
-            rows = []
-            for pp, gp, ap, sp, n in ptrs:
-                for start in range(0, n, self.CHUNK):
-                    rows.append((pp, gp, ap, sp, start, min(self.CHUNK, n - start)))
-            host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-            dev = host.to(items[0][0].device, non_blocking=True)
-            nrows = len(rows)
-            # the pinned host copy stays alive until its H2D has landed (two steps later)
-            self._tables = (self._tables + [(host, dev)])[-2:]
-            self._table_cache[dtype] = (key, dev, nrows)
-        rows = range(nrows)
-        ops.call("ltx_adamw_multi", ops._p(dev), len(rows), 1 if dtype == torch.bfloat16 else 0,
+            return hit[1], hit[2]
+        rows = []
+        for pp, gp, ap, sp, n in ptrs:
+            for start in range(0, n, self.CHUNK):
+                rows.append((pp, gp, ap, sp, start, min(self.CHUNK, n - start)))
+        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+        dev = host.to(items[0][0].device, non_blocking=True)
+        nrows = len(rows)
+        # the pinned host copy stays alive until its H2D has landed (two steps later, and while
+        # the cache entry holds it)
+        self._tables = (self._tables + [(host, dev)])[-2:]
+        self._table_cache[slot] = (key, dev, nrows, host)
+        return dev, nrows
+
+    def _multi(self, items, dtype, group, b1, b2, step):
+        """One ltx_adamw_multi launch for all tensors of a dtype (bitwise the per-tensor math)."""
+        dev, nrows = self._table(items, dtype)
+        ops.call("ltx_adamw_multi", ops._p(dev), nrows, 1 if dtype == torch.bfloat16 else 0,
                  float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                  float(group["weight_decay"]), int(step), ops._s())
+
+    def _step_clipped(self, max_norm):
+        """The step under global-norm clipping: every parameter with a gradient goes through the
+        table kernels, grouped by (param group, dtype, step). Launch order: the norm launches of
+        all groups (each writes its per-row partials behind the previous group's), the coefficient
+        launch, then one ltx_adamw_multi_clip per group."""
+        from . import _lib
+        todo, device = [], None
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise _lib.LtxHipError(f"FusedAdamW(max_grad_norm): the clip kernels need ROCm device "
+                                           f"parameters, got one on {p.device}")
+                if p.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError(f"FusedAdamW(max_grad_norm): expected f32 or bf16 parameters, got {p.dtype}")
+                if device is None:
+                    device = p.device
+                elif p.device != device:
+                    raise ValueError(f"FusedAdamW(max_grad_norm): parameters on {device} and {p.device}; the "
+                                     f"global norm is taken on one device")
+        launches = []  # (device table, rows, is_bf16, group, step)
+        for gi, group in enumerate(self.param_groups):
+            buckets = {}  # (dtype, step) -> items, in order of first appearance
+            for p in group["params"]:
+                if p.grad is None or p.numel() == 0:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p)
+                    st["exp_avg_sq"] = torch.zeros_like(p)
+                st["step"] += 1
+                buckets.setdefault((p.dtype, st["step"]), []).append((p, p.grad.contiguous(), st))
+            seen = {}
+            for (dtype, step), items in buckets.items():
+                j = seen[dtype] = seen.get(dtype, -1) + 1
+                # the unclipped step's cache entry for the usual case: one group, one step count
+                slot = dtype if (gi, j) == (0, 0) else (dtype, gi, j)
+                dev, nrows = self._table(items, dtype, slot)
+                launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, group, step))
+        if not launches:
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            return
+        total = sum(n for _, n, _, _, _ in launches)
+        if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
+            self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
+        part = self._clip_part
+        # the record {f64 sumsq, f32 norm, f32 coef}: a fresh one per step, so a norm somebody
+        # holds keeps its value
+        rec = torch.empty(2, dtype=torch.float64, device=device)
+        tail = rec[1:].view(torch.float32)
+        stream = ops._s()
+        off = 0
+        for dev, nrows, is_bf16, _, _ in launches:
+            ops.call("ltx_grad_sumsq_multi", ops._p(dev), nrows, is_bf16,
+                     ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
+            off += nrows
+        ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
+        for dev, nrows, is_bf16, group, step in launches:
+            b1, b2 = group["betas"]
+            ops.call("ltx_adamw_multi_clip", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
+                     float(b2), float(group["eps"]), float(group["weight_decay"]), int(step),
+                     ops._p(tail[1]), stream)
+        self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
+        ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
 
 class OverlapHooks:
@@ -395,12 +570,18 @@ class GradAllReduce(OverlapHooks):
 
 def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device, config,
                     prompt_embeds, prompt_attention_mask, epoch, global_step, reducer=None,
-                    log_fn=None):
+                    log_fn=None, lr_schedule=None):
     """training.py:169-231: micro-steps with gradient accumulation, the optimizer step every
     `gradient_accumulation_steps` batches (after the DP gradient all-reduce when `reducer` is
     given), per-step logging of loss / rel_mse / nrmse / lr through `log_fn` (wandb.log in the
     reference). Returns (global_step, mean epoch loss). The loss values stay on the device until
-    an optimizer step logs them (one host sync per optimizer step, as the reference's .item())."""
+    an optimizer step logs them (one host sync per optimizer step, as the reference's .item()).
+
+    `lr_schedule` (an LRSchedule): every optimizer step runs at lr_schedule.at(global_step), the
+    steps taken before it, and "train/lr" is the rate that step used. An optimizer that clips
+    (FusedAdamW(max_grad_norm)) adds "train/grad_norm", the pre-clip global norm of the step's
+    gradients -- under data parallelism the averaged ones, the same on every rank -- read at the
+    same sync point as the loss."""
     model.train()
     accum = max(1, int(config.gradient_accumulation_steps))
 
@@ -421,6 +602,10 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
         if last:
             if reducer is not None:
                 reducer()
+            if lr_schedule is not None:
+                lr = lr_schedule.at(global_step)
+                for group in optimizer.param_groups:
+                    group["lr"] = lr
             optimizer.step()
             zero()
             global_step += 1
@@ -428,6 +613,8 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
                 payload = {"train/loss": float(loss), "train/rel_mse": float(rel_mse),
                            "train/nrmse": float(nrmse), "train/epoch": epoch,
                            "train/lr": optimizer.param_groups[0]["lr"]}
+                if getattr(optimizer, "grad_norm", None) is not None:
+                    payload["train/grad_norm"] = float(optimizer.grad_norm)
                 for k, v in (loss_dict or {}).items():
                     if not k.startswith("_"):
                         payload[f"train/{k}"] = float(v)
@@ -450,7 +637,12 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     <output_dir>/adapter_epoch_{E}/ (adapters, optimizer moments, RNG states), after that epoch's
     validation pass. `resume_from` (or config.resume_from / train.resume_from): such a directory, or
     "auto" for the highest complete adapter_epoch_* of output_dir (none: start from scratch); the
-    run continues at epoch E + 1, bitwise as the uninterrupted run would. Resume is per epoch."""
+    run continues at epoch E + 1, bitwise as the uninterrupted run would. Resume is per epoch.
+
+    The optimizer step's optional keys (schedule_from_config; absent = today's step, call for call):
+    `max_grad_norm` clips the global gradient norm inside FusedAdamW and logs "train/grad_norm";
+    `lr_scheduler` / `lr_warmup_steps` / `lr_total_steps` set every step's lr from global_step
+    (LRSchedule), so a resumed run continues the schedule with no saved state of its own."""
     import os
 
     from . import io
@@ -463,6 +655,8 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
         raise NotImplementedError(f"save_adapters / resume_from with train_mode={train_mode!r}: adapter "
                                   f"checkpoints exist in lora_audio mode only (a full-mode checkpoint is the "
                                   f"whole model already, and its sharded optimizer state is not saved)")
+    # the optional optimizer-step keys, validated before anything is built
+    max_grad_norm, lr_schedule = schedule_from_config(config, dataloader)
     device = device or model.device
     patchifier = model.patchifier or SymmetricPatchifier(1)
     if getattr(config, "gradient_checkpointing", False):
@@ -473,7 +667,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                 target_shift_terminal=config.rf_target_shift_terminal,
                                 sampler=config.rf_sampler, shift=config.rf_shift)
     params = [p for p in model.parameters() if p.requires_grad]
-    optimizer = FusedAdamW(params, lr=config.learning_rate)
+    optimizer =FusedAdamW(params, lr=config.learning_rate, max_grad_norm=max_grad_norm)
     reducer = None
     if dist.is_available() and dist.is_initialized():
         order = model.grad_ready_order() if hasattr(model, "grad_ready_order") else None
@@ -493,7 +687,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
         global_step, epoch_loss = train_one_epoch(model, dataloader, optimizer, rf, patchifier,
                                                   device, config, prompt_embeds,
                                                   prompt_attention_mask, epoch, global_step,
-                                                  reducer, log_fn)
+                                                  reducer, log_fn, lr_schedule)
         if val_dataloader is not None:
             from .validation import validate_epoch
             val_loss = validate_epoch(model, val_dataloader, rf, patchifier, config, prompt_embeds,
