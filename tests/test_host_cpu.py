@@ -616,3 +616,30 @@ def test_sample_timesteps_is_the_lognormal_draw_bitwise():
         t = raw / (1 + raw)
         b = t.clamp(min=float(torch.quantile(t, 0.01)), max=float(torch.quantile(t, 0.99)))
         assert torch.equal(a, b)
+
+
+def test_block_saved_tensors_come_back_by_name():
+    """_BlockFn's saved tensors go through _pack_saved / _unpack_saved: over the eight present / absent
+    combinations of the (attn2, attn1, ff) adapter groups, with x2 kept or not, and in full mode (no
+    adapters), every name comes back as the very tensor that went in, and the flat tuple handed to
+    save_for_backward holds each tensor once, in order."""
+    import itertools
+    from ltx_amd.transformer3d import _pack_saved, _unpack_saved
+    sizes = {"base": 24, "attn2": 12, "full": 3, "attn1": 11, "ff": 7}
+    cases = [(a2, a1, ff, x2, False) for a2, a1, ff, x2 in itertools.product((False, True), repeat=4)]
+    cases.append((False, False, False, False, True))
+    for a2, a1, ff, keep_x2, full in cases:
+        have = {"base": True, "attn2": a2, "full": full, "attn1": a1, "ff": ff}
+        # (a group may hold None: u_k / u_v with the text stack)
+        groups = {k: tuple(None if (k == "attn2" and i == 9) else torch.zeros(1) for i in range(n)) if have[k] else ()
+                  for k, n in sizes.items()}
+        x2 = torch.zeros(1) if keep_x2 else None
+        flat, layout = _pack_saved(groups["base"], attn2=groups["attn2"], full=groups["full"],
+                                   attn1=groups["attn1"], ff=groups["ff"], x2=x2)
+        want = [t for k in sizes for t in groups[k]] + ([x2] if keep_x2 else [])
+        assert len(flat) == len(want) and all(a is b for a, b in zip(flat, want))
+        sv = _unpack_saved(flat, layout)
+        for k in sizes:
+            got = getattr(sv, k)
+            assert len(got) == len(groups[k]) and all(a is b for a, b in zip(got, groups[k])), (k, a2, a1, ff)
+        assert sv.x2 is x2

@@ -113,7 +113,7 @@ def test_ff_only_is_legal_at_the_inject_level():
 @pytest.mark.parametrize("half", FF)
 def test_half_wrapped_ff_raises_before_anything_is_replaced(half):
     from ltx_amd.lora import inject_lora, lora_target_modules
-    from ltx_amd.transformer3d import LoraLinear, _lora_abf, _lora_params_ff
+    from ltx_amd.transformer3d import LoraLinear, _block_ab as _lora_abf, _lora_params_ff
     m = _bare()
     with pytest.raises(NotImplementedError, match="both linears.*ff"):
         inject_lora(m, lora_target_modules(2, "attn2") + ff_names(1) + [f"transformer_blocks.1.ff.{half}"], 8, 8,

@@ -1,0 +1,252 @@
+"""Fingerprint of one step per model configuration, to hold a refactor of the fused block to equality.
+
+    python tools/step_fingerprint.py run --pkg <dir that holds ltx_amd/> --group <name> --out fp.json
+    python tools/step_fingerprint.py compare old.json new.json [--md table.md]
+
+`run` imports ltx_amd from --pkg (another commit's Python sources beside the same built library:
+set LTX_HIP_LIB to the library) in a fresh process, sets the group's environment switches before the
+import (several are read at import), and for every configuration of the group runs one step under
+ops.LaunchTimer. It writes the ordered kernel names, SHA-256 of the loss, of the model output and of
+every gradient of grads_by_canonical, and torch.cuda.max_memory_allocated() of the step. Training
+steps here are bitwise reproducible (fixed-order sums), so two commits that compute the same thing
+give identical files. `compare` merges the per-group files of two commits into one verdict per
+configuration: identical kernel lists and hashes, and a peak no higher than the old one.
+
+The models come from the test helpers (tests/model_utils.py, lora_attn1_utils.py, lora_ff_utils.py,
+lora_dora_utils.py); the tiny configurations use the inputs of tests/golden/tiny_lora_ff_step.
+"""
+import argparse
+import gc
+import hashlib
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(REPO, "tests", "golden")
+R_TINY, R_2B = 8, 16
+
+TINY = ["fwd", "fwd_AttentionSkip", "fwd_AttentionValues", "fwd_Residual", "fwd_TransformerBlock",
+        "attn2_shared", "attn2_per_sample", "attn1", "attn1+attn2", "attn2+ff", "all3", "all3_dropout",
+        "dora_shared", "dora_per_sample", "full", "all3_ckpt"]
+# group -> (environment set before the import, configurations)
+GROUPS = {
+    "tiny": ({}, TINY),
+    "text_batch0": ({"LTX_TEXT_BATCH": "0"}, ["attn2_shared"]),
+    "qkv_grouped0": ({"LTX_LORA_QKV_GROUPED": "0"}, ["all3"]),
+    "ff_keep_x2_0": ({"LTX_LORA_FF_KEEP_X2": "0"}, ["all3"]),
+    "ff_dy_da1": ({"LTX_LORA_FF_DY_DA": "1"}, ["all3"]),
+    "delta_fused0": ({"LTX_DELTA_FUSED": "0"}, ["all3"]),
+    "lora_dy0": ({"LTX_LORA_DY": "0"}, ["all3"]),
+    # one LTX-2B-width block, B = 8, N = 1024 (M = 8192: past the token-sized gates), r = 16, 256 text tokens
+    "2b": ({}, ["2b_all3", "2b_dora"]),
+}
+
+
+def _sha(t):
+    import torch
+    t = t.detach().contiguous().cpu().reshape(-1)
+    return hashlib.sha256(t.view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def _tiny_case():
+    from safetensors.torch import load_file
+    from lora_ff_utils import ff_params
+    with open(os.path.join(GOLD, "tiny_lora_ff_step.json")) as f:
+        meta = json.load(f)
+    raw = load_file(os.path.join(GOLD, "tiny_lora_ff_step.safetensors"))
+    d = {k: v.cuda() for k, v in raw.items() if k.startswith("in.") or k in ("out.t", "out.noise")}
+    d["out.noise"] = d["out.noise"].bfloat16()
+    cfg = meta["config"]
+    return cfg, ff_params(cfg, meta["param_seed"], R_TINY, targets=("attn1", "attn2")), d
+
+
+def _2b_case():
+    from lora_ff_utils import ff_params
+    from ltx_amd.transformer3d import OURS_TRANSFORMER_CONFIG
+    from model_utils import synth_inputs
+    cfg = dict(OURS_TRANSFORMER_CONFIG, num_layers=1)
+    return cfg, ff_params(cfg, 300 + R_2B, R_2B, targets=("attn1", "attn2")), synth_inputs(8, 4, 16, 16, 256, 16, seed=33)
+
+
+def _per_sample(d):
+    B = d["in.latents"].shape[0]
+    return dict(d, **{"in.prompt_embeds": d["in.prompt_embeds"].repeat(B, 1, 1),
+                      "in.prompt_attention_mask": d["in.prompt_attention_mask"].repeat(B, 1)})
+
+
+def _build(name, cfg, params, r):
+    """The model of a configuration, through the tests' builders."""
+    from lora_attn1_utils import build_targets_model
+    from lora_dora_utils import build_dora_model
+    from lora_ff_utils import build_ff_model, train_config
+    from model_utils import build_full_model, build_model
+    name = name[3:] if name.startswith("2b_") else name
+    if name.startswith("fwd"):
+        return build_model(cfg, params, 0)
+    if name.startswith("attn2_"):
+        return build_model(cfg, params, r)
+    if name in ("attn1", "attn1+attn2"):
+        return build_targets_model(cfg, params, r, name)
+    if name == "attn2+ff":
+        return build_ff_model(cfg, params, r, "attn2")
+    if name in ("all3", "all3_ckpt"):
+        return build_ff_model(cfg, params, r, "attn1+attn2")
+    if name == "all3_dropout":
+        import torch
+        from ltx_amd.lora import apply_training_strategy
+        from ltx_amd.patchifier import SymmetricPatchifier
+        from ltx_amd.transformer3d import Transformer3DModel
+        from params import canonical_name
+        tc = train_config(r, "attn1+attn2", True)
+        setattr(tc, "lora_dropout", 0.1)
+        with torch.device("meta"):
+            m = Transformer3DModel.from_config(cfg)
+            apply_training_strategy(m, tc, "lora_audio")
+        m.load_state_dict({n: params[canonical_name(n)].detach().cuda().clone() for n, _ in m.named_parameters()},
+                          assign=True, strict=True)
+        for n, q in m.named_parameters():
+            q.requires_grad_(("lora_" in n) or ("caption_projection" in n))
+        m.patchifier = SymmetricPatchifier(1)
+        m.lora_dropout_key = 0x5EED5EED
+        return m
+    if name.startswith("dora"):
+        return build_dora_model(cfg, params, r)
+    if name == "full":
+        return build_full_model(cfg, params)
+    raise KeyError(name)
+
+
+def _forward_only(model, d, strategy, torch):
+    import ltx_oracle as O
+    B = d["in.latents"].shape[0]
+    tok, coords = O.patchify(d["in.latents"].bfloat16())
+    x = O.add_noise(tok, d["out.noise"], d["out.t"]).bfloat16()
+    nl = len(model.transformer_blocks)
+    skip = (torch.arange(nl * B, device="cuda").view(nl, B) % 2).float() if strategy else None
+    model.eval()
+    with torch.no_grad():
+        return model(hidden_states=x, indices_grid=coords.cuda(),
+                     ref_image_hidden_states=d["in.ref_image_latents"].bfloat16(),
+                     pose_hidden_states=d["in.pose_latents"].bfloat16(),
+                     encoder_hidden_states=d["in.prompt_embeds"].bfloat16().expand(B, -1, -1), timestep=d["out.t"],
+                     encoder_attention_mask=d["in.prompt_attention_mask"].expand(B, -1), skip_layer_mask=skip,
+                     skip_layer_strategy=strategy or None).sample
+
+
+def _one(name, case, torch):
+    from ltx_amd import ops
+    from model_utils import build_step, grads_by_canonical
+    cfg, params, d = case
+    model = _build(name, cfg, params, R_2B if name.startswith("2b_") else R_TINY)
+    if name.endswith("per_sample"):
+        d = _per_sample(d)
+    outs = []
+    if not name.startswith("fwd"):
+        model.train()
+        model.gradient_checkpointing = name.endswith("_ckpt")
+        inner = model._forward_tokens
+        model._forward_tokens = lambda *a, **k: (outs.append(inner(*a, **k)), outs[-1])[1]
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    timer = ops.LaunchTimer()
+    ops.set_launch_timer(timer)
+    try:
+        if name.startswith("fwd"):
+            outs.append(_forward_only(model, d, name[4:], torch))
+            loss = None
+        else:
+            loss = build_step(model, d)
+    finally:
+        ops.set_launch_timer(None)
+    torch.cuda.synchronize()
+    rec = {"kernels": [r[0] for r in timer.records], "peak_bytes": torch.cuda.max_memory_allocated(),
+           "output": _sha(outs[0]), "loss": None if loss is None else _sha(torch.tensor(loss, dtype=torch.float64)),
+           "grads": {}}
+    if loss is not None:
+        for k, g in sorted(grads_by_canonical(model).items()):
+            rec["grads"][k] = None if g is None else _sha(g)
+    return rec
+
+
+def run(args):
+    env, names = GROUPS[args.group]
+    os.environ.update(env)
+    for p in (os.path.abspath(args.pkg), os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
+        sys.path.insert(0, p)
+    import torch
+    import ltx_amd
+    from ltx_amd import _lib
+    _lib.ensure_device("cuda:0")
+    torch.cuda.set_device(0)
+    case = _2b_case() if args.group == "2b" else _tiny_case()
+    out = {"pkg": os.path.dirname(os.path.abspath(ltx_amd.__file__)), "env": env, "configs": {}}
+    for name in names:
+        out["configs"][f"{args.group}/{name}"] = _one(name, case, torch)
+        gc.collect()
+        torch.cuda.empty_cache()
+        print(f"{args.group}/{name}: {len(out['configs'][f'{args.group}/{name}']['kernels'])} launches", flush=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+def _load(paths):
+    cfgs = {}
+    for p in paths:
+        with open(p) as f:
+            cfgs.update(json.load(f)["configs"])
+    return cfgs
+
+
+def compare(args):
+    old, new = _load(args.old.split(",")), _load(args.new.split(","))
+    rows, bad = [], 0
+    for name in sorted(set(old) | set(new)):
+        a, b = old.get(name), new.get(name)
+        if a is None or b is None:
+            rows.append((name, "-", "-", "-", "-", "-", "-", "MISSING"))
+            bad += 1
+            continue
+        why = []
+        if a["kernels"] != b["kernels"]:
+            why.append("kernel list differs")
+        if (a["output"], a["loss"]) != (b["output"], b["loss"]):
+            why.append("output / loss differs")
+        diff = [k for k in set(a["grads"]) | set(b["grads"]) if a["grads"].get(k, 0) != b["grads"].get(k, 1)]
+        if diff:
+            why.append(f"{len(diff)} gradients differ")
+        if b["peak_bytes"] > a["peak_bytes"]:
+            why.append("peak above the old one")
+        bad += bool(why)
+        n = lambda c: len(c["grads"]) + 1 + (c["loss"] is not None)  # noqa: E731
+        rows.append((name, len(a["kernels"]), len(b["kernels"]), n(a), n(b), a["peak_bytes"], b["peak_bytes"],
+                     "identical" if not why else "; ".join(why)))
+    head = ("configuration", "launches old", "launches new", "tensors old", "tensors new", "peak bytes old",
+            "peak bytes new", "verdict")
+    lines = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
+    lines += ["| " + " | ".join(str(c) for c in r) + " |" for r in rows]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.md:
+        with open(args.md, "w") as f:
+            f.write(text)
+    sys.exit(1 if bad else 0)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    r = sub.add_parser("run")
+    r.add_argument("--pkg", default=os.path.join(REPO, "video-generation-for-human-avatars_amd"))
+    r.add_argument("--group", required=True, choices=sorted(GROUPS))
+    r.add_argument("--out", required=True)
+    c = sub.add_parser("compare")
+    c.add_argument("old", help="comma-separated fingerprint files of the old commit")
+    c.add_argument("new", help="... of the new commit")
+    c.add_argument("--md")
+    args = ap.parse_args()
+    run(args) if args.cmd == "run" else compare(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -20,7 +20,7 @@ import os
 from dataclasses import dataclass
 from enum import Enum, auto
 from pathlib import Path
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -170,50 +170,44 @@ class LoraLinear(nn.Module):
             self._dora_cache = hit
         return hit[1]
 
-    def weight_split(self, which):
-        """Cached K-extension weight operands (3-term bf16 split, ltx_lora_split_bf16):
-        'B' -> s*B for the forward GEMM, 'A' -> A^T for the input-gradient GEMM. Rebuilt when
-        the adapter changes: new storage, an in-place torch update (version counter) or a
-        FusedAdamW step (ops.weight_generation()). Under DoRA 'B' is the split of c (.) s B
-        (dora_operands), rebuilt with it."""
-        p = _ab(self)[1 if which == "B" else 0]
-        key = (p.data_ptr(), p._version, ops.weight_generation())
-        dora = self.use_dora and which == "B"
+    def _operand(self, kind, which, of_b):
+        """The keyed cache behind weight_split / weight_pieces: the 'split' or 'pieces' operand of lora_B
+        (of_b) or lora_A. Rebuilt when the adapter changes: new storage, an in-place torch update
+        (version counter) or a FusedAdamW step (ops.weight_generation()). Under DoRA the operands of B
+        are those of c (.) s B (dora_operands), rebuilt with it."""
+        p = _ab(self)[1 if of_b else 0]
+        dora = self.use_dora and of_b
         if dora:
             dop = self.dora_operands()
             key = id(dop)  # the dict is replaced when an operand changes, and held below
-        hit = self._split_cache.get(which)
+        else:
+            key = (p.data_ptr(), p._version, ops.weight_generation())
+        name = which if kind == "split" else "pieces_" + which
+        hit = self._split_cache.get(name)
         if hit is None or hit[0] != key:
             with torch.no_grad():
-                if dora:
-                    t = (ops.lora_split(dop["sB"], "weight", 1.0), dop)
+                src, scale = (dop["sB"], 1.0) if dora else (p, self.scaling)
+                if kind == "pieces":
+                    t = ops.lora_pieces(src, transposed=of_b)
+                elif of_b:
+                    t = ops.lora_split(src, "weight", scale)
                 else:
-                    t = (ops.lora_split(p, "weight", self.scaling) if which == "B"
-                         else ops.lora_split(p, "weight", transposed=True))
-            hit = (key, t)
-            self._split_cache[which] = hit
+                    t = ops.lora_split(p, "weight", transposed=True)
+            hit = (key, (t, dop) if dora else t)
+            self._split_cache[name] = hit
         return hit[1][0] if dora else hit[1]
+
+    def weight_split(self, which):
+        """Cached K-extension weight operands (3-term bf16 split, ltx_lora_split_bf16):
+        'B' -> s*B for the forward GEMM, 'A' -> A^T for the input-gradient GEMM. Under DoRA 'B' is
+        the split of c (.) s B."""
+        return self._operand("split", which, which == "B")
 
     def weight_pieces(self, which):
         """Cached bf16 pieces (ops.lora_pieces) of 'A' (lora_A) or 'Bt' (lora_B^T): the weight
         operand of the token-sized adapter contractions (ltx_lora_rows); same keys as
         weight_split. Under DoRA 'Bt' holds the pieces of (c (.) s B)^T: its callers pass alpha 1."""
-        p = _ab(self)[1 if which == "Bt" else 0]
-        key = (p.data_ptr(), p._version, ops.weight_generation())
-        dora = self.use_dora and which == "Bt"
-        if dora:
-            dop = self.dora_operands()
-            key = id(dop)
-        hit = self._split_cache.get("pieces_" + which)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                if dora:
-                    t = (ops.lora_pieces(dop["sB"], transposed=True), dop)
-                else:
-                    t = ops.lora_pieces(p, transposed=(which == "Bt"))
-            hit = (key, t)
-            self._split_cache["pieces_" + which] = hit
-        return hit[1][0] if dora else hit[1]
+        return self._operand("pieces", which, which == "Bt")
 
     @property
     def weight(self):
@@ -584,6 +578,89 @@ def _lora_backward(dy, u, lin, Bw, x, r, s, w_out=None, split_out=None, merge_da
     return w, sw
 
 
+def _lora_gemm(x, w, b, lin, A, dp, slot, **kw):
+    """One projection of the block with its adapter: (y, u) of y = gemm(x, w, bias=b, **kw), and with
+    an adapter (lin its LoraLinear, A its lora_A; else u = None) peft LoRA fused into the K loop:
+    [x | split(u)] . [w | split(s B)]^T with u = x . A^T, or c xd . A^T on the adapter's own masked
+    input under LoRA dropout (dp, slot)."""
+    if lin is None:
+        return ops.gemm(x, w, bias=b, **kw), None
+    u, su = ops.lora_down(x if dp is None else _drop_x(x, dp, slot), A, alpha=1.0 if dp is None else dp[2],
+                          split=True, pieces=lambda: lin.weight_pieces("A"))
+    return ops.gemm(x, w, bias=b, ext=(su, lin.weight_split("B")), **kw), u
+
+
+def _lora_dgrad(dy, wT, lin, A, Bw, u, x, r, s, dp, slot, epi=None, g=None, merge_da=True, dora=False, **kw):
+    """The backward of one _lora_gemm projection: the adapter's dB / dA into .grad (_lora_backward) and
+    dx = gemm(dy, wT, **kw). Without dropout w = s dY B rides the GEMM's K extension with A's split, and
+    the GEMM also takes the caller's epilogue `epi` (the row-dot or gated keywords). Under LoRA dropout
+    (dp, slot) dA = c w^T xd on the regenerated xd, the GEMM runs without the extension and without
+    `epi`, and the masked term c keep (w . A) is added afterwards (_masked_add, times the kept GELU
+    derivative g at ff.net.2). x may be a function that makes it: such an x is released again before the
+    GEMM, as xd is."""
+    if epi is None:
+        epi = {}
+    if lin is None:
+        return ops.gemm(dy, wT, **kw, **epi)
+    if callable(x):
+        x = x()
+    if dp is None:
+        _, sw = _lora_backward(dy, u, lin, Bw, x, r, s, merge_da=merge_da, dora=dora)
+        del x
+        return ops.gemm(dy, wT, ext=(sw, lin.weight_split("A")), **kw, **epi)
+    xd = _drop_x(x, dp, slot)
+    del x
+    w, _ = _lora_backward(dy, u, lin, Bw, xd, r, s, merge_da=merge_da, da_alpha=dp[2])
+    del xd
+    dx = ops.gemm(dy, wT, **kw)
+    _masked_add(dx, w, [A], dp, (slot,), g=g)
+    return dx
+
+
+def _text_kv_lora_backward(blk, dkv, dys, ys, us, lins, ab, enc2, wT, r, s, dp=None, dora=False):
+    """The to_k / to_v adapters' backward on the per-block text path and the encoder gradient
+    denc = dK_raw . W_k + dV . W_v + both adapters' input-gradient terms: per adapter dB, w = s dY B and
+    dA = w^T enc2 into .grad, then one GEMM over dkv = [dK_raw | dV] with the two w's splits as its K
+    extension. ab = (A_k, B_k, A_v, B_v); dys / ys / us / lins the (k, v) pairs of dY, the projection's
+    output, u and the LoraLinear.
+    dp (LoRA dropout; per-sample text rows, slots 5 and 6): dA = c w^T xd on the masked text rows, the
+    w's stay f32 side by side (no split), the GEMM runs plain and the masked terms follow (_masked_add).
+    dora: the kernels run on B_eff = c (.) s B with alpha 1 and dB goes through a scratch
+    (ops.dora_rowscale_add, as _lora_backward), and each magnitude gradient follows its adapter."""
+    rows, dev = dkv.shape[0], dkv.device
+    if dp is not None:
+        w_kv = torch.empty(rows, 2 * r, dtype=torch.float32, device=dev)
+    else:
+        K2 = ops.lora_k2(r)
+        swkv = torch.empty(rows, 2 * K2, dtype=torch.bfloat16, device=dev)
+    for i, (dy, y, u, lt, Bw) in enumerate(zip(dys, ys, us, lins, ab[1::2])):
+        sa = s
+        if dora:
+            dop = lt.dora_operands()
+            dB = ops.lora_wgrad(dy, u)
+            ops.dora_rowscale_add(_grad_buf(lt, "B"), dB, dop["c"], s)
+            Bw, sa = dop["sB"], 1.0
+        else:
+            ops.lora_wgrad(dy, u, alpha=s, out=_grad_buf(lt, "B"), accumulate=True)
+        if dp is not None:
+            w = w_kv[:, i * r:(i + 1) * r]
+            ops.lora_down(dy, Bw, alpha=sa, transposed=True, out=w)
+            x, ca = _drop_x(enc2, dp, 5 + i), dp[2]
+        else:
+            w, _ = ops.lora_down(dy, Bw, alpha=sa, transposed=True, split=True,
+                                 split_out=swkv[:, i * K2:(i + 1) * K2])
+            x, ca = enc2, 1.0
+        ops.lora_wgrad(x, w, alpha=ca, transpose_out=True, out=_grad_buf(lt, "A"), accumulate=True)
+        del x
+        if dora:
+            ops.dora_mag_grad(dy, y, _lin(lt)[1], _dora_m(lt), _grad_buf(lt, "m"))
+    if dp is not None:
+        denc = ops.gemm(dkv, wT)
+        _masked_add(denc, w_kv, [ab[0], ab[2]], dp, (5, 6))
+        return denc
+    return ops.gemm(dkv, wT, ext=(swkv, _kv_ext(blk, lins[0], lins[1])[1]))
+
+
 def _qkv_lora_backward(dqkv, u, lora1, ab1, x1, r, s):
     """dB / dA of the q / k / v adapters into .grad from the packed dQKV [M, 3D]; returns the
     [M, 3 K2] split operand of w_g = s dY_g B_g, the K extension of dx1 = dQKV . Wqkv^T."""
@@ -695,13 +772,19 @@ def _base(m):
     return m._modules["base_layer"] if type(m) is LoraLinear else m
 
 
+def _wb(m):
+    """(weight, bias) of an nn.Linear, or of the one under a LoraLinear, by direct lookup (as _frozen)."""
+    p = _base(m)._parameters
+    return p["weight"], p["bias"]
+
+
 def _lora_params(blk, attn="attn2"):
     """The LoraLinear of an attention's four projections in _LORA_KEYS order, or None (no adapters)."""
     a2 = blk._modules[attn]._modules
     lins = (a2["to_q"], a2["to_k"], a2["to_v"], a2["to_out"]._modules["0"])
-    kinds = [type(m) is LoraLinear for m in lins]
-    if not all(kinds):
-        if any(kinds):
+    n = sum([type(m) is LoraLinear for m in lins])
+    if n != 4:
+        if n:
             raise NotImplementedError(f"LoRA must wrap all four {attn} projections (training.py:52-60)")
         return None
     return lins
@@ -721,9 +804,9 @@ def _lora_params_ff(blk):
     None (no adapters). Both or none, and one rank and scaling for the two."""
     net = blk._modules["ff"]._modules["net"]._modules
     lins = (net["0"]._modules["proj"], net["2"])
-    kinds = [type(m) is LoraLinear for m in lins]
-    if not all(kinds):
-        if any(kinds):
+    n = (type(lins[0]) is LoraLinear) + (type(lins[1]) is LoraLinear)
+    if n != 2:
+        if n:
             raise NotImplementedError("LoRA must wrap both feed-forward linears (ff.net.0.proj, ff.net.2) or none")
         return None
     if lins[0].r != lins[1].r or lins[0].scaling != lins[1].scaling:
@@ -766,6 +849,81 @@ def _grad_buf(lin, which):
     return p.grad
 
 
+class _BlockLora(NamedTuple):
+    """One block's adapters, as _BlockFn's forward and backward read them: per group the LoraLinear
+    tuple (None: the group has no adapters) with its rank and scaling, and the DoRA flag."""
+    attn2: Optional[tuple]  # to_q, to_k, to_v, to_out.0 (_LORA_KEYS order)
+    attn1: Optional[tuple]
+    ff: Optional[tuple]  # ff.net.0.proj, ff.net.2
+    r: int  # attn2's rank and scaling
+    s: float
+    r1: int
+    s1: float
+    rf: int
+    sf: float
+    # DoRA on attn2 (DESIGN.md "DoRA (use_dora)"; _block_dora has checked the block in blk.weights())
+    dora: bool
+
+    @property
+    def n_ab(self):
+        """how many adapter tensors the block hands to _BlockFn.apply (_block_ab)"""
+        return 8 * (self.attn2 is not None) + 8 * (self.attn1 is not None) + 4 * (self.ff is not None)
+
+    def split(self, flat):
+        """_BlockFn's flat adapter arguments (_block_ab) as (attn2's 8, attn1's 8, the feed-forward's 4),
+        () for an absent group."""
+        n2 = 8 * (self.attn2 is not None)
+        n1 = n2 + 8 * (self.attn1 is not None)
+        if len(flat) != n1 + 4 * (self.ff is not None):
+            raise ValueError(f"the block's adapters take {self.n_ab} tensors (_block_ab), got {len(flat)}")
+        return flat[:n2], flat[n2:n1], flat[n1:]
+
+
+def _block_lora(blk):
+    """The _BlockLora of a block, with the groups' own checks (_lora_params, _lora_params1,
+    _lora_params_ff; direct _modules lookups, as _frozen)."""
+    lora, lora1, loraf = _lora_params(blk), _lora_params1(blk), _lora_params_ff(blk)
+    r, s = (0, 1.0) if lora is None else (lora[0].r, lora[0].scaling)
+    r1, s1 = (0, 1.0) if lora1 is None else (lora1[0].r, lora1[0].scaling)
+    rf, sf = (0, 1.0) if loraf is None else (loraf[0].r, loraf[0].scaling)
+    return _BlockLora(lora, lora1, loraf, r, s, r1, s1, rf, sf, lora is not None and lora[0].use_dora)
+
+
+def _block_ab(blk):
+    """The block's adapter weights as _BlockFn.apply's trailing arguments: attn2's [A_q, B_q, A_k, B_k,
+    A_v, B_v, A_o, B_o], then attn1's eight, then the feed-forward's [A_1, B_1, A_2, B_2] of
+    ff.net.0.proj and ff.net.2; an absent group adds nothing."""
+    groups = (_lora_params(blk), _lora_params1(blk), _lora_params_ff(blk))
+    return [t for g in groups if g is not None for m in g for t in _ab(m)]
+
+
+class _Saved(NamedTuple):
+    """_BlockFn's saved tensors by group (_pack_saved / _unpack_saved)."""
+    base: tuple  # h ... fpre: what every block keeps
+    attn2: tuple  # A_q ... B_o, u_q, u_k, u_v, u_o
+    full: tuple  # x1, y1, y3 (train_mode='full')
+    attn1: tuple  # attn1's A_q ... B_o, u1, u_o1, x1
+    ff: tuple  # A_1, B_1, A_2, B_2, u_f1, u_f2, act
+    x2: Optional[torch.Tensor]  # the feed-forward adapters' x2 unless LTX_LORA_FF_KEEP_X2=0
+
+
+def _pack_saved(base, attn2=(), full=(), attn1=(), ff=(), x2=None):
+    """(the flat tuple for ctx.save_for_backward, its layout for _unpack_saved); a group the block
+    does not have stays ()."""
+    x2 = () if x2 is None else (x2,)
+    return ((*base, *attn2, *full, *attn1, *ff, *x2),
+            (len(base), len(attn2), len(full), len(attn1), len(ff), len(x2)))
+
+
+def _unpack_saved(flat, layout):
+    """ctx.saved_tensors back as the named groups of _pack_saved."""
+    groups, i = [], 0
+    for n in layout:
+        groups.append(flat[i:i + n])
+        i += n
+    return _Saved(*groups[:5], groups[5][0] if groups[5] else None)
+
+
 class _BlockFn(torch.autograd.Function):
     """One BasicTransformerBlock.forward (attention.py:198-321) + its backward."""
 
@@ -779,47 +937,34 @@ class _BlockFn(torch.autograd.Function):
         if skip is not None and keep:
             raise NotImplementedError("skip-layer masks are an inference (forward-only) feature")
         W = blk.weights()
-        a1, a2, ff = blk.attn1, blk.attn2, blk.ff
+        a1, a2 = blk.attn1, blk.attn2
         ldm = mods.stride(0)
-        # lora_ab = the attn2 adapters' 8 tensors (_lora_ab), then the attn1 adapters' 8 (_lora_ab1),
-        # then the feed-forward adapters' 4 (_lora_abf): A1, B1 of ff.net.0.proj, A2, B2 of ff.net.2
-        lora = _lora_params(blk) if len(lora_ab) > 0 else None
-        has_lora = lora is not None
-        n_rest = len(lora_ab) - (8 if has_lora else 0)
-        lora1 = _lora_params1(blk) if n_rest >= 8 else None
-        has1 = lora1 is not None
-        loraf = _lora_params_ff(blk) if n_rest % 8 == 4 else None
-        hasf = loraf is not None
-        o1 = 8 if has_lora else 0
-        abf = lora_ab[o1 + (8 if has1 else 0):] if hasf else ()
-        ab1 = lora_ab[o1:o1 + 8] if has1 else ()
-        lora_ab = lora_ab[:8] if has_lora else ()
-        r = lora[0].r if has_lora else 0
-        s = lora[0].scaling if has_lora else 1.0
+        # lora_ab = the block's adapter weights in _block_ab's order, here per group
+        ad = _block_lora(blk)
+        ab2, ab1, abf = ad.split(lora_ab)
+        lora, lora1, loraf = ad.attn2, ad.attn1, ad.ff
         full = sh.full and keep
-        if (has_lora or has1 or hasf) and full:  # before the block's first launch
+        if lora_ab and full:  # before the block's first launch
             raise NotImplementedError("train_mode='full' trains the base weights without LoRA")
         # LoRA dropout (training forwards of a model whose adapters have lora_dropout > 0): every
         # adapter's lora_A reads its own masked input xd, scaled by c (the down-projection's alpha);
         # the s u B^T term rides the GEMM K extension as without dropout
         dp = sh.block_drop(blk) if keep else None
-        ca = 1.0 if dp is None else dp[2]
         # ---- 1. norm1 + AdaLN(msa) -> fused QKV -> q/k RMSNorm + RoPE -> SDPA -> gated residual
         x1, rstd1 = ops.rmsnorm_modulate_fwd(h, mods[:, 0], onep[:, 1], ldm, rpm, blk.norm_eps)
-        if has1:
+        if lora1 is not None:
             # the q / k / v adapters ride the packed QKV GEMM: their u rows side by side as one
             # [M, 3 K2] operand, column group g of the output reading its own K2 columns
-            r1 = lora1[0].r
-            u1, su1 = _qkv_lora_down(x1, lora1, ab1, r1, dp)
+            u1, su1 = _qkv_lora_down(x1, lora1, ab1, ad.r1, dp)
             ext_w, grouped, _ = _qkv_ext(blk, lora1[0], lora1[1], lora1[2])
             qkv = ops.gemm(x1, W["qkv_w"], bias=W["qkv_b"], ext=(su1, ext_w),
-                           ext_group=(D, ops.lora_k2(r1)) if grouped else None)
+                           ext_group=(D, ops.lora_k2(ad.r1)) if grouped else None)
             del su1
         else:
             qkv = ops.gemm(x1, W["qkv_w"], bias=W["qkv_b"])
         strat = skip[1] if skip is not None else None
         # x1 is kept for the backward of the attn1 adapters (dA_g = w_g^T . x1), as full mode keeps it
-        keep_x1 = full or (has1 and keep)
+        keep_x1 = full or (lora1 is not None and keep)
         if strat is not SkipLayerStrategy.AttentionSkip and not keep_x1:
             del x1
         qk = torch.empty(M, 2 * D, dtype=torch.bfloat16, device=h.device)
@@ -834,142 +979,101 @@ class _BlockFn(torch.autograd.Function):
         elif strat is SkipLayerStrategy.AttentionValues:  # blend with to_v's output
             o1 = ops.skip_blend(o1, qkv[:, 2 * D:], skip[0], N)
         y1 = torch.empty(M, D, dtype=torch.bfloat16, device=h.device) if full else None
-        if has1:  # to_out.0's adapter sees the (blended) o1, as the reference's to_out does
-            lo1 = lora1[3]
-            u_o1, su = ops.lora_down(o1 if dp is None else _drop_x(o1, dp, 3), ab1[6], alpha=ca, split=True,
-                                     pieces=lambda: lo1.weight_pieces("A"))
-            h1 = ops.gemm(o1, lo1.base_layer.weight, bias=lo1.base_layer.bias, epilogue="gated_residual",
-                          aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm,
-                          ext=(su, lo1.weight_split("B")))
-            del su
-        else:
-            h1 = ops.gemm(o1, a1.to_out[0].weight, bias=a1.to_out[0].bias, epilogue="gated_residual",
-                          aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm)
+        # to_out.0's adapter sees the (blended) o1, as the reference's to_out does
+        m1, m2 = blk._modules["attn1"]._modules, blk._modules["attn2"]._modules  # (direct lookups, as _frozen)
+        wo1, bo1 = _wb(m1["to_out"]._modules["0"])
+        lo1 = lora1[3] if lora1 is not None else None
+        h1, u_o1 = _lora_gemm(o1, wo1, bo1, lo1, ab1[6] if ab1 else None, dp, 3, epilogue="gated_residual",
+                              aux0=h, aux1=mods[:, 2], aux2=y1, rows_per_batch=rpm)
         # ---- 2. attn2 on the un-normalised h1 (attention.py:273-285), LoRA fused into the GEMMs
         # (W["q2_w"] / W["o2_w"]: the base weights, or under DoRA the effective bf16(c W); the s u B^T
         # term then rides the K extension with split(c (.) s B), LoraLinear.weight_split)
-        wq, bq = W["q2_w"], _lin(a2.to_q)[1]
-        wo, bo = W["o2_w"], _lin(a2.to_out[0])[1]
+        wq, bq = W["q2_w"], _wb(m2["to_q"])[1]
+        wo, bo = W["o2_w"], _wb(m2["to_out"]._modules["0"])[1]
+        lq, _, _, lo = lora or (None,) * 4
+        Aq, _, _, _, _, _, Ao, _ = ab2 or (None,) * 8
         pre = sh.text_pre.pop(id(blk), None) if sh.text_pre is not None else None
-        if has_lora:
-            # peft LoRA fused into the K loop: [x | split(x.A^T)] . [W | split(s*B)]^T
-            Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo = lora_ab
-            u_q, su = ops.lora_down(h1 if dp is None else _drop_x(h1, dp, 4), Aq, alpha=ca, split=True,
-                                    pieces=lambda: lora[0].weight_pieces("A"))
-            q2raw = ops.gemm(h1, wq, bias=bq, ext=(su, lora[0].weight_split("B")))
-            del su
-        else:
-            u_q = None
-            q2raw = ops.gemm(h1, wq, bias=bq)
+        q2raw, u_q = _lora_gemm(h1, wq, bq, lq, Aq, dp, 4)
         q2, _, rq2, _ = ops.qk_norm_rope_fwd(q2raw, None, a2.q_norm.weight, None, None, B=B, N=N)
         if sh.text_stack is not None:  # computed for every block at once (_TextStack.forward)
             k2raw, k2, rk2, v2, u_k, u_v = sh.text_stack.block_kv(blk, sh)
         elif pre is None:
-            k2raw, k2, rk2, v2, u_k, u_v = _text_kv(blk, sh, enc2, lora_ab, dp)
+            k2raw, k2, rk2, v2, u_k, u_v = _text_kv(blk, sh, enc2, ab2, dp)
         else:  # computed on the text side stream one block ahead (_forward_tokens)
             (k2raw, k2, rk2, v2, u_k, u_v), ev = pre
             torch.cuda.current_stream().wait_event(ev)
         o2, lse2 = ops.attn_fwd(q2, k2, v2, B, H, d, a2.scale, key_bias=sh.enc_bias,
                                 kv_shared=sh.text_shared)
-        if has_lora:
-            u_o, su = ops.lora_down(o2 if dp is None else _drop_x(o2, dp, 7), Ao, alpha=ca, split=True,
-                                    pieces=lambda: lora[3].weight_pieces("A"))
-            h2 = ops.gemm(o2, wo, bias=bo, epilogue="accum", aux0=h1,
-                          ext=(su, lora[3].weight_split("B")))
-            del su
-        else:
-            u_o = None
-            h2 = ops.gemm(o2, wo, bias=bo, epilogue="accum", aux0=h1)
+        h2, u_o = _lora_gemm(o2, wo, bo, lo, Ao, dp, 7, epilogue="accum", aux0=h1)
         # ---- 3. norm2 + AdaLN(mlp) -> FF (tanh-GELU fused) -> gated residual
         x2, rstd2 = ops.rmsnorm_modulate_fwd(h2, mods[:, 3], onep[:, 4], ldm, rpm, blk.norm_eps)
+        # the feed-forward adapters ride the two GEMMs' K extension: u1 = x2 . A1^T with s B1 under the
+        # GELU epilogue (fpre is then the derivative at the adapted pre-activation), u2 = act . A2^T
+        # (K = 8192) with s B2 under the gated residual
+        net = blk._modules["ff"]._modules["net"]._modules
+        (wf1, bf1), (wf2, bf2) = _wb(net["0"]._modules["proj"]), _wb(net["2"])
+        lf1, lf2 = loraf or (None, None)
         # fpre: rint(32767 gelu_tanh'(pre-activation) / 2) (int16), kept by the GELU epilogue for the
         # backward's multiply (ltx_hip.h LTX_EPI_GELU)
-        fpre = torch.empty(M, ff.net[0].proj.out_features, dtype=torch.int16, device=h.device)
+        fpre = torch.empty(M, wf1.shape[0], dtype=torch.int16, device=h.device)
         y3 = torch.empty(M, D, dtype=torch.bfloat16, device=h.device) if full else None
-        if hasf:
-            # the feed-forward adapters ride the two GEMMs' K extension: u1 = x2 . A1^T with s B1 under
-            # the GELU epilogue (fpre is then the derivative at the adapted pre-activation), u2 =
-            # act . A2^T (K = 8192) with s B2 under the gated residual
-            lf1, lf2 = loraf
-            u_f1, su = ops.lora_down(x2 if dp is None else _drop_x(x2, dp, 8), abf[0], alpha=ca, split=True,
-                                     pieces=lambda: lf1.weight_pieces("A"))
-            act = ops.gemm(x2, lf1.base_layer.weight, bias=lf1.base_layer.bias, epilogue="gelu", aux0=fpre,
-                           ext=(su, lf1.weight_split("B")))
-            if not (keep and _ff_keep_x2()):
-                del x2
-            u_f2, su = ops.lora_down(act if dp is None else _drop_x(act, dp, 9), abf[2], alpha=ca, split=True,
-                                     pieces=lambda: lf2.weight_pieces("A"))
-            h3 = ops.gemm(act, lf2.base_layer.weight, bias=lf2.base_layer.bias, epilogue="gated_residual",
-                          aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm,
-                          ext=(su, lf2.weight_split("B")))
-            del su
-            if not keep:
-                del act
-        else:
-            act = ops.gemm(x2, ff.net[0].proj.weight, bias=ff.net[0].proj.bias, epilogue="gelu",
-                           aux0=fpre)
+        act, u_f1 = _lora_gemm(x2, wf1, bf1, lf1, abf[0] if abf else None, dp, 8, epilogue="gelu", aux0=fpre)
+        # the backward of ff.net.0.proj's adapter needs x2 (_ff_keep_x2)
+        keep_x2 = loraf is not None and keep and _ff_keep_x2()
+        if not keep_x2:
             del x2
-            h3 = ops.gemm(act, ff.net[2].weight, bias=ff.net[2].bias, epilogue="gated_residual",
-                          aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm)
+        h3, u_f2 = _lora_gemm(act, wf2, bf2, lf2, abf[2] if abf else None, dp, 9, epilogue="gated_residual",
+                              aux0=h2, aux1=mods[:, 5], aux2=y3, rows_per_batch=rpm)
+        if not (loraf is not None and keep):
             del act
         if strat is SkipLayerStrategy.TransformerBlock:
             h3 = ops.skip_blend(h3, h, skip[0], N)
         if keep:
-            lora_saved = (u_q, u_k, u_v, u_o) if has_lora else ()
-            full_saved = (x1, y1, y3) if full else ()
-            lora1_saved = (*ab1, u1, u_o1, x1) if has1 else ()
+            base = (h, enc2, mods, onep, rstd1, qkv, qk, rq1, rk1, o1, lse1, h1, q2raw, rq2, q2, k2raw, rk2, k2,
+                    v2, o2, lse2, h2, rstd2, fpre)
             # the feed-forward adapters keep the GELU output (dA2 = w2^T . act; [M, 4D] bf16) and
             # their two u, and x2 unless LTX_LORA_FF_KEEP_X2=0
-            loraf_saved = (*abf, u_f1, u_f2, act, *((x2,) if _ff_keep_x2() else ())) if hasf else ()
-            ctx.save_for_backward(h, enc2, mods, onep, rstd1, qkv, qk, rq1, rk1, o1, lse1, h1,
-                                  q2raw, rq2, q2, k2raw, rk2, k2, v2, o2, lse2, h2, rstd2, fpre,
-                                  *lora_ab, *lora_saved, *full_saved, *lora1_saved, *loraf_saved)
-            ctx.blk, ctx.sh, ctx.has_lora, ctx.full, ctx.has1 = blk, sh, has_lora, full, has1
-            ctx.hasf = hasf
-            ctx.dp = dp
+            flat, ctx.layout = _pack_saved(
+                base, attn2=(*ab2, u_q, u_k, u_v, u_o) if lora is not None else (),
+                full=(x1, y1, y3) if full else (), attn1=(*ab1, u1, u_o1, x1) if lora1 is not None else (),
+                ff=(*abf, u_f1, u_f2, act) if loraf is not None else (), x2=x2 if keep_x2 else None)
+            ctx.save_for_backward(*flat)
+            ctx.blk, ctx.sh, ctx.full, ctx.dp = blk, sh, full, dp
         return h3
 
     @staticmethod
     def backward(ctx, dh3):
         blk, sh = ctx.blk, ctx.sh
         B, N, L, H, d, D = sh.B, sh.N, sh.L, sh.H, sh.d, sh.D
-        has_lora = ctx.has_lora
-        saved = ctx.saved_tensors
+        ad = _block_lora(blk)
+        lora, lora1, loraf = ad.attn2, ad.attn1, ad.ff
+        sv = _unpack_saved(ctx.saved_tensors, ctx.layout)
         (h, enc2, mods, onep, rstd1, qkv, qk, rq1, rk1, o1, lse1, h1, q2raw, rq2, q2, k2raw, rk2,
-         k2, v2, o2, lse2, h2, rstd2, fpre) = saved[:24]
+         k2, v2, o2, lse2, h2, rstd2, fpre) = sv.base
         W = blk.weights()
         a1, a2 = blk.attn1, blk.attn2
         ldm = mods.stride(0)
         dh3 = dh3.contiguous()
-        grads_lora = []
         full = ctx.full
         if full:
-            x1, y1, y3 = saved[24:27]
+            x1, y1, y3 = sv.full
             dmods = torch.empty(B, 6, D, dtype=torch.bfloat16, device=h.device)
-        if has_lora:
-            Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo = saved[24:32]
-            u_q, u_k, u_v, u_o = saved[32:36]
-            lora = _lora_params(blk)
-            r, s = lora[0].r, lora[0].scaling
+        # an absent group's names are None: its sites then run the bare GEMMs (_lora_dgrad)
+        lq, lk, lv, lo = lora or (None,) * 4
+        Aq, Bq, Ak, Bk, Av, Bv, Ao, Bo, u_q, u_k, u_v, u_o = sv.attn2 or (None,) * 12
+        r, s = ad.r, ad.s
         # DoRA on attn2 (DESIGN.md "DoRA (use_dora)"): W holds the effective weights, the adapters'
         # backward runs on B_eff = c (.) s B (_lora_backward dora=True), and the four magnitude gradients
         # dm = (1 / m) sum_rows dY (y - b) go straight into .grad
-        dora = has_lora and lora[0].use_dora
-        has1 = ctx.has1
-        if has1:
-            o1s = 36 if has_lora else 24
-            ab1 = saved[o1s:o1s + 8]
-            u1, u_o1, x1 = saved[o1s + 8:o1s + 11]
-            lora1 = _lora_params1(blk)
-            r1, s1 = lora1[0].r, lora1[0].scaling
-        hasf = ctx.hasf
-        if hasf:
-            of = 24 + (12 if has_lora else 0) + (11 if has1 else 0)
-            abf = saved[of:of + 4]
-            u_f1, u_f2, act = saved[of + 4:of + 7]
-            x2 = saved[of + 7] if len(saved) > of + 7 else None
-            lf1, lf2 = _lora_params_ff(blk)
-            rf, sf = lf1.r, lf1.scaling
+        dora = ad.dora
+        lo1 = Ao1 = Bo1 = u_o1 = None
+        if lora1 is not None:  # (x1: full mode's own without adapters)
+            *ab1, u1, u_o1, x1 = sv.attn1
+            lo1, Ao1, Bo1 = lora1[3], ab1[6], ab1[7]
+        r1, s1 = ad.r1, ad.s1
+        lf1, lf2 = loraf or (None, None)
+        Af1, Bf1, Af2, Bf2, u_f1, u_f2, act = sv.ff or (None,) * 7
+        rf, sf = ad.rf, ad.sf
         # ---- FF: h3 = h2 + g_mlp * ff(x2)
         rpm = sh.rpm
         pre, sh.ffo_pre = sh.ffo_pre, None
@@ -988,44 +1092,19 @@ class _BlockFn(torch.autograd.Function):
         # GEMM of a dropped-out adapter runs WITHOUT its K extension (the plain classes of the
         # no-adapter path); the masked term c keep (w . A) is added afterwards (_masked_add)
         dp = ctx.dp
-        ca = 1.0 if dp is None else dp[2]
-        if hasf and dp is not None:
-            # ff.net.2: the GELU-backward GEMM without the extension, then the masked term times the
-            # kept derivative; ff.net.0.proj: a plain add into dx2
-            xd = _drop_x(act, dp, 9)
-            w2, _ = _lora_backward(d_ffo, u_f2, lf2, abf[3], xd, rf, sf, merge_da=_ff_merge_da(), da_alpha=ca)
-            del xd
-            d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre)
-            _masked_add(d_f, w2, [abf[2]], dp, (9,), g=fpre)
-            del d_ffo, act, w2
-            if x2 is None:  # bitwise the forward's x2
-                x2, _ = ops.rmsnorm_modulate_fwd(h2, mods[:, 3], onep[:, 4], ldm, rpm, blk.norm_eps)
-            xd = _drop_x(x2, dp, 8)
-            del x2
-            w1, _ = _lora_backward(d_f, u_f1, lf1, abf[1], xd, rf, sf, merge_da=_ff_merge_da(), da_alpha=ca)
-            del xd
-            dx2 = ops.gemm(d_f, W["ff1_wT"])
-            _masked_add(dx2, w1, [abf[0]], dp, (8,))
-            del d_f, w1
-            grads_lora = [None] * 4
-        elif hasf:
-            # ff.net.2's adapter: dY = d_ffo, x = act (K = 8192); w2 = s d_ffo B2 rides the GELU-backward
-            # GEMM's K extension with A2's split. ff.net.0.proj's: dY = d_f [M, 4D], x = x2; w1 rides dx2's
-            _, sw = _lora_backward(d_ffo, u_f2, lf2, abf[3], act, rf, sf, merge_da=_ff_merge_da())
-            d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre, ext=(sw, lf2.weight_split("A")))
-            del d_ffo, act, sw
-            if x2 is None:  # bitwise the forward's x2
-                x2, _ = ops.rmsnorm_modulate_fwd(h2, mods[:, 3], onep[:, 4], ldm, rpm, blk.norm_eps)
-            _, sw = _lora_backward(d_f, u_f1, lf1, abf[1], x2, rf, sf, merge_da=_ff_merge_da())
-            del x2
-            dx2 = ops.gemm(d_f, W["ff1_wT"], ext=(sw, lf1.weight_split("A")))
-            del d_f, sw
-            grads_lora = [None] * 4
-        else:
-            d_f = ops.gemm(d_ffo, W["ff2_wT"], epilogue="gelu_bwd", aux0=fpre)
-            del d_ffo
-            dx2 = ops.gemm(d_f, W["ff1_wT"])
-            del d_f
+        # ff.net.2's adapter: dY = d_ffo, x = act (K = 8192); w2 = s d_ffo B2 rides the GELU-backward
+        # GEMM's K extension with A2's split (under dropout: that GEMM without the extension, then the
+        # masked term times the kept derivative). ff.net.0.proj's: dY = d_f [M, 4D], x = x2; w1 rides
+        # dx2's (under dropout: a plain add into dx2)
+        merge_da = loraf is not None and _ff_merge_da()
+        d_f = _lora_dgrad(d_ffo, W["ff2_wT"], lf2, Af2, Bf2, u_f2, act, rf, sf, dp, 9, g=fpre,
+                          merge_da=merge_da, epilogue="gelu_bwd", aux0=fpre)
+        del d_ffo, act
+        x2 = sv.x2
+        if loraf is not None and x2 is None:  # not kept (LTX_LORA_FF_KEEP_X2=0): remade, bitwise the forward's
+            x2 = lambda: ops.rmsnorm_modulate_fwd(h2, mods[:, 3], onep[:, 4], ldm, rpm, blk.norm_eps)[0]
+        dx2 = _lora_dgrad(d_f, W["ff1_wT"], lf1, Af1, Bf1, u_f1, x2, rf, sf, dp, 8, merge_da=merge_da)
+        del d_f, x2
         dh2 = ops.rmsnorm_modulate_bwd(dx2, h2, rstd2, onep[:, 4], ldm, rpm, dres=dh3)
         if full:  # shift_mlp / scale_mlp (attention.py:287-290)
             ops.colsum_into(dmods[:, 3], dx2, rows_per_group=rpm, sum_groups=False, accumulate=False)
@@ -1036,45 +1115,17 @@ class _BlockFn(torch.autograd.Function):
         # dO of the cross-attention + its delta rowsum(dO*O) in the GEMM epilogue
         # (under LoRA dropout dO is complete only after the masked add: delta then comes from the
         # attention backward's own row-sum pass, as with LTX_DELTA_FUSED=0)
-        fused2 = _DELTA_FUSED and not (has_lora and dp is not None)
+        fused2 = _DELTA_FUSED and not (lora is not None and dp is not None)
         delta2 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if fused2 else None
         rd = dict(epilogue="store_rowdot", aux0=o2, aux1=delta2, rank=d, rows_per_batch=N) \
             if fused2 else {}
-        if has_lora and dp is not None:
-            lq, lk, lv, lo = lora
-            xd = _drop_x(o2, dp, 7)
-            w_o, _ = _lora_backward(dh2, u_o, lo, Bo, xd, r, s, da_alpha=ca)
-            del xd
-            do2 = ops.gemm(dh2, W["o2_wT"])
-            _masked_add(do2, w_o, [Ao], dp, (7,))
-            del w_o
-        elif dora:
-            lq, lk, lv, lo = lora
-            _, sw = _lora_backward(dh2, u_o, lo, None, o2, r, s, dora=True)
-            do2 = ops.gemm(dh2, W["o2_wT"], ext=(sw, lo.weight_split("A")), **rd)
+        do2 = _lora_dgrad(dh2, W["o2_wT"], lo, Ao, Bo, u_o, o2, r, s, dp, 7, epi=rd, dora=dora)
+        if dora:
             # to_out.0's output went into the residual and was never stored: y - b is recomputed with
             # one store GEMM (o2 . W_eff^T plus the K extension from the kept u_o, no bias)
             yo = ops.gemm(o2, W["o2_w"], ext=(ops.lora_split(u_o, "act"), lo.weight_split("B")))
             ops.dora_mag_grad(dh2, yo, None, _dora_m(lo), _grad_buf(lo, "m"))
             del yo
-        elif has_lora:
-            lq, lk, lv, lo = lora
-            dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dh2, r)
-            if dy_ok and ops.lora_dy_da_fits(dh2, o2, r):
-                # one pass over dY, one over o2 (dA), one finish for w / split, dB and dA
-                w_o, sw = ops.lora_dy(dh2, u_o, lo.weight_pieces("Bt"), r, s, _grad_buf(lo, "B"),
-                                      x=o2, dA_out=_grad_buf(lo, "A"))
-            else:
-                if dy_ok:  # one pass over dY
-                    w_o, sw = ops.lora_dy(dh2, u_o, lo.weight_pieces("Bt"), r, s, _grad_buf(lo, "B"))
-                else:
-                    ops.lora_wgrad(dh2, u_o, alpha=s, out=_grad_buf(lo, "B"), accumulate=True)
-                    w_o, sw = ops.lora_down(dh2, Bo, alpha=s, transposed=True, split=True,
-                                             pieces=lambda: lo.weight_pieces("Bt"))
-                ops.lora_wgrad(o2, w_o, transpose_out=True, out=_grad_buf(lo, "A"), accumulate=True)
-            do2 = ops.gemm(dh2, W["o2_wT"], ext=(sw, lo.weight_split("A")), **rd)
-        else:
-            do2 = ops.gemm(dh2, W["o2_wT"], **rd)
         if full:  # attn2.to_out.0
             lin = a2.to_out[0]
             ops.wgrad_into(_pgrad(lin.weight), dh2, o2)
@@ -1143,114 +1194,33 @@ class _BlockFn(torch.autograd.Function):
         # dh1 = dh2 + dq2raw . W_q2 (+ LoRA) and, from the same epilogue, d_y1 = bf16(dh1 * g_msa)
         d_y1 = torch.empty_like(dh2)
         gated = dict(aux1=mods[:, 2], aux2=d_y1, rows_per_batch=rpm)
-        if has_lora and dp is not None:
-            # to_q into the residual-stream gradient, to_k / to_v into the encoder gradient: the masked
-            # terms are added after the accumulation, and d_y1 = bf16(dh1 * g_msa) is taken from the
-            # completed dh1
-            xd = _drop_x(h1, dp, 4)
-            w_q, _ = _lora_backward(dq2raw, u_q, lq, Bq, xd, r, s, da_alpha=ca)
-            del xd
-            dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2)
-            _masked_add(dh1, w_q, [Aq], dp, (4,))
-            del w_q
+        # to_q into the residual-stream gradient (under LoRA dropout the masked term is added after the
+        # accumulation, and d_y1 = bf16(dh1 * g_msa) is taken from the completed dh1)
+        dh1 = _lora_dgrad(dq2raw, W["q2_wT"], lq, Aq, Bq, u_q, h1, r, s, dp, 4, epi=gated, dora=dora,
+                          epilogue="accum", aux0=dh2)
+        if lora is not None and dp is not None:
             d_y1 = ops.gate_mul(dh1, mods[:, 2], rpm)
-            # (the per-sample text path: under dropout there is no shared prompt and no text stack)
-            w_kv = torch.empty(dkv.shape[0], 2 * r, dtype=torch.float32, device=h.device)
-            for i, (dy, u_t, lt, Bt_) in enumerate(((dk2raw, u_k, lk, Bk), (dv2, u_v, lv, Bv))):
-                ops.lora_wgrad(dy, u_t, alpha=s, out=_grad_buf(lt, "B"), accumulate=True)
-                ops.lora_down(dy, Bt_, alpha=s, transposed=True, out=w_kv[:, i * r:(i + 1) * r])
-                xd = _drop_x(enc2, dp, 5 + i)
-                ops.lora_wgrad(xd, w_kv[:, i * r:(i + 1) * r], alpha=ca, transpose_out=True,
-                               out=_grad_buf(lt, "A"), accumulate=True)
-                del xd
-            denc = ops.gemm(dkv, W["kv2_wT"])
-            _masked_add(denc, w_kv, [Ak, Av], dp, (5, 6))
-            del w_kv
-            grads_lora = grads_lora + [None] * 8
-        elif dora:
-            # (the per-block text path: a DoRA model has no text stack; with a shared prompt dk2raw / dv2
-            # are the batch-summed text gradients, the right dY of the shared rows' magnitudes too)
-            _, sw = _lora_backward(dq2raw, u_q, lq, None, h1, r, s, dora=True)
-            dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2,
-                           ext=(sw, lq.weight_split("A")), **gated)
+        if dora:
             ops.dora_mag_grad(dq2raw, q2raw, _lin(lq)[1], _dora_m(lq), _grad_buf(lq, "m"))
-            K2 = ops.lora_k2(r)
-            swkv = torch.empty(dkv.shape[0], 2 * K2, dtype=torch.bfloat16, device=h.device)
-            for i, (dy, y_t, u_t, lt) in enumerate(((dk2raw, k2raw, u_k, lk), (dv2, v2, u_v, lv))):
-                dop = lt.dora_operands()
-                dB = ops.lora_wgrad(dy, u_t)
-                ops.dora_rowscale_add(_grad_buf(lt, "B"), dB, dop["c"], s)
-                w_t, _ = ops.lora_down(dy, dop["sB"], transposed=True, split=True,
-                                       split_out=swkv[:, i * K2:(i + 1) * K2])
-                ops.lora_wgrad(enc2, w_t, transpose_out=True, out=_grad_buf(lt, "A"), accumulate=True)
-                ops.dora_mag_grad(dy, y_t, _lin(lt)[1], _dora_m(lt), _grad_buf(lt, "m"))
-            denc = ops.gemm(dkv, W["kv2_wT"], ext=(swkv, _kv_ext(blk, lk, lv)[1]))
-            del swkv
-            grads_lora = grads_lora + [None] * 8
-        elif has_lora:
-            dy_ok = ops.lora_dy_enabled() and ops.lora_dy_fits(dq2raw, r)
-            if dy_ok and ops.lora_dy_da_fits(dq2raw, h1, r):
-                w_q, sw = ops.lora_dy(dq2raw, u_q, lq.weight_pieces("Bt"), r, s, _grad_buf(lq, "B"),
-                                      x=h1, dA_out=_grad_buf(lq, "A"))
-            else:
-                if dy_ok:
-                    w_q, sw = ops.lora_dy(dq2raw, u_q, lq.weight_pieces("Bt"), r, s, _grad_buf(lq, "B"))
-                else:
-                    ops.lora_wgrad(dq2raw, u_q, alpha=s, out=_grad_buf(lq, "B"), accumulate=True)
-                    w_q, sw = ops.lora_down(dq2raw, Bq, alpha=s, transposed=True, split=True,
-                                             pieces=lambda: lq.weight_pieces("Bt"))
-                ops.lora_wgrad(h1, w_q, transpose_out=True, out=_grad_buf(lq, "A"), accumulate=True)
-            dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2,
-                           ext=(sw, lq.weight_split("A")), **gated)
-            if tx is None:
-                K2 = ops.lora_k2(r)
-                swkv = torch.empty(dkv.shape[0], 2 * K2, dtype=torch.bfloat16, device=h.device)
-                ops.lora_wgrad(dk2raw, u_k, alpha=s, out=_grad_buf(lk, "B"), accumulate=True)
-                w_k, _ = ops.lora_down(dk2raw, Bk, alpha=s, transposed=True, split=True,
-                                       split_out=swkv[:, :K2])
-                ops.lora_wgrad(enc2, w_k, transpose_out=True, out=_grad_buf(lk, "A"),
-                               accumulate=True)
-                ops.lora_wgrad(dv2, u_v, alpha=s, out=_grad_buf(lv, "B"), accumulate=True)
-                w_v, _ = ops.lora_down(dv2, Bv, alpha=s, transposed=True, split=True,
-                                       split_out=swkv[:, K2:])
-                ops.lora_wgrad(enc2, w_v, transpose_out=True, out=_grad_buf(lv, "A"),
-                               accumulate=True)
-                # denc = dK_raw.W_k + dV.W_v + both adapters' input-gradient terms, one GEMM
-                denc = ops.gemm(dkv, W["kv2_wT"], ext=(swkv, _kv_ext(blk, lk, lv)[1]))
-                del swkv
-            # the adapter gradients went straight into .grad (accumulated across micro-steps by
-            # the kernels' atomics); autograd gets None for them
-            grads_lora = grads_lora + [None] * 8
-        else:
-            dh1 = ops.gemm(dq2raw, W["q2_wT"], epilogue="accum", aux0=dh2, **gated)
-            if tx is None:
-                denc = ops.gemm(dkv, W["kv2_wT"])
+        # to_k / to_v into the encoder gradient, one GEMM. With the text stack _TextStackFn.backward
+        # computes it, and the two adapters' gradients; under dropout there is no shared prompt and no text
+        # stack, and a DoRA model has no text stack (with a shared prompt dk2raw / dv2 are then the
+        # batch-summed text gradients, the right dY of the shared rows' magnitudes too)
+        if tx is None and lora is not None:
+            denc = _text_kv_lora_backward(blk, dkv, (dk2raw, dv2), (k2raw, v2), (u_k, u_v), (lk, lv),
+                                          (Ak, Bk, Av, Bv), enc2, W["kv2_wT"], r, s, dp, dora)
+        elif tx is None:
+            denc = ops.gemm(dkv, W["kv2_wT"])
         del dq2raw, dk2raw, dv2, dh2, dkv
         # ---- attn1: h1 = h + g_msa * to_out(sdpa(rope(qn(q)), rope(kn(k)), v))
         # (d_y1 = bf16(dh1 * g_msa) came out of the dh1 GEMM's epilogue: `gated` above)
-        fused1 = _DELTA_FUSED and not (has1 and dp is not None)  # as fused2 above
+        fused1 = _DELTA_FUSED and not (lora1 is not None and dp is not None)  # as fused2 above
         delta1 = torch.empty(B, H, N, dtype=torch.float32, device=h.device) if fused1 else None
         rd = dict(epilogue="store_rowdot", aux0=o1, aux1=delta1, rank=d, rows_per_batch=N) \
             if fused1 else {}
-        if has1 and dp is not None:
-            lo1 = lora1[3]
-            xd = _drop_x(o1, dp, 3)
-            w_o1, _ = _lora_backward(d_y1, u_o1, lo1, ab1[7], xd, r1, s1, da_alpha=ca)
-            del xd
-            do1 = ops.gemm(d_y1, W["out1_wT"])
-            _masked_add(do1, w_o1, [ab1[6]], dp, (3,))
-            del w_o1
-            grads_lora = grads_lora + [None] * 8
-        elif has1:
-            # to_out.0's adapter: dB_o, dA_o (x = o1) into .grad; w_o = s d_y1 B_o rides the dgrad's
-            # K extension with A_o's split
-            lo1 = lora1[3]
-            _, sw = _lora_backward(d_y1, u_o1, lo1, ab1[7], o1, r1, s1)
-            do1 = ops.gemm(d_y1, W["out1_wT"], ext=(sw, lo1.weight_split("A")), **rd)
-            del sw
-            grads_lora = grads_lora + [None] * 8
-        else:
-            do1 = ops.gemm(d_y1, W["out1_wT"], **rd)
+        # to_out.0's adapter: dB_o, dA_o (x = o1) into .grad; w_o = s d_y1 B_o rides the dgrad's
+        # K extension with A_o's split
+        do1 = _lora_dgrad(d_y1, W["out1_wT"], lo1, Ao1, Bo1, u_o1, o1, r1, s1, dp, 3, epi=rd)
         if full:  # gate_msa, attn1.to_out.0
             ops.colsum_into(dmods[:, 2], dh1, y1, mode=1, rows_per_group=rpm, sum_groups=False,
                             accumulate=False)
@@ -1278,22 +1248,22 @@ class _BlockFn(torch.autograd.Function):
             del dwqkv
         del dq1, dk1
         dh = None
-        if has1 and dp is not None:
+        if lora1 is not None and dp is not None:
             # q / k / v have three different xd: the one-adapter calls for dB / dA, their w side by side
             # for the G = 3 masked add into dx1
             w1 = torch.empty(M, 3 * r1, dtype=torch.float32, device=h.device)
             for g in range(3):
                 xd = _drop_x(x1, dp, g)
                 _lora_backward(dqkv[:, g * D:(g + 1) * D], u1[:, g * r1:(g + 1) * r1], lora1[g], ab1[2 * g + 1],
-                               xd, r1, s1, w_out=w1[:, g * r1:(g + 1) * r1], da_alpha=ca)
+                               xd, r1, s1, w_out=w1[:, g * r1:(g + 1) * r1], da_alpha=dp[2])
                 del xd
-        elif has1:  # dB / dA of the q / k / v adapters (one pass over dqkv, one over x1) and w's split
+        elif lora1 is not None:  # dB / dA of the q / k / v adapters (one pass over dqkv, one over x1) and w's split
             sw1 = _qkv_lora_backward(dqkv, u1, lora1, ab1, x1, r1, s1)
         if ctx.needs_input_grad[4] or full:  # (blk, sh, keep, skip, h, ...)
-            if has1 and dp is not None:
+            if lora1 is not None and dp is not None:
                 dx1 = ops.gemm(dqkv, W["qkv_wT"])
                 _masked_add(dx1, w1, [ab1[0], ab1[2], ab1[4]], dp, (0, 1, 2))
-            elif has1:  # + sum_g w_g . A_g: a plain K extension of 3 K2
+            elif lora1 is not None:  # + sum_g w_g . A_g: a plain K extension of 3 K2
                 dx1 = ops.gemm(dqkv, W["qkv_wT"], ext=(sw1, _qkv_ext(blk, lora1[0], lora1[1], lora1[2])[2]))
             else:
                 dx1 = ops.gemm(dqkv, W["qkv_wT"])
@@ -1318,7 +1288,9 @@ class _BlockFn(torch.autograd.Function):
         done = None if tx is None else tx.token_params[tx.index[id(blk)]]
         for cb in getattr(blk, "_grad_ready_hooks", ()):
             cb(blk, done)
-        return (None, None, None, None, dh, denc, dm, None, *grads_lora)
+        # the adapter gradients went straight into .grad (accumulated across micro-steps by the
+        # kernels' atomics); autograd gets None for them
+        return (None, None, None, None, dh, denc, dm, None, *(None,) * ad.n_ab)
 
 
 class _CaptionProjFn(torch.autograd.Function):
@@ -1343,36 +1315,6 @@ class _CaptionProjFn(torch.autograd.Function):
         dw1 = ops.wgrad(dpre, enc)
         db1 = ops.colsum(dpre)
         return None, dw1, db1, dw2, db2
-
-
-def _lora_ab(blk):
-    """[A_q, B_q, A_k, B_k, A_v, B_v, A_o, B_o] adapter weights of attn2 (or [])."""
-    lora = _lora_params(blk)
-    ab = []
-    if lora is not None:
-        for m in lora:
-            ab += _ab(m)
-    return ab
-
-
-def _lora_ab1(blk):
-    """[A_q, B_q, A_k, B_k, A_v, B_v, A_o, B_o] adapter weights of attn1 (or [])."""
-    lora = _lora_params1(blk)
-    ab = []
-    if lora is not None:
-        for m in lora:
-            ab += _ab(m)
-    return ab
-
-
-def _lora_abf(blk):
-    """[A_1, B_1, A_2, B_2] adapter weights of ff.net.0.proj and ff.net.2 (or [])."""
-    lora = _lora_params_ff(blk)
-    ab = []
-    if lora is not None:
-        for m in lora:
-            ab += _ab(m)
-    return ab
 
 
 def _text_kv(blk, sh, enc2, lora_ab, dp=None):
@@ -2103,7 +2045,7 @@ class Transformer3DModel(nn.Module):
                 ready.record(main)
                 with torch.no_grad(), torch.cuda.stream(side):
                     side.wait_event(ready)
-                    vals = _text_kv(bj, sh, enc2, _lora_ab(bj))
+                    vals = _text_kv(bj, sh, enc2, [t for m in lj or () for t in _ab(m)])
                     ev = torch.cuda.Event()
                     ev.record(side)
                 for t in vals:
@@ -2127,7 +2069,7 @@ class Transformer3DModel(nn.Module):
                 with torch.no_grad():
                     mods, onep = ops.ada_modulation(blk.scale_shift_table, tmod,
                                                     (1 << 1) | (1 << 4))
-            ab = _lora_ab(blk) + _lora_ab1(blk) + _lora_abf(blk)
+            ab = _block_ab(blk)
             if fuse_gate:
                 if prev_gate is not None:
                     sh.ffgate[id(blk)] = prev_gate
