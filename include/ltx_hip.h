@@ -480,6 +480,29 @@ int ltx_grad_clip_coef(const double* part, int64_t nparts, float max_norm, void*
 int ltx_adamw_multi_clip(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
                          float eps, float weight_decay, int64_t step, const float* coef, void* stream);
 
+/* ---- EMA of the trainable weights, fused into the multi-tensor AdamW step (csrc/optim.hip) ------- */
+/* The EMA table: device int64 [nchunks][8] of (param, grad, exp_avg, exp_avg_sq, first element,
+ * count <= 2048, shadow, stash). shadow is the tensor's f32 moving average (f32 for bf16 parameters too),
+ * stash a buffer of the parameter's dtype and size; both are indexed like the parameter. A field an
+ * entry point does not read may be 0: stash for ltx_adamw_multi_ema; grad, exp_avg and exp_avg_sq for
+ * the two swap entries. One block per row, 256 threads.
+ *
+ * ltx_adamw_multi_ema: ltx_adamw_multi (coef_or_null == null) or ltx_adamw_multi_clip (coef_or_null: the
+ * device coefficient) -- param, exp_avg and exp_avg_sq bitwise theirs -- and, for each element, with p'
+ * the parameter value the step stores (for bf16 the value just rounded to bf16),
+ *   shadow <- shadow - one_minus_decay * (shadow - float(p'))
+ * as three separately rounded f32 operations (subtract, multiply, subtract; never an FMA): diffusers'
+ * EMAModel.step s_param.sub_(one_minus_decay * (s_param - param)) on an f32 shadow. one_minus_decay is
+ * (float)(1.0 - decay), computed by the caller in double; it must lie in [0, 1]. */
+int ltx_adamw_multi_ema(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int64_t step, const float* coef_or_null,
+                        float one_minus_decay, void* stream);
+/* stash[i] = param[i]; param[i] = R(shadow[i]) over the EMA table's rows (R: round to nearest even to
+ * bf16 for bf16 parameters, identity for f32). One launch per dtype. */
+int ltx_ema_load_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream);
+/* param[i] = stash[i] over the EMA table's rows: undoes ltx_ema_load_multi. */
+int ltx_ema_restore_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream);
+
 /* ---- train_mode='full' parameter gradients (csrc/paramgrad.hip) --------- */
 /* Weight gradient of the q/k RMSNorm weights: partials[(which * splits + s) * D + d] (f32) =
  * sum over row split s of bf16(dn * bf16(x_raw * rstd)), dn = RoPE^T of the incoming gradient (the

@@ -7,7 +7,11 @@ the merged file on demand, through the same export train_loop uses (io.export_me
 W + s B A, or DoRA's (m / norm) (W + s B A), rounded once to the base dtype; adapter keys dropped), so
 the small directories are all that has to be kept. Runs on the CPU; nothing in either input is executed.
 
-    python tools/merge_adapter.py BASE.safetensors ADAPTER_DIR OUT.safetensors
+    python tools/merge_adapter.py [--ema] BASE.safetensors ADAPTER_DIR OUT.safetensors
+
+--ema merges the exponential moving average of the trained weights (ema_model.safetensors, written when
+the run had train.ema_decay set) in place of the raw adapters: each f32 shadow is cast to its parameter's
+dtype, then the same export.
 """
 import argparse
 import os
@@ -17,14 +21,16 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "video-generation-for-human-avatars_amd"))
 
 
-def merge(base, adapter_dir, out):
+def merge(base, adapter_dir, out, ema=False):
     """The base checkpoint (anything Transformer3DModel.from_pretrained reads) with the adapters,
-    magnitudes and caption_projection of `adapter_dir` folded in, written to `out`; returns `out`."""
+    magnitudes and caption_projection of `adapter_dir` folded in, written to `out`; returns `out`.
+    `ema`: the directory's averaged weights in place of the raw ones (ValueError when it has none)."""
     from ltx_amd import io
     from ltx_amd.transformer3d import Transformer3DModel
     model = Transformer3DModel.from_pretrained(base)
-    state = io.load_adapter_checkpoint(model, adapter_dir)
-    meta = {"epoch": str(state["epoch"]), "global_step": str(state["global_step"]), "source": "merge_adapter"}
+    state = io.load_adapter_checkpoint(model, adapter_dir, weights="ema" if ema else "raw")
+    meta = {"epoch": str(state["epoch"]), "global_step": str(state["global_step"]),
+            "source": "merge_adapter_ema" if ema else "merge_adapter"}
     if os.path.isfile(base):  # a single-file base carries its scheduler config along
         import json
 
@@ -42,8 +48,9 @@ def main(argv=None):
     ap.add_argument("base", help="base checkpoint: a single-file safetensors or a diffusers-style directory")
     ap.add_argument("adapter_dir", help="an adapter_epoch_{E} directory")
     ap.add_argument("out", help="the merged single-file safetensors to write")
+    ap.add_argument("--ema", action="store_true", help="merge the averaged weights (ema_model.safetensors)")
     a = ap.parse_args(argv)
-    print(merge(a.base, a.adapter_dir, a.out))
+    print(merge(a.base, a.adapter_dir, a.out, ema=a.ema))
 
 
 if __name__ == "__main__":

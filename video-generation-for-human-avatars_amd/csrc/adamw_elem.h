@@ -1,5 +1,6 @@
 // The per-element AdamW update shared by the optimizer kernels (elementwise.hip: ltx_adamw_step /
-// ltx_adamw_multi; optim.hip: ltx_adamw_multi_clip), so every entry point runs one arithmetic.
+// ltx_adamw_multi; optim.hip: ltx_adamw_multi_clip / ltx_adamw_multi_ema), so every entry point runs one
+// arithmetic.
 #pragma once
 #include <cmath>
 
@@ -17,11 +18,16 @@ __device__ __forceinline__ float torch_lerp(float self, float end, float w) {
 // sqrt, / sqrt(bc2), + eps, p += step_size * m / den), rounding every op for bf16 tensors.
 // CLIP: the gradient is first scaled by `coef` and rounded to its dtype, which is what an in-place
 // grad.mul_(coef) would leave in memory (the global-norm clip; grad itself is not written).
-template <bool BF16, bool CLIP = false>
+// EMA: the f32 shadow of the parameter follows the value this step stores, p' (for bf16 the value just
+// rounded to bf16): s <- s - omd (s - float(p')), diffusers' EMAModel.step
+// s_param.sub_(one_minus_decay * (s_param - param)) as three separately rounded f32 operations (no FMA).
+// The shadow only observes the step: p', m and v are those of EMA = false.
+template <bool BF16, bool CLIP = false, bool EMA = false>
 __device__ __forceinline__ void adamw_elem(void* __restrict__ param, const void* __restrict__ grad,
                                            void* __restrict__ m_, void* __restrict__ v_, int64_t i, float decay,
                                            float w1, float b2, float w2, float step_size, float bc2_sqrt, float eps,
-                                           float coef = 1.0f) {
+                                           float coef = 1.0f, float* __restrict__ shadow = nullptr,
+                                           float omd = 0.0f) {
   float p, g, m, v;
   if (BF16) {
     p = bf2f(((bf16_t*)param)[i]); g = bf2f(((const bf16_t*)grad)[i]);
@@ -39,6 +45,10 @@ __device__ __forceinline__ void adamw_elem(void* __restrict__ param, const void*
   den = R(den / bc2_sqrt);
   den = R(den + eps);
   p = R(p + step_size * (m / den));
+  if (EMA) {
+    const float s = shadow[i];
+    shadow[i] = __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p)));
+  }
   if (BF16) {
     ((bf16_t*)param)[i] = f2bf(p); ((bf16_t*)m_)[i] = f2bf(m); ((bf16_t*)v_)[i] = f2bf(v);
   } else {

@@ -9,6 +9,9 @@
 //   3. adamw_multi_clip_kernel: adamw_multi_kernel on g' = R(g * coef), coef read from the record.
 // Every sum has a fixed order and there are no atomics, so the record is bitwise reproducible; nothing here
 // reads a value back to the host.
+// Below them, the exponential moving average of the trainable weights (FusedAdamW with ema): the AdamW
+// launch with the f32 shadow update fused in (ltx_adamw_multi_ema), and the two swap kernels that install
+// the averaged weights for an evaluation or an export and put the live ones back.
 #include <cmath>
 
 #include "adamw_elem.h"
@@ -102,6 +105,66 @@ __global__ __launch_bounds__(256) void adamw_multi_clip_kernel(const int64_t* __
     adamw_elem<BF16, true>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c);
 }
 
+// ---- EMA of the trainable weights (FusedAdamW(ema=...)) ----------------------------------------------
+// The EMA table has 8 int64 per row: the six fields above, then the row's tensor's f32 shadow and its
+// stash (a buffer of the parameter's dtype; 0 where an entry point does not use it). Rows index the shadow
+// and the stash like the parameter: element i of the tensor, first element .. first element + count.
+// Accesses are one element per lane (4 or 2 bytes, a wave's 64 lanes contiguous), as in the sibling
+// kernels: a row's first element has only its tensor's alignment, so 16-byte accesses would need a
+// per-row alignment guard and a peeled head / tail, and adamw_multi_kernel already moves its 28 B per
+// f32 element at 6 TB/s this way (profiles/grad_clip_bench.md).
+constexpr int EMA_ROW = 8;
+
+// adamw_multi_kernel / adamw_multi_clip_kernel with the shadow update riding on the parameter register
+template <bool BF16, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_multi_ema_kernel(const int64_t* __restrict__ table, float decay,
+                                                              float w1, float b2, float w2, float step_size,
+                                                              float bc2_sqrt, float eps,
+                                                              const float* __restrict__ coef, float omd) {
+  const int64_t* e = table + (int64_t)blockIdx.x * EMA_ROW;
+  void* param = (void*)e[0];
+  const void* grad = (const void*)e[1];
+  void* m = (void*)e[2];
+  void* v = (void*)e[3];
+  const int64_t start = e[4], end = e[4] + e[5];
+  float* shadow = (float*)e[6];
+  const float c = CLIP ? *coef : 1.0f;
+  for (int64_t i = start + threadIdx.x; i < end; i += 256)
+    adamw_elem<BF16, CLIP, true>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c, shadow, omd);
+}
+
+// LOAD: stash <- param, param <- R(shadow) (R: round to nearest even to bf16 for bf16 parameters);
+// otherwise param <- stash
+template <bool BF16, bool LOAD>
+__global__ __launch_bounds__(256) void ema_swap_multi_kernel(const int64_t* __restrict__ table) {
+  const int64_t* e = table + (int64_t)blockIdx.x * EMA_ROW;
+  const int64_t start = e[4], end = e[4] + e[5];
+  const float* __restrict__ shadow = (const float*)e[6];
+  if (BF16) {
+    bf16_t* __restrict__ param = (bf16_t*)e[0];
+    bf16_t* __restrict__ stash = (bf16_t*)e[7];
+    for (int64_t i = start + threadIdx.x; i < end; i += 256) {
+      if (LOAD) {
+        stash[i] = param[i];
+        param[i] = f2bf(shadow[i]);
+      } else {
+        param[i] = stash[i];
+      }
+    }
+  } else {
+    float* __restrict__ param = (float*)e[0];
+    float* __restrict__ stash = (float*)e[7];
+    for (int64_t i = start + threadIdx.x; i < end; i += 256) {
+      if (LOAD) {
+        stash[i] = param[i];
+        param[i] = shadow[i];
+      } else {
+        param[i] = stash[i];
+      }
+    }
+  }
+}
+
 }  // namespace ltx
 
 using namespace ltx;
@@ -139,6 +202,53 @@ int ltx_adamw_multi_clip(const int64_t* table, int64_t nchunks, int is_bf16, flo
   else
     hipLaunchKernelGGL(adamw_multi_clip_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
                        table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_adamw_multi_ema(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int64_t step, const float* coef_or_null,
+                        float one_minus_decay, void* stream) {
+  LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_ema: bad args");
+  LTX_CHECK_ARG(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "adamw_multi_ema: one_minus_decay outside [0, 1]");
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
+  const dim3 grid((unsigned)nchunks), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define LTX_EMA_LAUNCH(BF, CL)                                                                                    \
+  hipLaunchKernelGGL((adamw_multi_ema_kernel<BF, CL>), grid, block, 0, st, table, a.decay, a.w1, beta2, a.w2,     \
+                     a.step_size, a.bc2_sqrt, eps, coef_or_null, one_minus_decay)
+  if (is_bf16) {
+    if (coef_or_null) LTX_EMA_LAUNCH(true, true);
+    else LTX_EMA_LAUNCH(true, false);
+  } else {
+    if (coef_or_null) LTX_EMA_LAUNCH(false, true);
+    else LTX_EMA_LAUNCH(false, false);
+  }
+#undef LTX_EMA_LAUNCH
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_ema_load_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream) {
+  LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31), "ema_load_multi: bad args");
+  if (is_bf16)
+    hipLaunchKernelGGL((ema_swap_multi_kernel<true, true>), dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table);
+  else
+    hipLaunchKernelGGL((ema_swap_multi_kernel<false, true>), dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_ema_restore_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream) {
+  LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31), "ema_restore_multi: bad args");
+  if (is_bf16)
+    hipLaunchKernelGGL((ema_swap_multi_kernel<true, false>), dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table);
+  else
+    hipLaunchKernelGGL((ema_swap_multi_kernel<false, false>), dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

@@ -149,4 +149,17 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
         setattr(config, "lr_warmup_steps", int(t["lr_warmup_steps"]))
     if "lr_total_steps" in t:
         setattr(config, "lr_total_steps", int(t["lr_total_steps"]))
+    # and the keys training.ema_from_config reads (and validates): `train.ema_decay` (a float, absent
+    # or 0 = no EMA): the exponential moving average of the trained weights inside the LoRA optimizer
+    # step, with diffusers' EMAModel schedule: `train.ema_warmup` (a bool), `train.ema_inv_gamma`,
+    # `train.ema_power`, `train.ema_update_after_step` and `train.ema_min_decay`
+    if "ema_decay" in t:
+        setattr(config, "ema_decay", float(t["ema_decay"]))
+    if "ema_warmup" in t:
+        setattr(config, "ema_warmup", bool(t["ema_warmup"]))
+    for key in ("ema_inv_gamma", "ema_power", "ema_min_decay"):
+        if key in t:
+            setattr(config, key, float(t[key]))
+    if "ema_update_after_step" in t:
+        setattr(config, "ema_update_after_step", int(t["ema_update_after_step"]))
     return config

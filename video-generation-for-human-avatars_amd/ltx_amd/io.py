@@ -18,7 +18,9 @@
 * Adapter checkpoints (save_adapter_checkpoint / load_adapter_checkpoint): a directory of
   safetensors and JSON files only -- the trainable tensors under peft's saved names, peft's
   adapter_config.json, the FusedAdamW moments and the RNG states, and train_state.json, written
-  last. What train_loop resumes from; nothing in it is executed on load.
+  last. What train_loop resumes from; nothing in it is executed on load. With FusedAdamW(ema) also
+  ema_model.safetensors, the f32 moving averages of the same tensors, which
+  load_adapter_checkpoint(weights="ema") installs as the weights.
 """
 import json
 import math
@@ -232,6 +234,7 @@ ADAPTER_WEIGHTS = "adapter_model.safetensors"
 ADAPTER_CONFIG = "adapter_config.json"
 ADAPTER_OPTIMIZER = "optimizer.safetensors"
 ADAPTER_TRAIN_STATE = "train_state.json"
+ADAPTER_EMA = "ema_model.safetensors"  # optional: written when the optimizer keeps an EMA
 _PEFT_PREFIX = "base_model.model."
 _ADAPTER_HOLDERS = ("lora_A", "lora_B", "lora_magnitude_vector")  # ModuleDicts keyed by the adapter name
 _ADAPTER_GROUPS = ("attn1", "attn2", "ff")
@@ -368,9 +371,14 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
       and each group's own rank, alpha, scaling, dropout and DoRA flag;
     * optimizer.safetensors (with `optimizer`): exp_avg.<parameter name> / exp_avg_sq.<parameter name>
       in their stored dtype and every rank's RNG states (_gathered_rng_states);
+    * ema_model.safetensors (with an `optimizer` that keeps an EMA, FusedAdamW(ema)): the f32 shadow
+      of every parameter the optimizer holds under adapter_key's names (the parameter's own value in
+      f32 where it has not stepped yet, which is what its shadow starts from); every rank's shadows
+      are identical by construction, so nothing is gathered. A directory written without an EMA has
+      neither this file nor the "ema" block below;
     * train_state.json, written last: the format version, `train_state`'s epoch / global_step /
-      best_loss, the world size, the optimizer's hyper-parameters and per-parameter step, and
-      `loader`'s seed.
+      best_loss, the world size, the optimizer's hyper-parameters and per-parameter step,
+      `loader`'s seed, and with an EMA the block "ema": the EMASchedule's fields and ema_steps.
 
     Everything is written under `path`.tmp and moved into place with os.replace, so a checkpoint is
     complete or absent. Under torch.distributed every rank calls this (the RNG states are gathered);
@@ -381,6 +389,9 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
     targets, groups = _adapter_layout(model)
     if not targets:
         raise ValueError("save_adapter_checkpoint: the model has no LoRA adapters")
+    if getattr(optimizer, "_ema_swapped", None) is not None:
+        raise RuntimeError("save_adapter_checkpoint: the optimizer's EMA weights are swapped in; the model "
+                           "holds the averages, not the trained weights")
     # the one collective, before rank 0 goes its own way
     rng = _gathered_rng_states(_model_device(model)) if optimizer is not None else None
     if rank != 0:
@@ -410,6 +421,16 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
         hyper = [{k: _plain(v) for k, v in g.items() if k != "params" and _plain(v) is not None}
                  for g in optimizer.param_groups]
         state["optimizer"] = {"class": type(optimizer).__name__, "param_groups": hyper, "step": steps}
+    ema_tensors = None
+    schedule = getattr(optimizer, "ema", None)
+    if schedule is not None:
+        ema_tensors = {}
+        for group in optimizer.param_groups:
+            for p in group["params"]:
+                shadow = (optimizer.state.get(p) or {}).get("ema")
+                src = p if shadow is None else shadow
+                ema_tensors[adapter_key(names[id(p)])] = src.detach().float().cpu().contiguous()
+        state["ema"] = dict(schedule.fields(), ema_steps=int(optimizer.ema_steps))
     if loader is not None and hasattr(loader, "seed"):
         state["loader"] = {"seed": int(loader.seed)}
     meta = dict(metadata or {})
@@ -428,6 +449,8 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
     _write_json(os.path.join(tmp, ADAPTER_CONFIG), config)
     if opt_tensors is not None:
         save_file(opt_tensors, os.path.join(tmp, ADAPTER_OPTIMIZER))
+    if ema_tensors is not None:
+        save_file(ema_tensors, os.path.join(tmp, ADAPTER_EMA))
     _write_json(os.path.join(tmp, ADAPTER_TRAIN_STATE), state)
     old = None
     if os.path.isdir(path):  # os.replace does not move onto a directory that has files
@@ -477,7 +500,7 @@ def _read_json(path):
         return json.load(f)
 
 
-def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=True):
+def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=True, weights="raw"):
     """Restore the directory save_adapter_checkpoint wrote and return its train_state dict
     (best_loss = inf when none was recorded).
 
@@ -492,7 +515,17 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
     FusedAdamW chunk table) stay valid; then ops.bump_weight_generation() and every block's packed
     weights are dropped, as unload_lora does. With `optimizer` the moments, per-parameter steps
     (state is created where the optimizer has not stepped yet), hyper-parameters and this rank's two
-    RNG states are restored; with `loader` its seed."""
+    RNG states are restored; with `loader` its seed.
+
+    `weights="ema"` (for inference and export; not together with `optimizer`): the shadows of
+    ema_model.safetensors are loaded as the model's weights in place of the raw adapters, each cast to
+    its parameter's dtype; ValueError when the directory has none.
+
+    An `optimizer` that keeps an EMA (FusedAdamW(ema)) gets its shadows and ema_steps back from
+    ema_model.safetensors and the "ema" block: ValueError, before anything is written, when the saved
+    schedule's fields differ from the optimizer's, and under `strict` when the directory has no
+    shadows (strict=False: the shadows start from the loaded weights with ema_steps = 0). An
+    optimizer without an EMA ignores the file."""
     from safetensors.torch import load_file
 
     from . import ops
@@ -509,7 +542,34 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
     if state.get("world_size") != world:
         raise ValueError(f"{path}: written by {state.get('world_size')} ranks, loaded by {world}: the RNG "
                          f"states are per rank")
-    tensors = load_file(os.path.join(path, ADAPTER_WEIGHTS))
+    if weights not in ("raw", "ema"):
+        raise ValueError(f"weights must be 'raw' or 'ema', got {weights!r}")
+    has_ema = "ema" in state and os.path.isfile(os.path.join(path, ADAPTER_EMA))
+    if weights == "ema":
+        if optimizer is not None:
+            raise ValueError("load_adapter_checkpoint(weights='ema') with an optimizer: the moments belong to "
+                             "the raw weights")
+        if not has_ema:
+            raise ValueError(f"{path}: holds no EMA weights ({ADAPTER_EMA})")
+    if getattr(optimizer, "_ema_swapped", None) is not None:
+        raise RuntimeError("load_adapter_checkpoint: the optimizer's EMA weights are swapped in")
+    fname = ADAPTER_EMA if weights == "ema" else ADAPTER_WEIGHTS
+    tensors = load_file(os.path.join(path, fname))
+    # the optimizer's EMA: (saved shadows or None, ema_steps) once the checks below have passed
+    ema_plan = None
+    schedule = getattr(optimizer, "ema", None)
+    if schedule is not None:
+        if has_ema:
+            saved = {k: v for k, v in state["ema"].items() if k != "ema_steps"}
+            if saved != schedule.fields():
+                diff = sorted(k for k in set(saved) | set(schedule.fields()) if saved.get(k) != schedule.fields().get(k))
+                raise ValueError(f"{path}: the saved EMA schedule differs from the optimizer's in {', '.join(diff)} "
+                                 f"(saved {saved}, the optimizer's {schedule.fields()})")
+            ema_plan = (load_file(os.path.join(path, ADAPTER_EMA)), int(state["ema"]["ema_steps"]))
+        elif strict:
+            raise ValueError(f"{path}: holds no EMA weights ({ADAPTER_EMA}) and the optimizer keeps an EMA")
+        else:
+            ema_plan = (None, 0)
     opt_tensors = None
     if optimizer is not None:
         if "optimizer" not in state or not os.path.isfile(os.path.join(path, ADAPTER_OPTIMIZER)):
@@ -531,16 +591,22 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
         missing = [k for k in trainable if k not in tensors]
         unexpected = [k for k in tensors if k not in trainable]
         if strict and (missing or unexpected):
-            raise ValueError(f"{path}: {ADAPTER_WEIGHTS} missing keys {missing[:3]}, unexpected keys "
+            raise ValueError(f"{path}: {fname} missing keys {missing[:3]}, unexpected keys "
                              f"{unexpected[:3]} ({len(missing)} / {len(unexpected)} in all)")
         for k, p in trainable.items():
             t = tensors.get(k)
-            if t is not None and (t.shape != p.shape or (strict and t.dtype != p.dtype)):
+            want_dtype = torch.float32 if weights == "ema" else p.dtype  # the shadows are f32, cast on the copy
+            if t is not None and (t.shape != p.shape or (strict and t.dtype != want_dtype)):
                 raise ValueError(f"{path}: {k} is {t.dtype} {tuple(t.shape)}, the model's parameter "
                                  f"{p.dtype} {tuple(p.shape)}")
         plan = None
         if optimizer is not None:
             plan = _optimizer_plan(path, optimizer, named, state["optimizer"], opt_tensors, rank, strict)
+            if ema_plan is not None and ema_plan[0] is not None:
+                for p, name, step in plan:
+                    t = ema_plan[0].get(adapter_key(name))
+                    if step is not None and (t is None or t.shape != p.shape or t.dtype != torch.float32):
+                        raise ValueError(f"{path}: {ADAPTER_EMA} has no f32 {tuple(p.shape)} shadow of {name}")
     except Exception:
         if injected:
             _remove_adapters(model, requires_grad)
@@ -555,6 +621,8 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
         blk._dora_pack = None
     if optimizer is not None:
         _restore_optimizer(optimizer, state["optimizer"], opt_tensors, plan, rank, _model_device(model))
+        if ema_plan is not None:
+            _restore_ema(optimizer, plan, *ema_plan)
     if loader is not None and "loader" in state and hasattr(loader, "seed"):
         loader.seed = state["loader"]["seed"]
     if state.get("best_loss") is None:
@@ -617,6 +685,24 @@ def _restore_optimizer(optimizer, saved, opt_tensors, plan, rank, device):
     dev_state = opt_tensors.get(f"rng.device.rank{rank}")
     if dev_state is not None and device.type == "cuda":
         torch.cuda.set_rng_state(dev_state, device)
+
+
+@torch.no_grad()
+def _restore_ema(optimizer, plan, shadows, ema_steps):
+    """The shadows of every parameter that has optimizer state, in place where they exist; `shadows`
+    None: each starts again from its parameter's (loaded) value."""
+    for p, name, step in plan:
+        if step is None:
+            continue  # no state: the shadow is created with the moments at the first step
+        st = optimizer.state[p]
+        src = p.detach().float() if shadows is None else shadows[adapter_key(name)]
+        cur = st.get("ema")
+        if torch.is_tensor(cur) and cur.shape == src.shape and cur.dtype == torch.float32:
+            cur.copy_(src)  # in place: the chunk table's pointers stay valid
+        else:
+            st["ema"] = src.to(device=p.device, dtype=torch.float32, copy=True)
+    optimizer.ema_steps = int(ema_steps)
+    optimizer.ema_decay = optimizer.ema.decay_at(ema_steps) if ema_steps > 0 else None
 
 
 def latest_adapter_checkpoint(output_dir):

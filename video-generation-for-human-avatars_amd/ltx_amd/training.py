@@ -13,6 +13,7 @@ Differences that are deliberate and documented:
     quantile clamp takes the bounds as 0-dim device tensors instead of `float(t_low)`, which gives
     the same f32 result without the device->host round trip in every micro-step.
 """
+import contextlib
 import ctypes
 import functools
 import math
@@ -178,6 +179,73 @@ def schedule_from_config(config, dataloader=None):
     return (max_norm or None), schedule
 
 
+class EMASchedule:
+    """The decay of the exponential moving average of the trained weights as a pure function of n, the
+    optimizer steps taken including the current one: `decay_at(n)` is diffusers' EMAModel.get_decay
+    (training_utils.py; `--use_ema` in its training scripts) in Python float arithmetic. With
+    k = max(0, n - update_after_step - 1):
+      k == 0        0.0    (the shadow follows the weights)
+      use_warmup    1 - (1 + k / inv_gamma) ** (-power)
+      otherwise     (1 + k) / (10 + k)
+    then min(., decay), then max(., min_decay). Nothing is stored between steps, so a resumed run needs
+    only its step count. diffusers is not a dependency of this project and is not installed where the
+    tests run: the formula is pinned to its published behaviour only, by hand-computed values."""
+
+    FIELDS = ("decay", "use_warmup", "inv_gamma", "power", "update_after_step", "min_decay")
+
+    def __init__(self, decay, use_warmup=False, inv_gamma=1.0, power=2 / 3, update_after_step=0, min_decay=0.0):
+        decay, inv_gamma, power, min_decay = float(decay), float(inv_gamma), float(power), float(min_decay)
+        if not 0.0 < decay <= 1.0:
+            raise ValueError(f"ema_decay must be in (0, 1], got {decay}")
+        if int(update_after_step) != update_after_step or int(update_after_step) < 0:
+            raise ValueError(f"ema_update_after_step must be an integer >= 0, got {update_after_step}")
+        if not inv_gamma > 0.0:
+            raise ValueError(f"ema_inv_gamma must be > 0, got {inv_gamma}")
+        if not 0.0 <= min_decay <= decay:
+            raise ValueError(f"ema_min_decay must be in [0, ema_decay = {decay}], got {min_decay}")
+        self.decay = decay
+        self.use_warmup = bool(use_warmup)
+        self.inv_gamma = inv_gamma
+        self.power = power
+        self.update_after_step = int(update_after_step)
+        self.min_decay = min_decay
+
+    def decay_at(self, n):
+        k = max(0, int(n) - self.update_after_step - 1)
+        if k <= 0:
+            return 0.0
+        if self.use_warmup:
+            cur = 1 - (1 + k / self.inv_gamma) ** -self.power
+        else:
+            cur = (1 + k) / (10 + k)
+        return float(max(min(cur, self.decay), self.min_decay))
+
+    def fields(self):
+        """The constructor's arguments as a JSON-able dict (train_state.json's "ema" block)."""
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+
+def ema_from_config(config):
+    """EMASchedule or None from the optional config keys (setattr, or train.<key> in the YAML; not
+    TrainConfig fields): `ema_decay` (absent or 0: off), `ema_warmup` (a bool), `ema_inv_gamma`,
+    `ema_power`, `ema_update_after_step`, `ema_min_decay`; absent ones take EMASchedule's defaults.
+    NotImplementedError outside train_mode 'lora_audio' (the full mode's sharded Zero2AdamW is its own
+    path), ValueError for what EMASchedule refuses."""
+    decay = getattr(config, "ema_decay", None)
+    if decay is None or float(decay) == 0.0:
+        return None
+    train_mode = getattr(config, "train_mode", "full")
+    if train_mode != "lora_audio":
+        raise NotImplementedError(f"ema_decay with train_mode={train_mode!r}: the EMA of the trained weights "
+                                  f"rides FusedAdamW's step, which exists in lora_audio mode only")
+    kw = {}
+    for key, arg in (("ema_warmup", "use_warmup"), ("ema_inv_gamma", "inv_gamma"), ("ema_power", "power"),
+                     ("ema_update_after_step", "update_after_step"), ("ema_min_decay", "min_decay")):
+        if getattr(config, key, None) is not None:
+            kw[arg] = getattr(config, key)
+    return EMASchedule(decay, **kw)
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW (defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2; the
     reference constructs AdamW(trainable, lr) at training.py:270-271) with one ltx_adamw_step
@@ -189,14 +257,31 @@ class FusedAdamW(torch.optim.Optimizer):
     ltx_grad_sumsq_multi per (dtype, step) group over the chunk table, one ltx_grad_clip_coef, then
     ltx_adamw_multi_clip per group, which scales the gradient on the way in -- .grad itself stays
     unscaled. After such a step `grad_norm` (the pre-clip norm) and `clip_coef` are 0-dim f32 device
-    tensors; reading them syncs only at float()."""
+    tensors; reading them syncs only at float().
+
+    `ema` (an EMASchedule; None: off, and step() is today's, call for call): an exponential moving
+    average of every stepped parameter, updated inside the AdamW launch (ltx_adamw_multi_ema per (param
+    group, dtype, step) bucket, the clip's norm and coefficient launches in front of them unchanged when
+    max_grad_norm is set). state[p]["ema"] is the f32 shadow -- f32 for the bf16 caption projection too:
+    at decay 0.9999 the increment is below bf16's resolution and a bf16 shadow would stop moving, which
+    is where this departs from diffusers' EMAModel -- created with the moments as p.detach().float(),
+    the value before the first step; after a step s = s - omd (s - float(p)) with
+    omd = float32(1 - ema.decay_at(ema_steps)), three separately rounded f32 operations. `ema_steps`
+    counts the steps taken, `ema_decay` is the last step's decay. A parameter without a gradient at a
+    step is not averaged at that step (diffusers averages it anyway; no trainable parameter of this
+    model is ever without one). Parameters, moments and steps are bitwise those of ema=None.
+    ema_swap_in() / ema_swap_out() / the context manager ema_weights() install the shadows as the
+    weights (rounded to the parameter's dtype) for an evaluation or an export and put the live values
+    back; step() refuses to run in between."""
 
     CHUNK = 2048  # elements per block of the multi-tensor kernel
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 multi_tensor=True, max_grad_norm=None):
+                 multi_tensor=True, max_grad_norm=None, ema=None):
         if max_grad_norm is not None and not float(max_grad_norm) >= 0:
             raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+        if ema is not None and not isinstance(ema, EMASchedule):
+            raise TypeError(f"ema must be an EMASchedule or None, got {type(ema).__name__}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm))
         self.multi_tensor = multi_tensor
@@ -205,6 +290,11 @@ class FusedAdamW(torch.optim.Optimizer):
         self._clip_part = None  # f64 per-row partial sums of the norm pass
         # the last clipped step's device record: f64 sum of squares, f32 pre-clip norm, f32 coefficient
         self.clip_sumsq = self.grad_norm = self.clip_coef = None
+        self.ema = ema
+        self.ema_steps = 0  # optimizer steps taken with the EMA on
+        self.ema_decay = None  # the last step's decay (a Python float)
+        self._ema_stash = {}  # parameter -> the buffer its live value waits in while swapped in
+        self._ema_swapped = None  # the (device table, rows, is_bf16) launches of the swap-in to undo
 
     def _max_grad_norm(self):
         vals = {float(g.get("max_grad_norm") or 0.0) for g in self.param_groups}
@@ -218,9 +308,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._ema_swapped is not None:
+            raise RuntimeError("FusedAdamW.step() while the EMA weights are swapped in: call ema_swap_out() first")
         max_norm = self._max_grad_norm()
-        if max_norm > 0:
-            return self._step_clipped(max_norm)
+        if max_norm > 0 or self.ema is not None:
+            return self._step_tables(max_norm)
         for group in self.param_groups:
             b1, b2 = group["betas"]
             todo = []
@@ -247,22 +339,29 @@ class FusedAdamW(torch.optim.Optimizer):
                                    group["eps"], group["weight_decay"], st["step"])
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
-    def _table(self, items, dtype, slot=None):
+    def _table(self, items, dtype, slot=None, ema=False):
         """(device chunk table, rows) of `items`: int64 rows of (param, grad, exp_avg, exp_avg_sq,
         first element, count <= CHUNK). The table (~10^4 rows at LTX-2B: milliseconds of host time)
         is built once per set of buffers and reused while the parameter / grad / state storages
-        stay the same; `slot` is the cache entry (the dtype, for the one group the LoRA path has)."""
+        stay the same; `slot` is the cache entry (the dtype, for the one group the LoRA path has).
+        `ema`: the 8-field rows of the EMA entry points, (..., shadow = st["ema"], stash = 0), in a
+        cache entry of their own whose key holds the shadow pointers too."""
         slot = dtype if slot is None else slot
-        ptrs = [(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                 p.numel()) for p, g, st in items]
+        if ema:
+            slot = ("ema", slot)
+            ptrs = [(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                     p.numel(), st["ema"].data_ptr()) for p, g, st in items]
+        else:
+            ptrs = [(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                     p.numel()) for p, g, st in items]
         key = (dtype, tuple(ptrs))
         hit = self._table_cache.get(slot)
         if hit is not None and hit[0] == key:
             return hit[1], hit[2]
         rows = []
-        for pp, gp, ap, sp, n in ptrs:
+        for pp, gp, ap, sp, n, *shadow in ptrs:
             for start in range(0, n, self.CHUNK):
-                rows.append((pp, gp, ap, sp, start, min(self.CHUNK, n - start)))
+                rows.append((pp, gp, ap, sp, start, min(self.CHUNK, n - start)) + ((shadow[0], 0) if ema else ()))
         host = torch.tensor(rows, dtype=torch.int64).pin_memory()
         dev = host.to(items[0][0].device, non_blocking=True)
         nrows = len(rows)
@@ -279,28 +378,32 @@ class FusedAdamW(torch.optim.Optimizer):
                  float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                  float(group["weight_decay"]), int(step), ops._s())
 
-    def _step_clipped(self, max_norm):
-        """The step under global-norm clipping: every parameter with a gradient goes through the
-        table kernels, grouped by (param group, dtype, step). Launch order: the norm launches of
-        all groups (each writes its per-row partials behind the previous group's), the coefficient
-        launch, then one ltx_adamw_multi_clip per group."""
+    def _step_tables(self, max_norm):
+        """The step under global-norm clipping (max_norm > 0) and / or with the EMA: every parameter
+        with a gradient goes through the table kernels, grouped by (param group, dtype, step). Launch
+        order: when clipping, the norm launches of all groups (each writes its per-row partials behind
+        the previous group's) and the coefficient launch; then one AdamW launch per group --
+        ltx_adamw_multi_clip, or with the EMA ltx_adamw_multi_ema (given the coefficient when clipping)."""
         from . import _lib
+        ema = self.ema
+        what = "FusedAdamW(max_grad_norm)" if max_norm > 0 else "FusedAdamW(ema)"
+        kernels = "clip kernels" if max_norm > 0 else "EMA kernels"
         todo, device = [], None
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if not p.is_cuda:
-                    raise _lib.LtxHipError(f"FusedAdamW(max_grad_norm): the clip kernels need ROCm device "
+                    raise _lib.LtxHipError(f"{what}: the {kernels} need ROCm device "
                                            f"parameters, got one on {p.device}")
                 if p.dtype not in (torch.float32, torch.bfloat16):
-                    raise TypeError(f"FusedAdamW(max_grad_norm): expected f32 or bf16 parameters, got {p.dtype}")
+                    raise TypeError(f"{what}: expected f32 or bf16 parameters, got {p.dtype}")
                 if device is None:
                     device = p.device
                 elif p.device != device:
-                    raise ValueError(f"FusedAdamW(max_grad_norm): parameters on {device} and {p.device}; the "
-                                     f"global norm is taken on one device")
-        launches = []  # (device table, rows, is_bf16, group, step)
+                    raise ValueError(f"{what}: parameters on {device} and {p.device}; the table kernels "
+                                     f"(and the global norm) run on one device")
+        launches = []  # (device table, rows, is_bf16, group, step, the 6-field table of the norm pass)
         for gi, group in enumerate(self.param_groups):
             buckets = {}  # (dtype, step) -> items, in order of first appearance
             for p in group["params"]:
@@ -311,6 +414,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p)
                     st["exp_avg_sq"] = torch.zeros_like(p)
+                if ema is not None and "ema" not in st:
+                    # with the moments; later only where a restore brought moments without shadows
+                    st["ema"] = p.detach().float().clone()
                 st["step"] += 1
                 buckets.setdefault((p.dtype, st["step"]), []).append((p, p.grad.contiguous(), st))
             seen = {}
@@ -318,12 +424,28 @@ class FusedAdamW(torch.optim.Optimizer):
                 j = seen[dtype] = seen.get(dtype, -1) + 1
                 # the unclipped step's cache entry for the usual case: one group, one step count
                 slot = dtype if (gi, j) == (0, 0) else (dtype, gi, j)
-                dev, nrows = self._table(items, dtype, slot)
-                launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, group, step))
+                dev, nrows = self._table(items, dtype, slot, ema=ema is not None)
+                # the norm kernel walks 6-field rows: with the EMA's 8-field table the clip keeps its own
+                norm_dev = self._table(items, dtype, slot)[0] if (ema is not None and max_norm > 0) else dev
+                launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, group, step, norm_dev))
+        omd = None
+        if ema is not None:
+            self.ema_steps += 1
+            self.ema_decay = ema.decay_at(self.ema_steps)
+            omd = 1.0 - self.ema_decay  # in double; the entry point takes it as one f32
         if not launches:
             self.clip_sumsq = self.grad_norm = self.clip_coef = None
             return
-        total = sum(n for _, n, _, _, _ in launches)
+        if not max_norm > 0:
+            stream = ops._s()
+            for dev, nrows, is_bf16, group, step, _ in launches:
+                b1, b2 = group["betas"]
+                ops.call("ltx_adamw_multi_ema", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
+                         float(b2), float(group["eps"]), float(group["weight_decay"]), int(step), None, omd, stream)
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
+            return
+        total = sum(n for _, n, _, _, _, _ in launches)
         if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
             self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
         part = self._clip_part
@@ -333,18 +455,98 @@ class FusedAdamW(torch.optim.Optimizer):
         tail = rec[1:].view(torch.float32)
         stream = ops._s()
         off = 0
-        for dev, nrows, is_bf16, _, _ in launches:
+        for _, nrows, is_bf16, _, _, dev in launches:
             ops.call("ltx_grad_sumsq_multi", ops._p(dev), nrows, is_bf16,
                      ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
             off += nrows
         ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
-        for dev, nrows, is_bf16, group, step in launches:
+        for dev, nrows, is_bf16, group, step, _ in launches:
             b1, b2 = group["betas"]
+            if ema is not None:
+                ops.call("ltx_adamw_multi_ema", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
+                         float(b2), float(group["eps"]), float(group["weight_decay"]), int(step),
+                         ops._p(tail[1]), omd, stream)
+                continue
             ops.call("ltx_adamw_multi_clip", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
                      float(b2), float(group["eps"]), float(group["weight_decay"]), int(step),
                      ops._p(tail[1]), stream)
         self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
+
+    # ---- the averaged weights as the model's weights ---------------------------------------
+    def _swap_tables(self):
+        """[(device table, rows, is_bf16)] over every parameter that has a shadow, one per dtype: the
+        EMA rows with (param, 0, 0, 0, first element, count, shadow, stash). The stashes are allocated
+        on first use and kept; the tables are cached on the three pointers."""
+        by_dtype = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                st = self.state.get(p)
+                if not st or "ema" not in st or p.numel() == 0:
+                    continue
+                stash = self._ema_stash.get(p)
+                if stash is None or stash.shape != p.shape or stash.dtype != p.dtype or stash.device != p.device:
+                    stash = self._ema_stash[p] = torch.empty_like(p)
+                by_dtype.setdefault(p.dtype, []).append((p, st["ema"], stash))
+        out = []
+        for dtype, items in by_dtype.items():
+            ptrs = tuple((p.data_ptr(), s.data_ptr(), t.data_ptr(), p.numel()) for p, s, t in items)
+            slot = ("ema_swap", dtype)
+            hit = self._table_cache.get(slot)
+            if hit is None or hit[0] != ptrs:
+                rows = [(pp, 0, 0, 0, start, min(self.CHUNK, n - start), sp, tp)
+                        for pp, sp, tp, n in ptrs for start in range(0, n, self.CHUNK)]
+                host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+                dev = host.to(items[0][0].device, non_blocking=True)
+                hit = self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
+            out.append((hit[1], hit[2], 1 if dtype == torch.bfloat16 else 0))
+        return out
+
+    @torch.no_grad()
+    def ema_swap_in(self):
+        """Stash the live value of every parameter that has a shadow and install the shadow in its
+        place, rounded to the parameter's dtype (ltx_ema_load_multi, one launch per dtype); the
+        weight-derived caches are invalidated. RuntimeError without an EMA or while swapped in."""
+        from . import _lib
+        if self.ema is None:
+            raise RuntimeError("FusedAdamW.ema_swap_in(): this optimizer keeps no EMA (ema=None)")
+        if self._ema_swapped is not None:
+            raise RuntimeError("FusedAdamW.ema_swap_in(): the EMA weights are swapped in already")
+        for group in self.param_groups:
+            for p in group["params"]:
+                if "ema" in self.state.get(p, ()):
+                    if not p.is_cuda:
+                        raise _lib.LtxHipError(f"FusedAdamW(ema): the EMA kernels need ROCm device parameters, "
+                                               f"got one on {p.device}")
+                    if p.dtype not in (torch.float32, torch.bfloat16):
+                        raise TypeError(f"FusedAdamW(ema): expected f32 or bf16 parameters, got {p.dtype}")
+        launches = self._swap_tables()
+        stream = ops._s()
+        for dev, nrows, is_bf16 in launches:
+            ops.call("ltx_ema_load_multi", ops._p(dev), nrows, is_bf16, stream)
+        self._ema_swapped = launches
+        ops.bump_weight_generation()
+
+    @torch.no_grad()
+    def ema_swap_out(self):
+        """Put the stashed live values back (ltx_ema_restore_multi over the swap-in's tables).
+        RuntimeError when nothing is swapped in."""
+        if self._ema_swapped is None:
+            raise RuntimeError("FusedAdamW.ema_swap_out(): the EMA weights are not swapped in")
+        stream = ops._s()
+        for dev, nrows, is_bf16 in self._ema_swapped:
+            ops.call("ltx_ema_restore_multi", ops._p(dev), nrows, is_bf16, stream)
+        self._ema_swapped = None
+        ops.bump_weight_generation()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with optimizer.ema_weights():` runs its body under the averaged weights."""
+        self.ema_swap_in()
+        try:
+            yield self
+        finally:
+            self.ema_swap_out()
 
 
 class OverlapHooks:
@@ -581,7 +783,8 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
     steps taken before it, and "train/lr" is the rate that step used. An optimizer that clips
     (FusedAdamW(max_grad_norm)) adds "train/grad_norm", the pre-clip global norm of the step's
     gradients -- under data parallelism the averaged ones, the same on every rank -- read at the
-    same sync point as the loss."""
+    same sync point as the loss. An optimizer that averages (FusedAdamW(ema)) adds "train/ema_decay",
+    the decay that step's shadow update used."""
     model.train()
     accum = max(1, int(config.gradient_accumulation_steps))
 
@@ -615,6 +818,8 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
                            "train/lr": optimizer.param_groups[0]["lr"]}
                 if getattr(optimizer, "grad_norm", None) is not None:
                     payload["train/grad_norm"] = float(optimizer.grad_norm)
+                if getattr(optimizer, "ema", None) is not None:
+                    payload["train/ema_decay"] = optimizer.ema_decay  # a host value: no sync
                 for k, v in (loss_dict or {}).items():
                     if not k.startswith("_"):
                         payload[f"train/{k}"] = float(v)
@@ -642,7 +847,19 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     The optimizer step's optional keys (schedule_from_config; absent = today's step, call for call):
     `max_grad_norm` clips the global gradient norm inside FusedAdamW and logs "train/grad_norm";
     `lr_scheduler` / `lr_warmup_steps` / `lr_total_steps` set every step's lr from global_step
-    (LRSchedule), so a resumed run continues the schedule with no saved state of its own."""
+    (LRSchedule), so a resumed run continues the schedule with no saved state of its own.
+
+    `ema_decay` (ema_from_config; absent or 0 = today's run, call for call and file for file; with
+    `ema_warmup`, `ema_inv_gamma`, `ema_power`, `ema_update_after_step`, `ema_min_decay`): FusedAdamW
+    keeps an f32 exponential moving average of the trained weights inside its step and
+    "train/ema_decay" is logged per step. With a val_dataloader a second validation pass runs under
+    the averaged weights (optimizer.ema_weights()), logged as {"val/loss_ema", "val/epoch"}, after the
+    normal one and before the adapter checkpoint is written. With save_adapters the directory gains
+    ema_model.safetensors and an "ema" block in train_state.json, which a resumed run with the same
+    schedule restores (bitwise the uninterrupted run, shadows included). The merged per-epoch
+    checkpoints stay the raw weights'. The shadow update runs after the gradient all-reduce, inside
+    step(), and needs no collective: every rank's shadows are identical by construction (run at world
+    size 1 only, like the rest of data parallelism here)."""
     import os
 
     from . import io
@@ -657,6 +874,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                   f"whole model already, and its sharded optimizer state is not saved)")
     # the optional optimizer-step keys, validated before anything is built
     max_grad_norm, lr_schedule = schedule_from_config(config, dataloader)
+    ema = ema_from_config(config)
     device = device or model.device
     patchifier = model.patchifier or SymmetricPatchifier(1)
     if getattr(config, "gradient_checkpointing", False):
@@ -667,7 +885,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                 target_shift_terminal=config.rf_target_shift_terminal,
                                 sampler=config.rf_sampler, shift=config.rf_shift)
     params = [p for p in model.parameters() if p.requires_grad]
-    optimizer =FusedAdamW(params, lr=config.learning_rate, max_grad_norm=max_grad_norm)
+    optimizer = FusedAdamW(params, lr=config.learning_rate, max_grad_norm=max_grad_norm, ema=ema)
     reducer = None
     if dist.is_available() and dist.is_initialized():
         order = model.grad_ready_order() if hasattr(model, "grad_ready_order") else None
@@ -694,6 +912,12 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                       prompt_attention_mask, device)
             if log_fn is not None:
                 log_fn({"val/loss": val_loss, "val/epoch": epoch}, global_step)
+            if ema is not None:
+                with optimizer.ema_weights():
+                    val_loss = validate_epoch(model, val_dataloader, rf, patchifier, config, prompt_embeds,
+                                              prompt_attention_mask, device)
+                if log_fn is not None:
+                    log_fn({"val/loss_ema": val_loss, "val/epoch": epoch}, global_step)
         if log_fn is not None:
             log_fn({"train/epoch_loss": epoch_loss}, global_step)
         saving = config.output_dir and (epoch + 1) % config.save_every_n_epochs == 0
