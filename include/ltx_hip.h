@@ -503,6 +503,52 @@ int ltx_ema_load_multi(const int64_t* table, int64_t nchunks, int is_bf16, void*
 /* param[i] = stash[i] over the EMA table's rows: undoes ltx_ema_load_multi. */
 int ltx_ema_restore_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream);
 
+/* ---- Prodigy, the learning-rate-free optimizer, over the chunk table (csrc/prodigy.hip) ---------- */
+/* The Prodigy table: device int64 [nchunks][10] of (param, grad, exp_avg, exp_avg_sq, first element,
+ * count <= 2048, s, p0, shadow, stash). exp_avg, exp_avg_sq, s and p0 have the parameter's dtype; shadow
+ * (the f32 EMA of the parameter) and stash are 0 without the EMA, and the Prodigy entry points never read
+ * stash. One block per row, 256 threads; rows whose tensors are all 16-byte aligned move 16 bytes per
+ * lane per access, the others one element.
+ *
+ * The record: 8 device f64 { d, d_max, d_numerator, d_denom, d_hat, dlr, k, applied }, 8-byte aligned;
+ * the caller initialises it to { d0, d0, 0, 0, 0, 0, 0, 0 }. Hyper-parameters arrive as doubles; every
+ * scalar derived from d is formed in f64 on the device and cast to f32 where torch would cast a Python
+ * float alpha / value. R rounds to the tensor's dtype (identity for f32).
+ *
+ * ltx_prodigy_moments_multi (pass 1), per element, with d and k read from the record and
+ * dlr = d lr bc, bc = use_bias_correction ? sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) : 1:
+ *   g    = grad;  g = R(g * *coef_or_null) when given (grad itself is not written);
+ *   g    = R(fma(coupled_weight_decay, p, g)) when coupled_weight_decay != 0;
+ *   exp_avg    = R(fma(f32(d (1 - beta1)), g, R(exp_avg * beta1)))
+ *   exp_avg_sq = R(fma(f32(d d (1 - beta2)), g * g, R(exp_avg_sq * beta2)))
+ *   s          = R(fma(f32((d / d0) (safeguard_warmup ? d : dlr)), g, R(s * beta3)))
+ * (torch's add_(alpha) / addcmul_ are one fused multiply-add on the device), and
+ *   part[2 b] = sum over row b of R(p0 - p) * g (an f32 product, added in f64),
+ *   part[2 b + 1] = sum over row b of the stored |s|,
+ * overwritten, in a fixed order: each lane its elements in order, the wave butterfly, four waves in
+ * order. A second dtype's launch is given part + 2 * the first's nchunks. */
+int ltx_prodigy_moments_multi(const int64_t* table, int64_t nchunks, int is_bf16, const double* record, double lr,
+                              double beta1, double beta2, double beta3, double d0, double coupled_weight_decay,
+                              int use_bias_correction, int safeguard_warmup, const float* coef_or_null, double* part,
+                              void* stream);
+/* One block adds the nrows (num, den) pairs of part in a fixed order (strided sums, a fixed-shape tree)
+ * and updates the record in f64:
+ *   dlr = d lr bc;  d_denom = SUM den;  if d_denom == 0: applied = 0, nothing else changes; otherwise
+ *   d_numerator = beta3 d_numerator + (d / d0) dlr SUM num;  d_hat = d_coef d_numerator / d_denom;
+ *   if d == d0: d = max(d, d_hat);  d_max = max(d_max, d_hat);  d = min(d_max, d growth_rate);
+ *   k = k + 1;  applied = 1. */
+int ltx_prodigy_d_update(const double* part, int64_t nrows, double* record, double lr, double beta1, double beta2,
+                         double beta3, double d0, double d_coef, double growth_rate, int use_bias_correction,
+                         void* stream);
+/* Pass 2, a no-op when the record's applied is 0; per element, with the record's new d and the dlr the
+ * step started from:
+ *   den = R(R(sqrt(exp_avg_sq)) + f32(d eps));
+ *   p = R(fma(f32(-decoupled_weight_decay dlr), p, p)) when decoupled_weight_decay != 0;
+ *   p = R(fma(f32(-dlr), exp_avg / den, p))     (torch's addcdiv_ on the device);
+ * and with ema != 0, shadow <- shadow - one_minus_decay * (shadow - float(p)) as in ltx_adamw_multi_ema. */
+int ltx_prodigy_apply_multi(const int64_t* table, int64_t nchunks, int is_bf16, const double* record, double eps,
+                            double decoupled_weight_decay, int ema, float one_minus_decay, void* stream);
+
 /* ---- train_mode='full' parameter gradients (csrc/paramgrad.hip) --------- */
 /* Weight gradient of the q/k RMSNorm weights: partials[(which * splits + s) * D + d] (f32) =
  * sum over row split s of bf16(dn * bf16(x_raw * rstd)), dn = RoPE^T of the incoming gradient (the

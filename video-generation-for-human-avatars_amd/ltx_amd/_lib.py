@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LTX_HIP_LIB", os.path.join(_HERE, "libltxhip.so"))
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
 _f32 = ctypes.c_float
+_f64 = ctypes.c_double
 _p = ctypes.c_void_p
 
 # name -> argtypes (all return int status)
@@ -112,6 +113,9 @@ _SIGNATURES = {
     "ltx_adamw_multi_ema": [_p, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _p, _f32, _p],
     "ltx_ema_load_multi": [_p, _i64, _i32, _p],
     "ltx_ema_restore_multi": [_p, _i64, _i32, _p],
+    "ltx_prodigy_moments_multi": [_p, _i64, _i32, _p, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _i32, _p, _p, _p],
+    "ltx_prodigy_d_update": [_p, _i64, _p, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p],
+    "ltx_prodigy_apply_multi": [_p, _i64, _i32, _p, _f64, _f64, _i32, _f32, _p],
     "ltx_qk_norm_wgrad": [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _p, _p, _p, _i64,
                           _i64, _i64, _i64, _i32, _i64, _p, _p],
     "ltx_group_colsum": [_p, _i64, _p, _i64, _p, _p, _i32, _i64, _i64, _i64, _i64, _p, _p],

@@ -83,7 +83,8 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
         output_dir=t.get("output_dir"),
         batch_size=int(t["batch_size"]) if "batch_size" in t else None,
         num_epochs=int(t["num_epochs"]) if "num_epochs" in t else None,
-        learning_rate=float(t["learning_rate"]) if "learning_rate" in t else None,
+        # `learning_rate: null` reads as unset (Prodigy's 1.0, training.optimizer_from_config)
+        learning_rate=float(t["learning_rate"]) if t.get("learning_rate") is not None else None,
         lora_rank=int(t.get("lora_rank", 8)),
         lora_alpha=int(t.get("lora_alpha", 8)),
         gradient_checkpointing=bool(t.get("gradient_checkpointing", False)),
@@ -162,4 +163,19 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
             setattr(config, key, float(t[key]))
     if "ema_update_after_step" in t:
         setattr(config, "ema_update_after_step", int(t["ema_update_after_step"]))
+    # and the keys training.optimizer_from_config reads (and validates): `train.optimizer` ("adamw", the
+    # same as absent, or "prodigy": the learning-rate-free optimizer, with `learning_rate: 1.0` or null);
+    # `train.weight_decay`, `train.adam_beta1`, `train.adam_beta2`, `train.adam_eps` (absent = the chosen
+    # optimizer's defaults); and Prodigy's own `train.prodigy_d0`, `train.prodigy_d_coef`,
+    # `train.prodigy_growth_rate`, `train.prodigy_beta3` (floats) and `train.prodigy_use_bias_correction`,
+    # `train.prodigy_safeguard_warmup`, `train.prodigy_decouple` (bools)
+    if "optimizer" in t:
+        setattr(config, "optimizer", str(t["optimizer"]))
+    for key in ("weight_decay", "adam_beta1", "adam_beta2", "adam_eps", "prodigy_d0", "prodigy_d_coef",
+                "prodigy_growth_rate", "prodigy_beta3"):
+        if key in t:
+            setattr(config, key, float(t[key]))
+    for key in ("prodigy_use_bias_correction", "prodigy_safeguard_warmup", "prodigy_decouple"):
+        if key in t:
+            setattr(config, key, bool(t[key]))
     return config

@@ -359,6 +359,14 @@ def _write_json(path, obj):
         f.write("\n")
 
 
+_PRODIGY_STATE = ("s", "p0")
+
+
+def _is_prodigy(optimizer):
+    """training.FusedProdigy (or a subclass), without importing training here"""
+    return optimizer is not None and hasattr(optimizer, "RECORD") and hasattr(optimizer, "ensure_record")
+
+
 def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, loader=None,
                             metadata: Optional[dict] = None):
     """Write the adapter checkpoint directory `path` (safetensors and JSON only) and return it:
@@ -379,6 +387,11 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
     * train_state.json, written last: the format version, `train_state`'s epoch / global_step /
       best_loss, the world size, the optimizer's hyper-parameters and per-parameter step,
       `loader`'s seed, and with an EMA the block "ema": the EMASchedule's fields and ema_steps.
+
+    With a training.FusedProdigy optimizer.safetensors also holds s.<parameter name> / p0.<parameter name>
+    and train_state.json the block "prodigy": {"hyper": the hyper-parameters (FusedProdigy.hyper()),
+    "record": the device record's float64 values as float.hex() strings}. A directory written with another
+    optimizer has neither.
 
     Everything is written under `path`.tmp and moved into place with os.replace, so a checkpoint is
     complete or absent. Under torch.distributed every rank calls this (the RNG states are gathered);
@@ -417,10 +430,17 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
                     steps[name] = int(st["step"])
                     opt_tensors["exp_avg." + name] = st["exp_avg"].detach().cpu().contiguous()
                     opt_tensors["exp_avg_sq." + name] = st["exp_avg_sq"].detach().cpu().contiguous()
+                    for k in _PRODIGY_STATE:  # FusedProdigy's two further tensors per parameter
+                        if k in st:
+                            opt_tensors[f"{k}.{name}"] = st[k].detach().cpu().contiguous()
         opt_tensors.update(rng)
         hyper = [{k: _plain(v) for k, v in g.items() if k != "params" and _plain(v) is not None}
                  for g in optimizer.param_groups]
         state["optimizer"] = {"class": type(optimizer).__name__, "param_groups": hyper, "step": steps}
+        if _is_prodigy(optimizer):
+            record = optimizer.ensure_record(_model_device(model)).tolist()
+            state["prodigy"] = {"hyper": optimizer.hyper(),
+                                "record": {k: float(v).hex() for k, v in zip(optimizer.RECORD, record)}}
     ema_tensors = None
     schedule = getattr(optimizer, "ema", None)
     if schedule is not None:
@@ -525,7 +545,11 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
     ema_model.safetensors and the "ema" block: ValueError, before anything is written, when the saved
     schedule's fields differ from the optimizer's, and under `strict` when the directory has no
     shadows (strict=False: the shadows start from the loaded weights with ema_steps = 0). An
-    optimizer without an EMA ignores the file."""
+    optimizer without an EMA ignores the file.
+
+    A training.FusedProdigy gets s, p0 and its record back in place from the "prodigy" block; ValueError,
+    before anything is written, when the directory was written by the other kind of optimizer (a Prodigy
+    checkpoint into FusedAdamW or the reverse) or with other Prodigy hyper-parameters."""
     from safetensors.torch import load_file
 
     from . import ops
@@ -574,6 +598,7 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
     if optimizer is not None:
         if "optimizer" not in state or not os.path.isfile(os.path.join(path, ADAPTER_OPTIMIZER)):
             raise ValueError(f"{path}: holds no optimizer state")
+        _check_prodigy(path, optimizer, state)
         opt_tensors = load_file(os.path.join(path, ADAPTER_OPTIMIZER))
     want = (list(config["target_modules"]), block["groups"])
     have = _adapter_layout(model)
@@ -620,7 +645,8 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
         blk._pack = blk._pack_key = None
         blk._dora_pack = None
     if optimizer is not None:
-        _restore_optimizer(optimizer, state["optimizer"], opt_tensors, plan, rank, _model_device(model))
+        _restore_optimizer(optimizer, state["optimizer"], opt_tensors, plan, rank, _model_device(model),
+                           state.get("prodigy"))
         if ema_plan is not None:
             _restore_ema(optimizer, plan, *ema_plan)
     if loader is not None and "loader" in state and hasattr(loader, "seed"):
@@ -628,6 +654,24 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
     if state.get("best_loss") is None:
         state["best_loss"] = float("inf")
     return state
+
+
+def _check_prodigy(path, optimizer, state):
+    """ValueError when the checkpoint's optimizer kind (a "prodigy" block or none) or Prodigy's
+    hyper-parameters differ from the live optimizer's: its moments mean something else then."""
+    saved = state.get("prodigy")
+    if (saved is not None) != _is_prodigy(optimizer):
+        kinds = ("Prodigy", type(optimizer).__name__) if saved is not None else ("AdamW", "Prodigy")
+        raise ValueError(f"{path}: holds {kinds[0]} optimizer state, the live optimizer is {kinds[1]}")
+    if saved is None:
+        return
+    live = optimizer.hyper()
+    if saved.get("hyper") != live:
+        diff = sorted(k for k in set(saved.get("hyper") or {}) | set(live) if (saved.get("hyper") or {}).get(k) != live.get(k))
+        raise ValueError(f"{path}: the saved Prodigy hyper-parameters differ from the optimizer's in {', '.join(diff)}")
+    missing = [k for k in optimizer.RECORD if k not in (saved.get("record") or {})]
+    if missing:
+        raise ValueError(f"{path}: the prodigy record lacks {', '.join(missing)}")
 
 
 def _optimizer_plan(path, optimizer, named, saved, opt_tensors, rank, strict):
@@ -644,7 +688,7 @@ def _optimizer_plan(path, optimizer, named, saved, opt_tensors, rank, strict):
             if name is None:
                 raise ValueError(f"{path}: the optimizer holds a parameter that is not the model's")
             step = saved["step"].get(name)
-            for k in ("exp_avg.", "exp_avg_sq."):
+            for k in ("exp_avg.", "exp_avg_sq.") + (tuple(k + "." for k in _PRODIGY_STATE) if _is_prodigy(optimizer) else ()):
                 t = opt_tensors.get(k + name)
                 if (t is None) != (step is None):
                     raise ValueError(f"{path}: {k + name} and the step of {name} do not go together")
@@ -663,7 +707,7 @@ def _optimizer_plan(path, optimizer, named, saved, opt_tensors, rank, strict):
 
 
 @torch.no_grad()
-def _restore_optimizer(optimizer, saved, opt_tensors, plan, rank, device):
+def _restore_optimizer(optimizer, saved, opt_tensors, plan, rank, device, saved_prodigy=None):
     for group, hyper in zip(optimizer.param_groups, saved["param_groups"]):
         for k, v in hyper.items():
             group[k] = tuple(v) if isinstance(group.get(k), tuple) and isinstance(v, list) else v
@@ -672,7 +716,7 @@ def _restore_optimizer(optimizer, saved, opt_tensors, plan, rank, device):
             optimizer.state.pop(p, None)
             continue
         st = optimizer.state[p]
-        for k in ("exp_avg", "exp_avg_sq"):
+        for k in ("exp_avg", "exp_avg_sq") + (_PRODIGY_STATE if _is_prodigy(optimizer) else ()):
             src = opt_tensors[f"{k}.{name}"]
             cur = st.get(k)
             if torch.is_tensor(cur) and cur.shape == src.shape and cur.dtype == src.dtype:
@@ -681,6 +725,9 @@ def _restore_optimizer(optimizer, saved, opt_tensors, plan, rank, device):
                 st[k] = src.to(p.device, copy=True)
         cur = st.get("step")
         st["step"] = cur.fill_(step) if torch.is_tensor(cur) else int(step)
+    if _is_prodigy(optimizer):
+        values = [float.fromhex(saved_prodigy["record"][k]) for k in optimizer.RECORD]
+        optimizer.ensure_record(device).copy_(torch.tensor(values, dtype=torch.float64))  # in place: step() holds it
     torch.set_rng_state(opt_tensors[f"rng.cpu.rank{rank}"])
     dev_state = opt_tensors.get(f"rng.device.rank{rank}")
     if dev_state is not None and device.type == "cuda":

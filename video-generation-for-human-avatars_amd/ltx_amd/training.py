@@ -549,6 +549,295 @@ class FusedAdamW(torch.optim.Optimizer):
             self.ema_swap_out()
 
 
+class FusedProdigy(FusedAdamW):
+    """Prodigy (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner"; the
+    published prodigyopt.Prodigy for one parameter group with fsdp_in_use = False), the optimizer that
+    estimates its own step size d: `lr` stays at 1.0 (times a schedule's factor). The statement is DESIGN.md's
+    Prodigy section and tests/prodigy_utils.ProdigyStatement. d, d_max, d_numerator and the step count k live
+    in `record`, a float64 device tensor (RECORD names its eight fields), and a step never reads it back:
+
+      [ltx_grad_sumsq_multi per dtype, ltx_grad_clip_coef]      with max_grad_norm, as FusedAdamW
+      ltx_prodigy_moments_multi per dtype   exp_avg, exp_avg_sq, s with the old d; f64 partials per row
+      ltx_prodigy_d_update                  the f64 update of the record
+      ltx_prodigy_apply_multi per dtype     the parameter step (a no-op where the sum of |s| was 0) and, with
+                                            `ema`, the shadow update of FusedAdamW(ema)
+
+    state[p] holds exp_avg, exp_avg_sq, s and p0 in the parameter's dtype (p0: the value before the first
+    step) and "step", the steps this parameter took. Parameters without a gradient are skipped and keep
+    everything. A step with lr == 0 launches nothing and changes nothing. The public surface is FusedAdamW's
+    (max_grad_norm, grad_norm / clip_coef, ema, ema_swap_in / ema_swap_out / ema_weights) plus `record` and
+    `d`, a 0-dim float64 device tensor that syncs only at float(). One parameter group only.
+
+    Two departures from the published code: the factor (d / d0) dlr multiplies the summed numerator once
+    instead of every tensor's dot product, and a bf16 tensor's dot product is not rounded to bf16 before it
+    is added (products in f32, sums in f64, fixed order: bitwise reproducible, the same on every rank)."""
+
+    RECORD = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "dlr", "k", "applied")
+    HYPER = ("betas", "beta3", "eps", "weight_decay", "decouple", "use_bias_correction", "safeguard_warmup",
+             "d0", "d_coef", "growth_rate")
+    ROW = 10  # int64 fields per row of the Prodigy chunk table
+
+    def __init__(self, params, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0,
+                 decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
+                 growth_rate=float("inf"), max_grad_norm=None, ema=None):
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must be in [0, 1), got {betas}")
+        if beta3 is not None and not 0.0 <= float(beta3) < 1.0:
+            raise ValueError(f"beta3 must be in [0, 1), got {beta3}")
+        if not float(eps) > 0.0:
+            raise ValueError(f"eps must be > 0, got {eps}")
+        if not float(weight_decay) >= 0.0:
+            raise ValueError(f"weight_decay must be >= 0, got {weight_decay}")
+        if not (float(d0) > 0.0 and math.isfinite(float(d0))):
+            raise ValueError(f"d0 must be a finite value > 0, got {d0}")
+        if not float(d_coef) > 0.0:
+            raise ValueError(f"d_coef must be > 0, got {d_coef}")
+        if not float(growth_rate) > 0.0:
+            raise ValueError(f"growth_rate must be > 0, got {growth_rate}")
+        super().__init__(params, lr=lr, betas=(b1, b2), eps=float(eps), weight_decay=float(weight_decay),
+                         max_grad_norm=max_grad_norm, ema=ema)
+        extra = dict(beta3=None if beta3 is None else float(beta3), decouple=bool(decouple),
+                     use_bias_correction=bool(use_bias_correction), safeguard_warmup=bool(safeguard_warmup),
+                     d0=float(d0), d_coef=float(d_coef), growth_rate=float(growth_rate))
+        self.defaults.update(extra)
+        for group in self.param_groups:
+            for k, v in extra.items():
+                group.setdefault(k, v)
+        self._one_group()
+        self.record = None  # the float64 device record, made with the first step (or a restore)
+        self._prodigy_part = None  # f64 (num, den) partials per row
+
+    def _one_group(self):
+        if len(self.param_groups) != 1:
+            raise ValueError(f"FusedProdigy takes one parameter group, got {len(self.param_groups)}: d is "
+                             f"estimated over all parameters together")
+        return self.param_groups[0]
+
+    def hyper(self):
+        """The hyper-parameters that shape the trajectory besides lr, as a JSON-able dict: floats as
+        float.hex() strings (growth_rate is inf by default), flags as bools, beta3 None when derived."""
+        group = self._one_group()
+        out = {}
+        for k in self.HYPER:
+            v = group[k]
+            if isinstance(v, tuple):
+                out[k] = [float(x).hex() for x in v]
+            elif isinstance(v, bool) or v is None:
+                out[k] = v
+            else:
+                out[k] = float(v).hex()
+        return out
+
+    def ensure_record(self, device=None):
+        """The record, created as {d0, d0, 0, ...} on the parameters' device when it does not exist yet."""
+        if self.record is None:
+            group = self._one_group()
+            if device is None:
+                device = next((p.device for p in group["params"]), torch.device("cpu"))
+            d0 = float(group["d0"])
+            self.record = torch.tensor([d0, d0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float64, device=device)
+        return self.record
+
+    @property
+    def d(self):
+        """The step-size estimate: a 0-dim float64 view of the device record (float() syncs)."""
+        return self.ensure_record()[0]
+
+    def _prodigy_table(self, items, dtype):
+        """(device table, rows) of ROW-field rows (param, grad, exp_avg, exp_avg_sq, first element, count,
+        s, p0, shadow or 0, 0), cached on the buffers' pointers like FusedAdamW._table."""
+        ptrs = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
+                      st["s"].data_ptr(), st["p0"].data_ptr(), st["ema"].data_ptr() if self.ema is not None else 0)
+                     for p, g, st in items)
+        slot = ("prodigy", dtype)
+        hit = self._table_cache.get(slot)
+        if hit is not None and hit[0] == ptrs:
+            return hit[1], hit[2]
+        rows = [(pp, gp, ap, vp, start, min(self.CHUNK, n - start), sp, p0p, ep, 0)
+                for pp, gp, ap, vp, n, sp, p0p, ep in ptrs for start in range(0, n, self.CHUNK)]
+        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+        dev = host.to(items[0][0].device, non_blocking=True)
+        self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
+        return dev, len(rows)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import _lib
+        if self._ema_swapped is not None:
+            raise RuntimeError("FusedProdigy.step() while the EMA weights are swapped in: call ema_swap_out() first")
+        group = self._one_group()
+        max_norm = self._max_grad_norm()
+        lr = float(group["lr"])
+        if lr == 0.0:
+            # the published code returns before any state moves; nothing is launched
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            return
+        ema = self.ema
+        device = None
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if not p.is_cuda:
+                raise _lib.LtxHipError(f"FusedProdigy: the Prodigy kernels need ROCm device parameters, got one "
+                                       f"on {p.device}")
+            if p.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"FusedProdigy: expected f32 or bf16 parameters, got {p.dtype}")
+            if device is None:
+                device = p.device
+            elif p.device != device:
+                raise ValueError(f"FusedProdigy: parameters on {device} and {p.device}; the table kernels (and "
+                                 f"the sums behind d) run on one device")
+        buckets = {}  # dtype -> items, in order of first appearance
+        for p in group["params"]:
+            if p.grad is None or p.numel() == 0:
+                continue
+            st = self.state[p]
+            if not st:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p)
+                st["exp_avg_sq"] = torch.zeros_like(p)
+            if "s" not in st:  # with the moments, before anything moves
+                st["s"] = torch.zeros_like(p)
+                st["p0"] = p.detach().clone()
+            if ema is not None and "ema" not in st:
+                st["ema"] = p.detach().float().clone()
+            st["step"] += 1
+            buckets.setdefault(p.dtype, []).append((p, p.grad.contiguous(), st))
+        if not buckets:
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            return
+        rec = self.ensure_record(device)
+        if rec.device != device:
+            raise ValueError(f"FusedProdigy: the record is on {rec.device}, the parameters on {device}")
+        launches = []  # (Prodigy table, rows, is_bf16, the 6-field table of the norm pass or None)
+        for dtype, items in buckets.items():
+            dev, nrows = self._prodigy_table(items, dtype)
+            norm_dev = self._table(items, dtype)[0] if max_norm > 0 else None
+            launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, norm_dev))
+        omd = 0.0
+        if ema is not None:
+            self.ema_steps += 1
+            self.ema_decay = ema.decay_at(self.ema_steps)
+            omd = 1.0 - self.ema_decay  # in double; the entry point takes it as one f32
+        total = sum(n for _, n, _, _ in launches)
+        if self._prodigy_part is None or self._prodigy_part.numel() < 2 * total or self._prodigy_part.device != device:
+            self._prodigy_part = torch.empty(2 * total, dtype=torch.float64, device=device)
+        part = self._prodigy_part
+        stream = ops._s()
+        coef = None
+        if max_norm > 0:
+            if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
+                self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
+            clip_rec = torch.empty(2, dtype=torch.float64, device=device)  # fresh per step, as FusedAdamW's
+            tail = clip_rec[1:].view(torch.float32)
+            off = 0
+            for _, nrows, is_bf16, norm_dev in launches:
+                ops.call("ltx_grad_sumsq_multi", ops._p(norm_dev), nrows, is_bf16,
+                         ctypes.c_void_p(self._clip_part.data_ptr() + 8 * off), stream)
+                off += nrows
+            ops.call("ltx_grad_clip_coef", ops._p(self._clip_part), total, float(max_norm), ops._p(clip_rec), stream)
+            self.clip_sumsq, self.grad_norm, self.clip_coef = clip_rec[0], tail[0], tail[1]
+            coef = ops._p(tail[1])
+        else:
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+        b1, b2 = (float(b) for b in group["betas"])
+        b3 = math.sqrt(b2) if group["beta3"] is None else float(group["beta3"])
+        d0, wd = float(group["d0"]), float(group["weight_decay"])
+        decouple, use_bc = bool(group["decouple"]), int(bool(group["use_bias_correction"]))
+        off = 0
+        for dev, nrows, is_bf16, _ in launches:
+            ops.call("ltx_prodigy_moments_multi", ops._p(dev), nrows, is_bf16, ops._p(rec), lr, b1, b2, b3, d0,
+                     0.0 if decouple else wd, use_bc, int(bool(group["safeguard_warmup"])), coef,
+                     ctypes.c_void_p(part.data_ptr() + 16 * off), stream)
+            off += nrows
+        ops.call("ltx_prodigy_d_update", ops._p(part), total, ops._p(rec), lr, b1, b2, b3, d0,
+                 float(group["d_coef"]), float(group["growth_rate"]), use_bc, stream)
+        for dev, nrows, is_bf16, _ in launches:
+            ops.call("ltx_prodigy_apply_multi", ops._p(dev), nrows, is_bf16, ops._p(rec), float(group["eps"]),
+                     wd if decouple else 0.0, 1 if ema is not None else 0, omd, stream)
+        ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
+
+
+OPTIMIZERS = ("adamw", "prodigy")
+_PRODIGY_KEYS = (("prodigy_d0", "d0", float), ("prodigy_d_coef", "d_coef", float),
+                 ("prodigy_growth_rate", "growth_rate", float), ("prodigy_beta3", "beta3", float),
+                 ("prodigy_use_bias_correction", "use_bias_correction", bool),
+                 ("prodigy_safeguard_warmup", "safeguard_warmup", bool), ("prodigy_decouple", "decouple", bool))
+
+
+class OptimizerSpec:
+    """What optimizer_from_config decided: `kind` ("adamw" or "prodigy"), `lr` and the constructor's other
+    keyword arguments -- only those the config names, so absent keys leave the class's defaults (and for
+    AdamW today's constructor call). build() makes the optimizer."""
+
+    def __init__(self, kind, lr, kwargs):
+        self.kind, self.lr, self.kwargs = kind, lr, dict(kwargs)
+
+    def build(self, params, max_grad_norm=None, ema=None):
+        cls = FusedProdigy if self.kind == "prodigy" else FusedAdamW  # the module's names at call time
+        return cls(params, lr=self.lr, max_grad_norm=max_grad_norm, ema=ema, **self.kwargs)
+
+
+def optimizer_from_config(config):
+    """OptimizerSpec from the optional config keys (setattr, or train.<key> in the YAML; not TrainConfig
+    fields), validated here, before anything is built: `optimizer` ("adamw", also when absent, or
+    "prodigy"), `weight_decay`, `adam_beta1`, `adam_beta2`, `adam_eps` (absent: the chosen optimizer's
+    defaults) and, with Prodigy, `prodigy_d0`, `prodigy_d_coef`, `prodigy_growth_rate`, `prodigy_beta3`,
+    `prodigy_use_bias_correction`, `prodigy_safeguard_warmup`, `prodigy_decouple`. The rate is
+    config.learning_rate; with Prodigy None means 1.0. ValueError for another optimizer name, a value out
+    of range, or a prodigy_* key without `optimizer: prodigy`; NotImplementedError for Prodigy outside
+    train_mode 'lora_audio' or with use_deepspeed (the sharded Zero2AdamW step is its own path)."""
+    kind = getattr(config, "optimizer", None)
+    kind = "adamw" if kind is None else kind
+    if kind not in OPTIMIZERS:
+        raise ValueError(f"optimizer {kind!r} is not one of {', '.join(OPTIMIZERS)}")
+    kw = {}
+    b1, b2 = getattr(config, "adam_beta1", None), getattr(config, "adam_beta2", None)
+    if b1 is not None or b2 is not None:
+        betas = (0.9 if b1 is None else float(b1), 0.999 if b2 is None else float(b2))
+        if not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"adam_beta1 / adam_beta2 must be in [0, 1), got {betas}")
+        kw["betas"] = betas
+    eps = getattr(config, "adam_eps", None)
+    if eps is not None:
+        if not float(eps) > 0.0:
+            raise ValueError(f"adam_eps must be > 0, got {eps}")
+        kw["eps"] = float(eps)
+    wd = getattr(config, "weight_decay", None)
+    if wd is not None:
+        if not float(wd) >= 0.0:
+            raise ValueError(f"weight_decay must be >= 0, got {wd}")
+        kw["weight_decay"] = float(wd)
+    named = [key for key, _, _ in _PRODIGY_KEYS if getattr(config, key, None) is not None]
+    lr = config.learning_rate
+    if kind == "adamw":
+        if named:
+            raise ValueError(f"{', '.join(named)} set without optimizer: prodigy")
+        return OptimizerSpec(kind, lr, kw)
+    train_mode = getattr(config, "train_mode", "full")
+    if train_mode != "lora_audio" or getattr(config, "use_deepspeed", False):
+        raise NotImplementedError(f"optimizer 'prodigy' with train_mode={train_mode!r}, use_deepspeed="
+                                  f"{bool(getattr(config, 'use_deepspeed', False))}: FusedProdigy steps the "
+                                  f"lora_audio trainable set only; the sharded Zero2AdamW path has no Prodigy")
+    for key, arg, cast in _PRODIGY_KEYS:
+        v = getattr(config, key, None)
+        if v is not None:
+            kw[arg] = cast(v)
+    if not (kw.get("d0", 1e-6) > 0.0 and math.isfinite(kw.get("d0", 1e-6))):
+        raise ValueError(f"prodigy_d0 must be a finite value > 0, got {kw['d0']}")
+    if not kw.get("d_coef", 1.0) > 0.0:
+        raise ValueError(f"prodigy_d_coef must be > 0, got {kw['d_coef']}")
+    if not kw.get("growth_rate", 1.0) > 0.0:
+        raise ValueError(f"prodigy_growth_rate must be > 0, got {kw['growth_rate']}")
+    if not 0.0 <= kw.get("beta3", 0.5) < 1.0:
+        raise ValueError(f"prodigy_beta3 must be in [0, 1), got {kw['beta3']}")
+    lr = 1.0 if lr is None else float(lr)
+    if not lr >= 0.0:
+        raise ValueError(f"learning_rate must be >= 0, got {lr}")
+    return OptimizerSpec(kind, lr, kw)
+
+
 class OverlapHooks:
     """Readiness tracking shared by the reducers that overlap their collectives with the last
     micro-step's backward (GradAllReduce here, zero.Zero2AdamW): ``self.buckets`` is a list of
@@ -784,7 +1073,8 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
     (FusedAdamW(max_grad_norm)) adds "train/grad_norm", the pre-clip global norm of the step's
     gradients -- under data parallelism the averaged ones, the same on every rank -- read at the
     same sync point as the loss. An optimizer that averages (FusedAdamW(ema)) adds "train/ema_decay",
-    the decay that step's shadow update used."""
+    the decay that step's shadow update used. FusedProdigy adds "train/prodigy_d", its step-size
+    estimate after the step, read from the device record there too."""
     model.train()
     accum = max(1, int(config.gradient_accumulation_steps))
 
@@ -818,6 +1108,8 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
                            "train/lr": optimizer.param_groups[0]["lr"]}
                 if getattr(optimizer, "grad_norm", None) is not None:
                     payload["train/grad_norm"] = float(optimizer.grad_norm)
+                if isinstance(optimizer, FusedProdigy):
+                    payload["train/prodigy_d"] = float(optimizer.d)  # the device record, at the same sync point
                 if getattr(optimizer, "ema", None) is not None:
                     payload["train/ema_decay"] = optimizer.ema_decay  # a host value: no sync
                 for k, v in (loss_dict or {}).items():
@@ -859,7 +1151,14 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     schedule restores (bitwise the uninterrupted run, shadows included). The merged per-epoch
     checkpoints stay the raw weights'. The shadow update runs after the gradient all-reduce, inside
     step(), and needs no collective: every rank's shadows are identical by construction (run at world
-    size 1 only, like the rest of data parallelism here)."""
+    size 1 only, like the rest of data parallelism here).
+
+    The optimizer itself comes from optimizer_from_config (absent keys = FusedAdamW(lr) with today's
+    defaults, call for call): `optimizer: prodigy` builds FusedProdigy, which estimates its own step
+    size on the device (`learning_rate` 1.0, also when null; the schedule multiplies it as it does
+    AdamW's rate), logs "train/prodigy_d" per optimizer step, and with save_adapters adds s.<name> /
+    p0.<name> to optimizer.safetensors and a "prodigy" block to train_state.json, from which a resumed
+    run continues bitwise. `weight_decay`, `adam_beta1`, `adam_beta2`, `adam_eps` reach either optimizer."""
     import os
 
     from . import io
@@ -875,6 +1174,9 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     # the optional optimizer-step keys, validated before anything is built
     max_grad_norm, lr_schedule = schedule_from_config(config, dataloader)
     ema = ema_from_config(config)
+    spec = optimizer_from_config(config)
+    if spec.kind == "prodigy" and lr_schedule is not None:
+        lr_schedule.base_lr = spec.lr  # learning_rate: null means 1.0 there
     device = device or model.device
     patchifier = model.patchifier or SymmetricPatchifier(1)
     if getattr(config, "gradient_checkpointing", False):
@@ -885,7 +1187,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                 target_shift_terminal=config.rf_target_shift_terminal,
                                 sampler=config.rf_sampler, shift=config.rf_shift)
     params = [p for p in model.parameters() if p.requires_grad]
-    optimizer = FusedAdamW(params, lr=config.learning_rate, max_grad_norm=max_grad_norm, ema=ema)
+    optimizer = spec.build(params, max_grad_norm=max_grad_norm, ema=ema)
     reducer = None
     if dist.is_available() and dist.is_initialized():
         order = model.grad_ready_order() if hasattr(model, "grad_ready_order") else None
