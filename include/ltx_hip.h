@@ -503,12 +503,35 @@ int ltx_ema_load_multi(const int64_t* table, int64_t nchunks, int is_bf16, void*
 /* param[i] = stash[i] over the EMA table's rows: undoes ltx_ema_load_multi. */
 int ltx_ema_restore_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream);
 
+/* ---- stochastically rounded bf16 parameters with f32 moments (csrc/optim.hip, csrc/philox.h) ------ */
+/* The mixed step of a bf16 parameter with a bf16 gradient: P = float(p), G = float(g) (with a coefficient
+ * G = float(bf16(G * *coef))), (P', M', V') exactly ltx_adamw_multi's f32 arithmetic on (P, G, M, V) with
+ * f32 exp_avg / exp_avg_sq, and p' = SR(P', r): for a finite P' the bf16 bits are (bits(P') + r) >> 16,
+ * NaN and +-inf take round-to-nearest. The 16-bit r of element i is lane i & 7 (low half of word
+ * (i & 7) / 2 for an even lane, high half for an odd one) of Philox4x32-10 on the counter
+ * (lo32(i >> 3), hi32(i >> 3), ordinal, step mod 2^32) under the key (seed lo, seed hi); it does not
+ * depend on the chunking or the access width.
+ *
+ * The table: device int64 [nchunks][8] of (param bf16, grad bf16, exp_avg f32, exp_avg_sq f32, first
+ * element, count <= 2048, shadow f32 or 0, ordinal in [0, 2^32)); first element is a multiple of 8. With
+ * ema != 0 the shadow follows the value stored, shadow <- shadow - one_minus_decay * (shadow - float(p')),
+ * as in ltx_adamw_multi_ema. Rows whose tensors are all 16-byte aligned move 16 bytes per lane per access
+ * and make one generator call per 8 elements. */
+int ltx_adamw_multi_sr(const int64_t* table, int64_t nchunks, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int64_t step, const float* coef_or_null, int ema, float one_minus_decay,
+                       uint64_t seed, void* stream);
+
 /* ---- Prodigy, the learning-rate-free optimizer, over the chunk table (csrc/prodigy.hip) ---------- */
 /* The Prodigy table: device int64 [nchunks][10] of (param, grad, exp_avg, exp_avg_sq, first element,
  * count <= 2048, s, p0, shadow, stash). exp_avg, exp_avg_sq, s and p0 have the parameter's dtype; shadow
  * (the f32 EMA of the parameter) and stash are 0 without the EMA, and the Prodigy entry points never read
  * stash. One block per row, 256 threads; rows whose tensors are all 16-byte aligned move 16 bytes per
  * lane per access, the others one element.
+ *
+ * is_bf16 = 2 in ltx_prodigy_moments_multi, and ltx_prodigy_apply_multi_sr, are the mixed step of a bf16
+ * parameter (see ltx_adamw_multi_sr): param, grad and p0 bf16, exp_avg, exp_avg_sq and s f32, the f32
+ * instantiation's arithmetic on float(p), float(g) (with a coefficient, float(bf16(g * *coef))) and
+ * float(p0), and the table's last field the parameter's ordinal in place of the stash.
  *
  * The record: 8 device f64 { d, d_max, d_numerator, d_denom, d_hat, dlr, k, applied }, 8-byte aligned;
  * the caller initialises it to { d0, d0, 0, 0, 0, 0, 0, 0 }. Hyper-parameters arrive as doubles; every
@@ -548,6 +571,12 @@ int ltx_prodigy_d_update(const double* part, int64_t nrows, double* record, doub
  * and with ema != 0, shadow <- shadow - one_minus_decay * (shadow - float(p)) as in ltx_adamw_multi_ema. */
 int ltx_prodigy_apply_multi(const int64_t* table, int64_t nchunks, int is_bf16, const double* record, double eps,
                             double decoupled_weight_decay, int ema, float one_minus_decay, void* stream);
+/* Pass 2 of the mixed step: ltx_prodigy_apply_multi's f32 arithmetic on float(p) and the f32 moments, the
+ * result stored as SR(p', r) with r from (seed, the row's ordinal, step, element) as in ltx_adamw_multi_sr;
+ * the shadow follows the value stored. `step` is the parameters' step count after its increment. */
+int ltx_prodigy_apply_multi_sr(const int64_t* table, int64_t nchunks, const double* record, double eps,
+                               double decoupled_weight_decay, int ema, float one_minus_decay, uint64_t seed,
+                               int64_t step, void* stream);
 
 /* ---- train_mode='full' parameter gradients (csrc/paramgrad.hip) --------- */
 /* Weight gradient of the q/k RMSNorm weights: partials[(which * splits + s) * D + d] (f32) =

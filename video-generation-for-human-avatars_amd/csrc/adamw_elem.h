@@ -14,6 +14,28 @@ __device__ __forceinline__ float torch_lerp(float self, float end, float w) {
   return fabsf(w) < 0.5f ? fmaf(w, d, self) : fmaf(-d, 1.0f - w, end);
 }
 
+// The arithmetic described below on register values: p, m, v in and out, g the gradient as loaded. R rounds
+// to bf16 for BF16 and is the identity for f32.
+template <bool BF16, bool CLIP>
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float decay, float w1, float b2,
+                                             float w2, float step_size, float bc2_sqrt, float eps, float coef) {
+  auto R = [](float x) { return BF16 ? rbf(x) : x; };
+  if (CLIP) g = R(g * coef);
+  p = R(p * decay);
+  m = R(torch_lerp(m, g, w1));
+  v = R(v * b2);
+  v = R(v + w2 * g * g);
+  float den = R(sqrtf(v));
+  den = R(den / bc2_sqrt);
+  den = R(den + eps);
+  p = R(p + step_size * (m / den));
+}
+
+// the shadow's step: s - omd (s - p') as three separately rounded f32 operations
+__device__ __forceinline__ float ema_update(float s, float p, float omd) {
+  return __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p)));
+}
+
 // torch.optim.AdamW, foreach implementation order (weight decay, lerp m, v*b2 + (1-b2) g g,
 // sqrt, / sqrt(bc2), + eps, p += step_size * m / den), rounding every op for bf16 tensors.
 // CLIP: the gradient is first scaled by `coef` and rounded to its dtype, which is what an in-place
@@ -35,20 +57,8 @@ __device__ __forceinline__ void adamw_elem(void* __restrict__ param, const void*
   } else {
     p = ((float*)param)[i]; g = ((const float*)grad)[i]; m = ((float*)m_)[i]; v = ((float*)v_)[i];
   }
-  auto R = [](float x) { return BF16 ? rbf(x) : x; };
-  if (CLIP) g = R(g * coef);
-  p = R(p * decay);
-  m = R(torch_lerp(m, g, w1));
-  v = R(v * b2);
-  v = R(v + w2 * g * g);
-  float den = R(sqrtf(v));
-  den = R(den / bc2_sqrt);
-  den = R(den + eps);
-  p = R(p + step_size * (m / den));
-  if (EMA) {
-    const float s = shadow[i];
-    shadow[i] = __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p)));
-  }
+  adamw_update<BF16, CLIP>(p, g, m, v, decay, w1, b2, w2, step_size, bc2_sqrt, eps, coef);
+  if (EMA) shadow[i] = ema_update(shadow[i], p, omd);
   if (BF16) {
     ((bf16_t*)param)[i] = f2bf(p); ((bf16_t*)m_)[i] = f2bf(m); ((bf16_t*)v_)[i] = f2bf(v);
   } else {

@@ -8,39 +8,9 @@
 //                            term that cannot ride the dgrad GEMM's K extension under a mask
 #include "common.h"
 #include "ltx_hip.h"
+#include "philox.h"
 
 namespace ltx {
-
-struct Philox4 {
-  uint32_t v[4];
-};
-
-__host__ __device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) {
-  return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32);
-}
-
-// Philox4x32-10 (Salmon et al., Random123): ten rounds, the key bumped between rounds
-__host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                                          uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint32_t hi0 = mulhi32(M0, c0), lo0 = M0 * c0;
-    const uint32_t hi1 = mulhi32(M1, c2), lo1 = M1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += W0;
-    k1 += W1;
-  }
-  return Philox4{{c0, c1, c2, c3}};
-}
-
-// the 16-bit lane of column k % 8 = j: low half of o[j / 2] for even j, high half for odd j
-__host__ __device__ __forceinline__ uint32_t mask_lane(const Philox4& o, int j) {
-  return (o.v[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-}
 
 // one 16-B vector (8 columns) per thread and step, grid-stride over the M * K / 8 vectors
 __global__ __launch_bounds__(256) void lora_dropout_apply_kernel(const bf16_t* __restrict__ x, int64_t ldx,

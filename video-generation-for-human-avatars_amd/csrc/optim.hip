@@ -12,9 +12,12 @@
 // Below them, the exponential moving average of the trainable weights (FusedAdamW with ema): the AdamW
 // launch with the f32 shadow update fused in (ltx_adamw_multi_ema), and the two swap kernels that install
 // the averaged weights for an evaluation or an export and put the live ones back.
+// Last, the mixed step of a bf16 parameter with f32 moments and a stochastically rounded store
+// (FusedAdamW(bf16_update="stochastic"), ltx_adamw_multi_sr).
 #include <cmath>
 
 #include "adamw_elem.h"
+#include "chunk_io.h"
 #include "common.h"
 #include "ltx_hip.h"
 
@@ -165,6 +168,64 @@ __global__ __launch_bounds__(256) void ema_swap_multi_kernel(const int64_t* __re
   }
 }
 
+// ---- bf16 parameters with f32 moments and a stochastically rounded store ----------------------------
+// Rows of 8 int64: (param bf16, grad bf16, exp_avg f32, exp_avg_sq f32, first element, count, shadow f32
+// or 0, the parameter's ordinal). Per element 2 + 2 + 4 + 4 bytes in and 2 + 4 + 4 out (8 more with the
+// shadow), so a row whose tensors are 16-byte aligned is walked 8 elements per lane: one 16-byte load each
+// of p and g, two each of m and v, one Philox call for the 8 stores (st_sr). A row's last count % 8
+// elements, and rows over a tensor that is not aligned, go one element per lane with that element's lane
+// of the same call.
+constexpr int SR_ROW = 8;
+
+struct AdamWSr {
+  float decay, w1, b2, w2, step_size, bc2_sqrt, eps, coef, omd;
+  uint32_t k0, k1, step;
+};
+
+template <bool CLIP, bool EMA, int N>
+__device__ __forceinline__ void adamw_sr_at(const int64_t* __restrict__ e, int64_t i, const AdamWSr& c) {
+  float p[N], g[N], m[N], v[N], sh[N];
+  ld<true, N>((const void*)e[0], i, p);
+  ld<true, N>((const void*)e[1], i, g);
+  ld<false, N>((const void*)e[2], i, m);
+  ld<false, N>((const void*)e[3], i, v);
+  if (EMA) ld<false, N>((const void*)e[6], i, sh);
+  const Philox4 o = sr_philox(i, (uint32_t)e[7], c.step, c.k0, c.k1);  // under the loads
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    // the clipped gradient is what grad.mul_(coef) would leave in the bf16 tensor
+    const float gj = CLIP ? rbf(g[j] * c.coef) : g[j];
+    adamw_update<false, false>(p[j], gj, m[j], v[j], c.decay, c.w1, c.b2, c.w2, c.step_size, c.bc2_sqrt, c.eps,
+                               1.0f);
+  }
+  st_sr<N>((void*)e[0], i, p, o);  // p becomes the value stored
+  st<false, N>((void*)e[2], i, m);
+  st<false, N>((void*)e[3], i, v);
+  if (EMA) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) sh[j] = ema_update(sh[j], p[j], c.omd);
+    st<false, N>((void*)e[6], i, sh);
+  }
+}
+
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_multi_sr_kernel(const int64_t* __restrict__ table, AdamWSr c,
+                                                             const float* __restrict__ coef) {
+  const int64_t* e = table + (int64_t)blockIdx.x * SR_ROW;
+  const int64_t start = e[4], count = e[5];
+  if (CLIP) c.coef = *coef;
+  uint64_t bits = (uint64_t)e[0] | (uint64_t)e[1] | (uint64_t)e[2] | (uint64_t)e[3];
+  if (EMA) bits |= (uint64_t)e[6];
+  if ((bits & 15) == 0 && (start & 7) == 0) {
+    const int64_t nvec = count / 8;
+    for (int64_t q = threadIdx.x; q < nvec; q += 256) adamw_sr_at<CLIP, EMA, 8>(e, start + q * 8, c);
+    const int64_t i = start + nvec * 8 + threadIdx.x;
+    if (i < start + count) adamw_sr_at<CLIP, EMA, 1>(e, i, c);
+  } else {
+    for (int64_t i = start + threadIdx.x; i < start + count; i += 256) adamw_sr_at<CLIP, EMA, 1>(e, i, c);
+  }
+}
+
 }  // namespace ltx
 
 using namespace ltx;
@@ -249,6 +310,31 @@ int ltx_ema_restore_multi(const int64_t* table, int64_t nchunks, int is_bf16, vo
   else
     hipLaunchKernelGGL((ema_swap_multi_kernel<false, false>), dim3((unsigned)nchunks), dim3(256), 0,
                        (hipStream_t)stream, table);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_adamw_multi_sr(const int64_t* table, int64_t nchunks, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int64_t step, const float* coef_or_null, int ema, float one_minus_decay,
+                       uint64_t seed, void* stream) {
+  LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_sr: bad args");
+  LTX_CHECK_ARG(!ema || (one_minus_decay >= 0.f && one_minus_decay <= 1.f),
+                "adamw_multi_sr: one_minus_decay outside [0, 1]");
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
+  const AdamWSr c = {a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, 1.0f, ema ? one_minus_decay : 0.f,
+                     (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)((uint64_t)step & 0xffffffffu)};
+  const dim3 grid((unsigned)nchunks), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define LTX_SR_LAUNCH(CL, EM) \
+  hipLaunchKernelGGL((adamw_multi_sr_kernel<CL, EM>), grid, block, 0, st, table, c, coef_or_null)
+  if (coef_or_null) {
+    if (ema) LTX_SR_LAUNCH(true, true);
+    else LTX_SR_LAUNCH(true, false);
+  } else {
+    if (ema) LTX_SR_LAUNCH(false, true);
+    else LTX_SR_LAUNCH(false, false);
+  }
+#undef LTX_SR_LAUNCH
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

@@ -17,8 +17,13 @@
 // walked with 16-byte accesses (4 f32 or 8 bf16 per lane, the row's last count % 4 or 8 elements one per
 // lane); rows over a tensor that is not (a gradient that is a view into a reducer's bucket) take one
 // element per lane throughout. The arithmetic per element is the same (prodigy_elem.h).
+//
+// The mixed step of a bf16 parameter (FusedProdigy(bf16_update="stochastic")): param, grad and p0 bf16,
+// exp_avg, exp_avg_sq and s f32, the f32 arithmetic on the widened values, and pass 2 stores the
+// parameter stochastically rounded (chunk_io.h st_sr); the row's last field is the parameter's ordinal.
 #include <cmath>
 
+#include "chunk_io.h"
 #include "common.h"
 #include "ltx_hip.h"
 #include "prodigy_elem.h"
@@ -26,52 +31,6 @@
 namespace ltx {
 
 constexpr int PRODIGY_ROW = 10;
-
-// N consecutive elements starting at element i, as f32 (N = 1, or 4 f32 / 8 bf16 as one 16-byte access;
-// an f32 column of a bf16 row, the shadow, as two)
-template <bool BF16, int N>
-__device__ __forceinline__ void ld(const void* base, int64_t i, float (&x)[N]) {
-  if constexpr (N == 1) {
-    x[0] = BF16 ? bf2f(((const bf16_t*)base)[i]) : ((const float*)base)[i];
-  } else if constexpr (BF16) {
-    static_assert(N == 8, "bf16 vector width");
-    const u32x4 w = *(const u32x4*)((const bf16_t*)base + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = __uint_as_float(w[j] << 16);
-      x[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-      const f32x4 w = *(const f32x4*)((const float*)base + i + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[4 * q + j] = w[j];
-    }
-  }
-}
-
-// the values are already rounded to the tensor's dtype, so the bf16 conversion is exact
-template <bool BF16, int N>
-__device__ __forceinline__ void st(void* base, int64_t i, const float (&x)[N]) {
-  if constexpr (N == 1) {
-    if (BF16) ((bf16_t*)base)[i] = f2bf(x[0]);
-    else ((float*)base)[i] = x[0];
-  } else if constexpr (BF16) {
-    u32x4 w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = pack2(x[2 * j], x[2 * j + 1]);
-    *(u32x4*)((bf16_t*)base + i) = w;
-  } else {
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-      f32x4 w;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w[j] = x[4 * q + j];
-      *(f32x4*)((float*)base + i + 4 * q) = w;
-    }
-  }
-}
 
 struct ProdigyRow {
   void* param;
@@ -140,12 +99,38 @@ __device__ __forceinline__ void moments_at(const ProdigyRow& r, int64_t i, const
   st<BF16, N>(r.s, i, s);
 }
 
-template <bool BF16, bool CLIP, bool COUPLED>
+// pass 1 of the mixed step: the f32 instantiation on (float(p), float(g), float(p0)) and the f32 state;
+// with a coefficient the gradient is first what grad.mul_(coef) would leave in the bf16 tensor
+template <bool CLIP, bool COUPLED, int N>
+__device__ __forceinline__ void moments_mixed_at(const ProdigyRow& r, int64_t i, const ProdigyMoments& c,
+                                                 double& num, double& den) {
+  float p[N], g[N], p0[N], m[N], v[N], s[N];
+  ld<true, N>(r.param, i, p);
+  ld<true, N>(r.grad, i, g);
+  ld<true, N>(r.p0, i, p0);
+  ld<false, N>(r.m, i, m);
+  ld<false, N>(r.v, i, v);
+  ld<false, N>(r.s, i, s);
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    float tn, td;
+    const float gj = CLIP ? rbf(g[j] * c.coef) : g[j];
+    prodigy_moments_elem<false, false, COUPLED>(p[j], gj, p0[j], m[j], v[j], s[j], c, tn, td);
+    num += (double)tn;
+    den += (double)td;
+  }
+  st<false, N>(r.m, i, m);
+  st<false, N>(r.v, i, v);
+  st<false, N>(r.s, i, s);
+}
+
+// MIXED: bf16 param / grad / p0 with f32 state (BF16 is then ignored)
+template <bool BF16, bool CLIP, bool COUPLED, bool MIXED = false>
 __global__ __launch_bounds__(256) void prodigy_moments_multi_kernel(const int64_t* __restrict__ table,
                                                                     const ProdigyRecord* __restrict__ rec,
                                                                     ProdigyHyper h, const float* __restrict__ coef,
                                                                     double* __restrict__ part) {
-  constexpr int VEC = BF16 ? 8 : 4;
+  constexpr int VEC = (BF16 || MIXED) ? 8 : 4;
   const ProdigyRow r = prodigy_row(table, true, false);
   const double d = rec->d;
   const double dlr = prodigy_dlr(d, rec->k, h.lr, h.beta1, h.beta2, h.use_bias_correction);
@@ -159,7 +144,18 @@ __global__ __launch_bounds__(256) void prodigy_moments_multi_kernel(const int64_
   c.wd = (float)h.weight_decay;
   c.coef = CLIP ? *coef : 1.0f;
   double num = 0.0, den = 0.0;
-  if (r.aligned) {
+  if constexpr (MIXED) {
+    if (r.aligned) {
+      const int64_t nvec = r.count / VEC;
+      for (int64_t q = threadIdx.x; q < nvec; q += 256)
+        moments_mixed_at<CLIP, COUPLED, VEC>(r, r.start + q * VEC, c, num, den);
+      const int64_t i = r.start + nvec * VEC + threadIdx.x;
+      if (i < r.start + r.count) moments_mixed_at<CLIP, COUPLED, 1>(r, i, c, num, den);
+    } else {
+      for (int64_t i = r.start + threadIdx.x; i < r.start + r.count; i += 256)
+        moments_mixed_at<CLIP, COUPLED, 1>(r, i, c, num, den);
+    }
+  } else if (r.aligned) {
     const int64_t nvec = r.count / VEC;
     for (int64_t q = threadIdx.x; q < nvec; q += 256)
       moments_at<BF16, CLIP, COUPLED, VEC>(r, r.start + q * VEC, c, num, den);
@@ -269,6 +265,53 @@ __global__ __launch_bounds__(256) void prodigy_apply_multi_kernel(const int64_t*
   }
 }
 
+// pass 2 of the mixed step: the f32 instantiation on float(p) and the f32 moments, the stochastically
+// rounded store, and the shadow following the value stored
+template <bool DECAY, bool EMA, int N>
+__device__ __forceinline__ void apply_sr_at(const ProdigyRow& r, int64_t i, const ProdigyApply& c, uint32_t ordinal,
+                                            uint32_t step, uint32_t k0, uint32_t k1) {
+  float p[N], m[N], v[N], sh[N], unused = 0.f;
+  ld<true, N>(r.param, i, p);
+  ld<false, N>(r.m, i, m);
+  ld<false, N>(r.v, i, v);
+  if (EMA) ld<false, N>(r.shadow, i, sh);
+  const Philox4 o = sr_philox(i, ordinal, step, k0, k1);  // under the loads
+#pragma unroll
+  for (int j = 0; j < N; ++j) p[j] = prodigy_apply_elem<false, DECAY, false>(p[j], m[j], v[j], c, unused);
+  st_sr<N>(r.param, i, p, o);  // p becomes the value stored
+  if (EMA) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) sh[j] = __fsub_rn(sh[j], __fmul_rn(c.omd, __fsub_rn(sh[j], p[j])));
+    st<false, N>(r.shadow, i, sh);
+  }
+}
+
+template <bool DECAY, bool EMA>
+__global__ __launch_bounds__(256) void prodigy_apply_multi_sr_kernel(const int64_t* __restrict__ table,
+                                                                     const ProdigyRecord* __restrict__ rec,
+                                                                     double eps, double weight_decay, float omd,
+                                                                     uint32_t k0, uint32_t k1, uint32_t step) {
+  if (rec->applied == 0.0) return;
+  const ProdigyRow r = prodigy_row(table, false, EMA);
+  const uint32_t ordinal = (uint32_t)table[(int64_t)blockIdx.x * PRODIGY_ROW + 9];
+  const double dlr = rec->dlr;
+  ProdigyApply c;
+  c.deps = (float)(rec->d * eps);
+  c.decay = (float)(-weight_decay * dlr);
+  c.step = (float)(-dlr);
+  c.omd = omd;
+  if (r.aligned && (r.start & 7) == 0) {
+    const int64_t nvec = r.count / 8;
+    for (int64_t q = threadIdx.x; q < nvec; q += 256)
+      apply_sr_at<DECAY, EMA, 8>(r, r.start + q * 8, c, ordinal, step, k0, k1);
+    const int64_t i = r.start + nvec * 8 + threadIdx.x;
+    if (i < r.start + r.count) apply_sr_at<DECAY, EMA, 1>(r, i, c, ordinal, step, k0, k1);
+  } else {
+    for (int64_t i = r.start + threadIdx.x; i < r.start + r.count; i += 256)
+      apply_sr_at<DECAY, EMA, 1>(r, i, c, ordinal, step, k0, k1);
+  }
+}
+
 }  // namespace ltx
 
 using namespace ltx;
@@ -286,7 +329,8 @@ int ltx_prodigy_moments_multi(const int64_t* table, int64_t nchunks, int is_bf16
   const dim3 grid((unsigned)nchunks), block(256);
   hipStream_t st = (hipStream_t)stream;
   const ProdigyRecord* rec = (const ProdigyRecord*)record;
-  const int sel = (is_bf16 ? 4 : 0) | (coef_or_null ? 2 : 0) | (coupled_weight_decay != 0.0 ? 1 : 0);
+  LTX_CHECK_ARG(is_bf16 >= 0 && is_bf16 <= 2, "prodigy_moments_multi: is_bf16 is 0 (f32), 1 (bf16) or 2 (mixed)");
+  const int sel = (is_bf16 == 2 ? 8 : is_bf16 ? 4 : 0) | (coef_or_null ? 2 : 0) | (coupled_weight_decay != 0.0 ? 1 : 0);
 #define LTX_PRODIGY_P1(BF, CL, CO)                                                                          \
   hipLaunchKernelGGL((prodigy_moments_multi_kernel<BF, CL, CO>), grid, block, 0, st, table, rec, h, coef_or_null, \
                      part)
@@ -298,7 +342,15 @@ int ltx_prodigy_moments_multi(const int64_t* table, int64_t nchunks, int is_bf16
     case 4: LTX_PRODIGY_P1(true, false, false); break;
     case 5: LTX_PRODIGY_P1(true, false, true); break;
     case 6: LTX_PRODIGY_P1(true, true, false); break;
-    default: LTX_PRODIGY_P1(true, true, true); break;
+    case 7: LTX_PRODIGY_P1(true, true, true); break;
+#define LTX_PRODIGY_P1M(CL, CO)                                                                                  \
+  hipLaunchKernelGGL((prodigy_moments_multi_kernel<true, CL, CO, true>), grid, block, 0, st, table, rec, h,     \
+                     coef_or_null, part)
+    case 8: LTX_PRODIGY_P1M(false, false); break;
+    case 9: LTX_PRODIGY_P1M(false, true); break;
+    case 10: LTX_PRODIGY_P1M(true, false); break;
+    default: LTX_PRODIGY_P1M(true, true); break;
+#undef LTX_PRODIGY_P1M
   }
 #undef LTX_PRODIGY_P1
   LTX_LAUNCH_CHECK();
@@ -342,6 +394,33 @@ int ltx_prodigy_apply_multi(const int64_t* table, int64_t nchunks, int is_bf16, 
     default: LTX_PRODIGY_P2(true, true, true); break;
   }
 #undef LTX_PRODIGY_P2
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_prodigy_apply_multi_sr(const int64_t* table, int64_t nchunks, const double* record, double eps,
+                               double decoupled_weight_decay, int ema, float one_minus_decay, uint64_t seed,
+                               int64_t step, void* stream) {
+  LTX_CHECK_ARG(table && record && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "prodigy_apply_multi_sr: bad args");
+  LTX_CHECK_ARG(((uintptr_t)record & 7) == 0, "prodigy_apply_multi_sr: record must be 8-byte aligned");
+  LTX_CHECK_ARG(!ema || (one_minus_decay >= 0.f && one_minus_decay <= 1.f),
+                "prodigy_apply_multi_sr: one_minus_decay outside [0, 1]");
+  const dim3 grid((unsigned)nchunks), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const ProdigyRecord* rec = (const ProdigyRecord*)record;
+  const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+  const uint32_t step32 = (uint32_t)((uint64_t)step & 0xffffffffu);
+#define LTX_PRODIGY_P2S(DE, EM)                                                                            \
+  hipLaunchKernelGGL((prodigy_apply_multi_sr_kernel<DE, EM>), grid, block, 0, st, table, rec, eps,         \
+                     decoupled_weight_decay, one_minus_decay, k0, k1, step32)
+  if (decoupled_weight_decay != 0.0) {
+    if (ema) LTX_PRODIGY_P2S(true, true);
+    else LTX_PRODIGY_P2S(true, false);
+  } else {
+    if (ema) LTX_PRODIGY_P2S(false, true);
+    else LTX_PRODIGY_P2S(false, false);
+  }
+#undef LTX_PRODIGY_P2S
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

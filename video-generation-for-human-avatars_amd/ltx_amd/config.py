@@ -178,4 +178,12 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     for key in ("prodigy_use_bias_correction", "prodigy_safeguard_warmup", "prodigy_decouple"):
         if key in t:
             setattr(config, key, bool(t[key]))
+    # and the two keys of the stochastically rounded bf16 step, read (and validated) there too:
+    # `train.bf16_update` ("nearest", the same as absent, or "stochastic": f32 moments and a stochastically
+    # rounded store for the bf16 caption projection) and `train.bf16_sr_seed` (an integer in [0, 2^64),
+    # absent = 0; the value is passed on as written, so a fraction is refused, not truncated)
+    if "bf16_update" in t:
+        setattr(config, "bf16_update", str(t["bf16_update"]))
+    if "bf16_sr_seed" in t:
+        setattr(config, "bf16_sr_seed", t["bf16_sr_seed"])
     return config

@@ -378,7 +378,9 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
       metadata['base_model_name_or_path'] when given) and an 'ltx_amd' block with the format version
       and each group's own rank, alpha, scaling, dropout and DoRA flag;
     * optimizer.safetensors (with `optimizer`): exp_avg.<parameter name> / exp_avg_sq.<parameter name>
-      in their stored dtype and every rank's RNG states (_gathered_rng_states);
+      in their stored dtype (f32 for a bf16 parameter under bf16_update="stochastic", whose mode and
+      seed train_state.json holds among the hyper-parameters) and every rank's RNG states
+      (_gathered_rng_states);
     * ema_model.safetensors (with an `optimizer` that keeps an EMA, FusedAdamW(ema)): the f32 shadow
       of every parameter the optimizer holds under adapter_key's names (the parameter's own value in
       f32 where it has not stepped yet, which is what its shadow starts from); every rank's shadows
@@ -549,7 +551,11 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
 
     A training.FusedProdigy gets s, p0 and its record back in place from the "prodigy" block; ValueError,
     before anything is written, when the directory was written by the other kind of optimizer (a Prodigy
-    checkpoint into FusedAdamW or the reverse) or with other Prodigy hyper-parameters."""
+    checkpoint into FusedAdamW or the reverse) or with other Prodigy hyper-parameters.
+
+    The moments come back in their stored dtype -- f32 for a bf16 parameter of an optimizer with
+    bf16_update="stochastic". ValueError, before anything is written, when the directory was written in the
+    other bf16_update mode or with another sr_seed than the live optimizer's."""
     from safetensors.torch import load_file
 
     from . import ops
@@ -599,6 +605,7 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
         if "optimizer" not in state or not os.path.isfile(os.path.join(path, ADAPTER_OPTIMIZER)):
             raise ValueError(f"{path}: holds no optimizer state")
         _check_prodigy(path, optimizer, state)
+        _check_bf16_update(path, optimizer, state)
         opt_tensors = load_file(os.path.join(path, ADAPTER_OPTIMIZER))
     want = (list(config["target_modules"]), block["groups"])
     have = _adapter_layout(model)
@@ -672,6 +679,22 @@ def _check_prodigy(path, optimizer, state):
     missing = [k for k in optimizer.RECORD if k not in (saved.get("record") or {})]
     if missing:
         raise ValueError(f"{path}: the prodigy record lacks {', '.join(missing)}")
+
+
+def _check_bf16_update(path, optimizer, state):
+    """ValueError when the checkpoint was written in the other bf16_update mode of the optimizer
+    (training.FusedAdamW(bf16_update)) or with another sr_seed: the moments' dtype and the rounding's
+    stream would not continue the run that wrote them. A directory without the keys is nearest mode's."""
+    saved = state["optimizer"].get("param_groups") or []
+    for i, (group, hyper) in enumerate(zip(optimizer.param_groups, saved)):
+        have = (group.get("bf16_update", "nearest"), group.get("sr_seed"))
+        want = (hyper.get("bf16_update", "nearest"), hyper.get("sr_seed"))
+        if have[0] != want[0]:
+            raise ValueError(f"{path}: parameter group {i} was saved with bf16_update {want[0]!r}, the live "
+                             f"optimizer's is {have[0]!r}")
+        if have[1] != want[1]:
+            raise ValueError(f"{path}: parameter group {i} was saved with sr_seed {want[1]}, the live "
+                             f"optimizer's is {have[1]}")
 
 
 def _optimizer_plan(path, optimizer, named, saved, opt_tensors, rank, strict):

@@ -246,6 +246,72 @@ def ema_from_config(config):
     return EMASchedule(decay, **kw)
 
 
+BF16_UPDATES = ("nearest", "stochastic")
+
+
+def _check_bf16_update(bf16_update, sr_seed):
+    """(mode, seed) validated: ValueError for a mode outside BF16_UPDATES or a seed outside [0, 2^64)."""
+    if bf16_update not in BF16_UPDATES:
+        raise ValueError(f"bf16_update {bf16_update!r} is not one of {', '.join(BF16_UPDATES)}")
+    if isinstance(sr_seed, bool) or not isinstance(sr_seed, int) or not 0 <= sr_seed < 2 ** 64:
+        raise ValueError(f"sr_seed must be an integer in [0, 2^64), got {sr_seed!r}")
+    return bf16_update, int(sr_seed)
+
+
+def stochastic_round_bits(seed, ordinal, step, index):
+    """The 16-bit random numbers (numpy uint32, the shape of `index`) that round elements `index` of
+    parameter `ordinal` at its step `step` under `seed`: Philox4x32-10 (lora.philox4x32_10) on the counter
+    (lo32(i >> 3), hi32(i >> 3), ordinal, step mod 2^32) with the key (seed lo, seed hi); element i takes
+    the 16-bit lane i & 7 of the four output words, low half of word (i & 7) // 2 for an even lane, high
+    half for an odd one (the rule of the LoRA dropout mask). CPU only."""
+    import numpy as np
+
+    from .lora import philox4x32_10
+    _, seed = _check_bf16_update("stochastic", seed)
+    i = np.asarray(index, dtype=np.uint64)
+    q = i >> np.uint64(3)
+    words = philox4x32_10((q & np.uint64(0xFFFFFFFF), q >> np.uint64(32), int(ordinal) & 0xFFFFFFFF,
+                           int(step) & 0xFFFFFFFF), (seed & 0xFFFFFFFF, seed >> 32))
+    lane = (i & np.uint64(7)).astype(np.int64)
+    word = np.choose(lane >> 1, [np.broadcast_to(w, i.shape) for w in words])
+    return (word >> (np.uint32(16) * (lane & 1).astype(np.uint32))) & np.uint32(0xFFFF)
+
+
+def stochastic_round_bf16(x_f32, seed, ordinal, step, r=None):
+    """The statement, on the CPU, of the stochastically rounded bf16 store of
+    FusedAdamW / FusedProdigy(bf16_update="stochastic"): `x_f32` (a float32 torch tensor or numpy array,
+    the f32 result of parameter `ordinal`'s step number `step`, elements in the tensor's contiguous order)
+    rounded to bf16 with the 16-bit random numbers of stochastic_round_bits(seed, ordinal, step, i) -- or
+    with `r` (an int or an array of x's shape) in their place. For a finite x the bf16 bits are
+    (bits(x) + r) >> 16: the magnitude rounds up with probability (discarded 16 bits) / 2^16, so the
+    expected value is x, a representable x stays for every r, and SR(-x) = -SR(x). NaN and +-inf take the
+    round-to-nearest conversion. Returns a torch.bfloat16 CPU tensor of x's shape for a tensor, the uint16
+    bit patterns for an array."""
+    import numpy as np
+    is_tensor = torch.is_tensor(x_f32)
+    if is_tensor:
+        if x_f32.dtype != torch.float32:
+            raise TypeError(f"stochastic_round_bf16: expected float32, got {x_f32.dtype}")
+        x = x_f32.detach().cpu().contiguous().numpy()
+    else:
+        x = np.ascontiguousarray(x_f32)
+        if x.dtype != np.float32:
+            raise TypeError(f"stochastic_round_bf16: expected float32, got {x.dtype}")
+    u = x.view(np.uint32).reshape(-1).astype(np.uint64)
+    if r is None:
+        r = stochastic_round_bits(seed, ordinal, step, np.arange(u.size, dtype=np.uint64))
+    r = np.broadcast_to(np.asarray(r, dtype=np.uint64).reshape(-1) & np.uint64(0xFFFF), u.shape)
+    bits = ((u + r) >> np.uint64(16)).astype(np.uint16)
+    special = (u & np.uint64(0x7F800000)) == np.uint64(0x7F800000)
+    if special.any():
+        nearest = torch.from_numpy(x.reshape(-1)[special].copy()).to(torch.bfloat16).view(torch.int16).numpy()
+        bits[special] = nearest.view(np.uint16)
+    bits = bits.reshape(x.shape)
+    if is_tensor:
+        return torch.from_numpy(bits.view(np.int16).copy()).view(torch.bfloat16)
+    return bits
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW (defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2; the
     reference constructs AdamW(trainable, lr) at training.py:270-271) with one ltx_adamw_step
@@ -272,18 +338,31 @@ class FusedAdamW(torch.optim.Optimizer):
     model is ever without one). Parameters, moments and steps are bitwise those of ema=None.
     ema_swap_in() / ema_swap_out() / the context manager ema_weights() install the shadows as the
     weights (rounded to the parameter's dtype) for an evaluation or an export and put the live values
-    back; step() refuses to run in between."""
+    back; step() refuses to run in between.
+
+    `bf16_update` ("nearest": today's step, call for call, bf16 moments and every op rounded to bf16 as
+    torch steps a bf16 tensor; "stochastic", with `sr_seed` in [0, 2^64)): a bf16 parameter (its gradient
+    must be bf16 too) keeps f32 exp_avg / exp_avg_sq, its step is the f32 arithmetic on float(p), float(g)
+    (with the clip, float(bf16(g * coef))), and the result is stored stochastically rounded --
+    stochastic_round_bf16, a pure function of (sr_seed, the parameter's index in the concatenation of
+    param_groups[*]["params"], its state["step"], the element) -- through ltx_adamw_multi_sr, always the
+    table kernels; the bf16 tensor stays the only copy of the weight, and the EMA shadow follows the value
+    stored. f32 parameters are stepped bitwise as without the mode. The two values enter param_groups (and
+    with them a checkpoint's train_state.json) in stochastic mode only."""
 
     CHUNK = 2048  # elements per block of the multi-tensor kernel
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 multi_tensor=True, max_grad_norm=None, ema=None):
+                 multi_tensor=True, max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0):
         if max_grad_norm is not None and not float(max_grad_norm) >= 0:
             raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
         if ema is not None and not isinstance(ema, EMASchedule):
             raise TypeError(f"ema must be an EMASchedule or None, got {type(ema).__name__}")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      max_grad_norm=max_grad_norm))
+        self.bf16_update, self.sr_seed = _check_bf16_update(bf16_update, sr_seed)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        if self.bf16_update == "stochastic":
+            defaults.update(bf16_update=self.bf16_update, sr_seed=self.sr_seed)
+        super().__init__(params, defaults)
         self.multi_tensor = multi_tensor
         self._tables = []  # pinned host tables of the last builds (alive until their H2D lands)
         self._table_cache = {}  # dtype -> (buffer pointers, device table, rows)
@@ -311,7 +390,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._ema_swapped is not None:
             raise RuntimeError("FusedAdamW.step() while the EMA weights are swapped in: call ema_swap_out() first")
         max_norm = self._max_grad_norm()
-        if max_norm > 0 or self.ema is not None:
+        if max_norm > 0 or self.ema is not None or self.bf16_update == "stochastic":
             return self._step_tables(max_norm)
         for group in self.param_groups:
             b1, b2 = group["betas"]
@@ -371,6 +450,39 @@ class FusedAdamW(torch.optim.Optimizer):
         self._table_cache[slot] = (key, dev, nrows, host)
         return dev, nrows
 
+    def _ordinals(self):
+        """parameter -> its index in the concatenation of param_groups[*]["params"] (torch's state_dict
+        index), the stream of its stochastic rounding"""
+        out = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                out[p] = len(out)
+        return out
+
+    def _mixed_state(self, p, st):
+        """The checks of a bf16 parameter's stochastic step: a bf16 gradient, f32 moments."""
+        if p.grad.dtype != torch.bfloat16:
+            raise TypeError(f"{type(self).__name__}(bf16_update='stochastic'): a bf16 parameter's gradient must "
+                            f"be bf16, got {p.grad.dtype}")
+        if st and st["exp_avg"].dtype != torch.float32:
+            raise ValueError(f"{type(self).__name__}(bf16_update='stochastic'): a bf16 parameter's moments are "
+                             f"{st['exp_avg'].dtype}, from a run in nearest mode; they are not converted")
+
+    def _sr_table(self, items, slot, ordinals, ema):
+        """(device table, rows) of the stochastic step's 8-field rows (param, grad, exp_avg, exp_avg_sq,
+        first element, count <= CHUNK, shadow or 0, ordinal), cached like _table's."""
+        ptrs = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
+                      st["ema"].data_ptr() if ema else 0, ordinals[p]) for p, g, st in items)
+        hit = self._table_cache.get(slot)
+        if hit is not None and hit[0] == ptrs:
+            return hit[1], hit[2]
+        rows = [(pp, gp, ap, sp, start, min(self.CHUNK, n - start), ep, o)
+                for pp, gp, ap, sp, n, ep, o in ptrs for start in range(0, n, self.CHUNK)]
+        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+        dev = host.to(items[0][0].device, non_blocking=True)
+        self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
+        return dev, len(rows)
+
     def _multi(self, items, dtype, group, b1, b2, step):
         """One ltx_adamw_multi launch for all tensors of a dtype (bitwise the per-tensor math)."""
         dev, nrows = self._table(items, dtype)
@@ -383,11 +495,17 @@ class FusedAdamW(torch.optim.Optimizer):
         with a gradient goes through the table kernels, grouped by (param group, dtype, step). Launch
         order: when clipping, the norm launches of all groups (each writes its per-row partials behind
         the previous group's) and the coefficient launch; then one AdamW launch per group --
-        ltx_adamw_multi_clip, or with the EMA ltx_adamw_multi_ema (given the coefficient when clipping)."""
+        ltx_adamw_multi_clip, or with the EMA ltx_adamw_multi_ema (given the coefficient when clipping).
+        With bf16_update="stochastic" every step comes here: a group's bf16 parameters form buckets of
+        their own, stepped by ltx_adamw_multi_sr (the coefficient and the shadow as arguments), and an
+        f32 bucket without clip or EMA by ltx_adamw_multi."""
         from . import _lib
         ema = self.ema
-        what = "FusedAdamW(max_grad_norm)" if max_norm > 0 else "FusedAdamW(ema)"
-        kernels = "clip kernels" if max_norm > 0 else "EMA kernels"
+        sr = self.bf16_update == "stochastic"
+        what = ("FusedAdamW(max_grad_norm)" if max_norm > 0 else "FusedAdamW(ema)" if ema is not None
+                else "FusedAdamW(bf16_update)")
+        kernels = ("clip kernels" if max_norm > 0 else "EMA kernels" if ema is not None
+                   else "stochastic-rounding kernels")
         todo, device = [], None
         for group in self.param_groups:
             for p in group["params"]:
@@ -403,25 +521,37 @@ class FusedAdamW(torch.optim.Optimizer):
                 elif p.device != device:
                     raise ValueError(f"{what}: parameters on {device} and {p.device}; the table kernels "
                                      f"(and the global norm) run on one device")
-        launches = []  # (device table, rows, is_bf16, group, step, the 6-field table of the norm pass)
+        ordinals = self._ordinals() if sr else None
+        # (device table, rows, 0 f32 / 1 bf16 / 2 bf16 with f32 moments and the stochastic store, group, step,
+        # the 6-field table of the norm pass)
+        launches = []
         for gi, group in enumerate(self.param_groups):
-            buckets = {}  # (dtype, step) -> items, in order of first appearance
+            buckets = {}  # (dtype or "sr", step) -> items, in order of first appearance
             for p in group["params"]:
                 if p.grad is None or p.numel() == 0:
                     continue
                 st = self.state[p]
+                mixed = sr and p.dtype == torch.bfloat16
+                if mixed:
+                    self._mixed_state(p, st)
                 if not st:
                     st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
+                    st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32 if mixed else p.dtype)
+                    st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32 if mixed else p.dtype)
                 if ema is not None and "ema" not in st:
                     # with the moments; later only where a restore brought moments without shadows
                     st["ema"] = p.detach().float().clone()
                 st["step"] += 1
-                buckets.setdefault((p.dtype, st["step"]), []).append((p, p.grad.contiguous(), st))
+                buckets.setdefault(("sr" if mixed else p.dtype, st["step"]), []).append((p, p.grad.contiguous(), st))
             seen = {}
             for (dtype, step), items in buckets.items():
                 j = seen[dtype] = seen.get(dtype, -1) + 1
+                if dtype == "sr":
+                    dev, nrows = self._sr_table(items, ("sr", gi, j), ordinals, ema is not None)
+                    # the norm kernel reads a 6-field row's gradient, first element and count only
+                    norm_dev = self._table(items, torch.bfloat16, ("sr_norm", gi, j))[0] if max_norm > 0 else dev
+                    launches.append((dev, nrows, 2, group, step, norm_dev))
+                    continue
                 # the unclipped step's cache entry for the usual case: one group, one step count
                 slot = dtype if (gi, j) == (0, 0) else (dtype, gi, j)
                 dev, nrows = self._table(items, dtype, slot, ema=ema is not None)
@@ -436,41 +566,40 @@ class FusedAdamW(torch.optim.Optimizer):
         if not launches:
             self.clip_sumsq = self.grad_norm = self.clip_coef = None
             return
-        if not max_norm > 0:
-            stream = ops._s()
-            for dev, nrows, is_bf16, group, step, _ in launches:
-                b1, b2 = group["betas"]
-                ops.call("ltx_adamw_multi_ema", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
-                         float(b2), float(group["eps"]), float(group["weight_decay"]), int(step), None, omd, stream)
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
-            ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
-            return
-        total = sum(n for _, n, _, _, _, _ in launches)
-        if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
-            self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
-        part = self._clip_part
-        # the record {f64 sumsq, f32 norm, f32 coef}: a fresh one per step, so a norm somebody
-        # holds keeps its value
-        rec = torch.empty(2, dtype=torch.float64, device=device)
-        tail = rec[1:].view(torch.float32)
         stream = ops._s()
-        off = 0
-        for _, nrows, is_bf16, _, _, dev in launches:
-            ops.call("ltx_grad_sumsq_multi", ops._p(dev), nrows, is_bf16,
-                     ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
-            off += nrows
-        ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
-        for dev, nrows, is_bf16, group, step, _ in launches:
+        coef = None
+        if max_norm > 0:
+            total = sum(n for _, n, _, _, _, _ in launches)
+            if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
+                self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
+            part = self._clip_part
+            # the record {f64 sumsq, f32 norm, f32 coef}: a fresh one per step, so a norm somebody
+            # holds keeps its value
+            rec = torch.empty(2, dtype=torch.float64, device=device)
+            tail = rec[1:].view(torch.float32)
+            off = 0
+            for _, nrows, mode, _, _, dev in launches:
+                ops.call("ltx_grad_sumsq_multi", ops._p(dev), nrows, 1 if mode else 0,
+                         ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
+                off += nrows
+            ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
+            coef = ops._p(tail[1])
+            self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
+        else:
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+        for dev, nrows, mode, group, step, _ in launches:
             b1, b2 = group["betas"]
-            if ema is not None:
-                ops.call("ltx_adamw_multi_ema", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
-                         float(b2), float(group["eps"]), float(group["weight_decay"]), int(step),
-                         ops._p(tail[1]), omd, stream)
-                continue
-            ops.call("ltx_adamw_multi_clip", ops._p(dev), nrows, is_bf16, float(group["lr"]), float(b1),
-                     float(b2), float(group["eps"]), float(group["weight_decay"]), int(step),
-                     ops._p(tail[1]), stream)
-        self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
+            hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                     int(step))
+            if mode == 2:
+                ops.call("ltx_adamw_multi_sr", ops._p(dev), nrows, *hyper, coef, 1 if ema is not None else 0,
+                         0.0 if omd is None else omd, self.sr_seed, stream)
+            elif ema is not None:
+                ops.call("ltx_adamw_multi_ema", ops._p(dev), nrows, mode, *hyper, coef, omd, stream)
+            elif coef is not None:
+                ops.call("ltx_adamw_multi_clip", ops._p(dev), nrows, mode, *hyper, coef, stream)
+            else:  # an f32 bucket of the stochastic mode without clip or EMA
+                ops.call("ltx_adamw_multi", ops._p(dev), nrows, mode, *hyper, stream)
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
     # ---- the averaged weights as the model's weights ---------------------------------------
@@ -568,6 +697,11 @@ class FusedProdigy(FusedAdamW):
     (max_grad_norm, grad_norm / clip_coef, ema, ema_swap_in / ema_swap_out / ema_weights) plus `record` and
     `d`, a 0-dim float64 device tensor that syncs only at float(). One parameter group only.
 
+    `bf16_update="stochastic"` / `sr_seed`, as FusedAdamW's: a bf16 parameter keeps f32 exp_avg, exp_avg_sq
+    and s (p0 stays a bf16 clone, which is exact), both passes run the f32 arithmetic on float(p), float(g)
+    and float(p0) (ltx_prodigy_moments_multi in its mixed mode, ltx_prodigy_apply_multi_sr), and pass 2
+    stores the parameter stochastically rounded (stochastic_round_bf16).
+
     Two departures from the published code: the factor (d / d0) dlr multiplies the summed numerator once
     instead of every tensor's dot product, and a bf16 tensor's dot product is not rounded to bf16 before it
     is added (products in f32, sums in f64, fixed order: bitwise reproducible, the same on every rank)."""
@@ -579,7 +713,7 @@ class FusedProdigy(FusedAdamW):
 
     def __init__(self, params, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0,
                  decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
-                 growth_rate=float("inf"), max_grad_norm=None, ema=None):
+                 growth_rate=float("inf"), max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas must be in [0, 1), got {betas}")
@@ -596,7 +730,7 @@ class FusedProdigy(FusedAdamW):
         if not float(growth_rate) > 0.0:
             raise ValueError(f"growth_rate must be > 0, got {growth_rate}")
         super().__init__(params, lr=lr, betas=(b1, b2), eps=float(eps), weight_decay=float(weight_decay),
-                         max_grad_norm=max_grad_norm, ema=ema)
+                         max_grad_norm=max_grad_norm, ema=ema, bf16_update=bf16_update, sr_seed=sr_seed)
         extra = dict(beta3=None if beta3 is None else float(beta3), decouple=bool(decouple),
                      use_bias_correction=bool(use_bias_correction), safeguard_warmup=bool(safeguard_warmup),
                      d0=float(d0), d_coef=float(d_coef), growth_rate=float(growth_rate))
@@ -644,18 +778,20 @@ class FusedProdigy(FusedAdamW):
         """The step-size estimate: a 0-dim float64 view of the device record (float() syncs)."""
         return self.ensure_record()[0]
 
-    def _prodigy_table(self, items, dtype):
+    def _prodigy_table(self, items, dtype, slot=None, ordinals=None):
         """(device table, rows) of ROW-field rows (param, grad, exp_avg, exp_avg_sq, first element, count,
-        s, p0, shadow or 0, 0), cached on the buffers' pointers like FusedAdamW._table."""
+        s, p0, shadow or 0, 0 -- or, with `ordinals` for the stochastic step, the parameter's ordinal),
+        cached on the buffers' pointers like FusedAdamW._table."""
         ptrs = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
-                      st["s"].data_ptr(), st["p0"].data_ptr(), st["ema"].data_ptr() if self.ema is not None else 0)
+                      st["s"].data_ptr(), st["p0"].data_ptr(), st["ema"].data_ptr() if self.ema is not None else 0,
+                      0 if ordinals is None else ordinals[p])
                      for p, g, st in items)
-        slot = ("prodigy", dtype)
+        slot = ("prodigy", dtype) if slot is None else slot
         hit = self._table_cache.get(slot)
         if hit is not None and hit[0] == ptrs:
             return hit[1], hit[2]
-        rows = [(pp, gp, ap, vp, start, min(self.CHUNK, n - start), sp, p0p, ep, 0)
-                for pp, gp, ap, vp, n, sp, p0p, ep in ptrs for start in range(0, n, self.CHUNK)]
+        rows = [(pp, gp, ap, vp, start, min(self.CHUNK, n - start), sp, p0p, ep, o)
+                for pp, gp, ap, vp, n, sp, p0p, ep, o in ptrs for start in range(0, n, self.CHUNK)]
         host = torch.tensor(rows, dtype=torch.int64).pin_memory()
         dev = host.to(items[0][0].device, non_blocking=True)
         self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
@@ -688,39 +824,54 @@ class FusedProdigy(FusedAdamW):
             elif p.device != device:
                 raise ValueError(f"FusedProdigy: parameters on {device} and {p.device}; the table kernels (and "
                                  f"the sums behind d) run on one device")
-        buckets = {}  # dtype -> items, in order of first appearance
+        sr = self.bf16_update == "stochastic"
+        ordinals = self._ordinals() if sr else None
+        # dtype -> items, in order of first appearance; the stochastic step's bf16 parameters under
+        # ("sr", step): the step count is part of their rounding's counter
+        buckets = {}
         for p in group["params"]:
             if p.grad is None or p.numel() == 0:
                 continue
             st = self.state[p]
+            mixed = sr and p.dtype == torch.bfloat16
+            if mixed:
+                self._mixed_state(p, st)
+            mdtype = torch.float32 if mixed else p.dtype
             if not st:
                 st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p)
-                st["exp_avg_sq"] = torch.zeros_like(p)
+                st["exp_avg"] = torch.zeros_like(p, dtype=mdtype)
+                st["exp_avg_sq"] = torch.zeros_like(p, dtype=mdtype)
             if "s" not in st:  # with the moments, before anything moves
-                st["s"] = torch.zeros_like(p)
+                st["s"] = torch.zeros_like(p, dtype=mdtype)
                 st["p0"] = p.detach().clone()
             if ema is not None and "ema" not in st:
                 st["ema"] = p.detach().float().clone()
             st["step"] += 1
-            buckets.setdefault(p.dtype, []).append((p, p.grad.contiguous(), st))
+            buckets.setdefault(("sr", st["step"]) if mixed else p.dtype, []).append((p, p.grad.contiguous(), st))
         if not buckets:
             self.clip_sumsq = self.grad_norm = self.clip_coef = None
             return
         rec = self.ensure_record(device)
         if rec.device != device:
             raise ValueError(f"FusedProdigy: the record is on {rec.device}, the parameters on {device}")
-        launches = []  # (Prodigy table, rows, is_bf16, the 6-field table of the norm pass or None)
-        for dtype, items in buckets.items():
+        # (Prodigy table, rows, 0 f32 / 1 bf16 / 2 the stochastic step's bf16 with f32 state, the 6-field
+        # table of the norm pass or None, the step count of a mode-2 bucket)
+        launches = []
+        for j, (dtype, items) in enumerate(buckets.items()):
+            if isinstance(dtype, tuple):
+                dev, nrows = self._prodigy_table(items, torch.bfloat16, ("prodigy_sr", j), ordinals)
+                norm_dev = self._table(items, torch.bfloat16, ("sr_norm", j))[0] if max_norm > 0 else None
+                launches.append((dev, nrows, 2, norm_dev, dtype[1]))
+                continue
             dev, nrows = self._prodigy_table(items, dtype)
             norm_dev = self._table(items, dtype)[0] if max_norm > 0 else None
-            launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, norm_dev))
+            launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, norm_dev, None))
         omd = 0.0
         if ema is not None:
             self.ema_steps += 1
             self.ema_decay = ema.decay_at(self.ema_steps)
             omd = 1.0 - self.ema_decay  # in double; the entry point takes it as one f32
-        total = sum(n for _, n, _, _ in launches)
+        total = sum(n for _, n, _, _, _ in launches)
         if self._prodigy_part is None or self._prodigy_part.numel() < 2 * total or self._prodigy_part.device != device:
             self._prodigy_part = torch.empty(2 * total, dtype=torch.float64, device=device)
         part = self._prodigy_part
@@ -732,8 +883,8 @@ class FusedProdigy(FusedAdamW):
             clip_rec = torch.empty(2, dtype=torch.float64, device=device)  # fresh per step, as FusedAdamW's
             tail = clip_rec[1:].view(torch.float32)
             off = 0
-            for _, nrows, is_bf16, norm_dev in launches:
-                ops.call("ltx_grad_sumsq_multi", ops._p(norm_dev), nrows, is_bf16,
+            for _, nrows, mode, norm_dev, _ in launches:
+                ops.call("ltx_grad_sumsq_multi", ops._p(norm_dev), nrows, 1 if mode else 0,
                          ctypes.c_void_p(self._clip_part.data_ptr() + 8 * off), stream)
                 off += nrows
             ops.call("ltx_grad_clip_coef", ops._p(self._clip_part), total, float(max_norm), ops._p(clip_rec), stream)
@@ -746,15 +897,19 @@ class FusedProdigy(FusedAdamW):
         d0, wd = float(group["d0"]), float(group["weight_decay"])
         decouple, use_bc = bool(group["decouple"]), int(bool(group["use_bias_correction"]))
         off = 0
-        for dev, nrows, is_bf16, _ in launches:
-            ops.call("ltx_prodigy_moments_multi", ops._p(dev), nrows, is_bf16, ops._p(rec), lr, b1, b2, b3, d0,
+        for dev, nrows, mode, _, _ in launches:
+            ops.call("ltx_prodigy_moments_multi", ops._p(dev), nrows, mode, ops._p(rec), lr, b1, b2, b3, d0,
                      0.0 if decouple else wd, use_bc, int(bool(group["safeguard_warmup"])), coef,
                      ctypes.c_void_p(part.data_ptr() + 16 * off), stream)
             off += nrows
         ops.call("ltx_prodigy_d_update", ops._p(part), total, ops._p(rec), lr, b1, b2, b3, d0,
                  float(group["d_coef"]), float(group["growth_rate"]), use_bc, stream)
-        for dev, nrows, is_bf16, _ in launches:
-            ops.call("ltx_prodigy_apply_multi", ops._p(dev), nrows, is_bf16, ops._p(rec), float(group["eps"]),
+        for dev, nrows, mode, _, step in launches:
+            if mode == 2:
+                ops.call("ltx_prodigy_apply_multi_sr", ops._p(dev), nrows, ops._p(rec), float(group["eps"]),
+                         wd if decouple else 0.0, 1 if ema is not None else 0, omd, self.sr_seed, int(step), stream)
+                continue
+            ops.call("ltx_prodigy_apply_multi", ops._p(dev), nrows, mode, ops._p(rec), float(group["eps"]),
                      wd if decouple else 0.0, 1 if ema is not None else 0, omd, stream)
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
@@ -787,12 +942,32 @@ def optimizer_from_config(config):
     `prodigy_use_bias_correction`, `prodigy_safeguard_warmup`, `prodigy_decouple`. The rate is
     config.learning_rate; with Prodigy None means 1.0. ValueError for another optimizer name, a value out
     of range, or a prodigy_* key without `optimizer: prodigy`; NotImplementedError for Prodigy outside
-    train_mode 'lora_audio' or with use_deepspeed (the sharded Zero2AdamW step is its own path)."""
+    train_mode 'lora_audio' or with use_deepspeed (the sharded Zero2AdamW step is its own path).
+
+    `bf16_update` ("nearest", also when absent: today's constructor call; "stochastic") and `bf16_sr_seed`
+    (an integer in [0, 2^64), 0 when absent) select the stochastically rounded bf16 step of either
+    optimizer; they become the keyword arguments bf16_update / sr_seed in stochastic mode only. The seed
+    comes from the config and never from a generator, so every data-parallel rank rounds alike and the
+    replicas stay identical without a collective. ValueError for another mode, a seed out of range or a
+    seed without `bf16_update: stochastic`; NotImplementedError outside train_mode 'lora_audio' or with
+    use_deepspeed."""
     kind = getattr(config, "optimizer", None)
     kind = "adamw" if kind is None else kind
     if kind not in OPTIMIZERS:
         raise ValueError(f"optimizer {kind!r} is not one of {', '.join(OPTIMIZERS)}")
     kw = {}
+    mode, seed = getattr(config, "bf16_update", None), getattr(config, "bf16_sr_seed", None)
+    mode, seed = _check_bf16_update("nearest" if mode is None else mode, 0 if seed is None else seed)
+    if mode == "stochastic":
+        train_mode = getattr(config, "train_mode", "full")
+        if train_mode != "lora_audio" or getattr(config, "use_deepspeed", False):
+            raise NotImplementedError(f"bf16_update 'stochastic' with train_mode={train_mode!r}, use_deepspeed="
+                                      f"{bool(getattr(config, 'use_deepspeed', False))}: the stochastically rounded "
+                                      f"step exists in FusedAdamW and FusedProdigy, which step the lora_audio "
+                                      f"trainable set; the sharded Zero2AdamW path has none")
+        kw.update(bf16_update=mode, sr_seed=seed)
+    elif getattr(config, "bf16_sr_seed", None) is not None:
+        raise ValueError("bf16_sr_seed set without bf16_update: stochastic")
     b1, b2 = getattr(config, "adam_beta1", None), getattr(config, "adam_beta2", None)
     if b1 is not None or b2 is not None:
         betas = (0.9 if b1 is None else float(b1), 0.999 if b2 is None else float(b2))
