@@ -294,6 +294,47 @@ def test_prodigy_is_the_f32_statement_then_the_stochastic_store_bitwise(variant)
     assert all(not torch.equal(p.detach(), s0) for p, s0 in zip(ps[3:], start[3:]))  # the tensors moved
 
 
+OFF_SIZES = [1, 7, 8, 9, 2047, 2049, 4096 + 13]
+
+
+def _one_element_off(t):
+    """a copy of `t` that starts one element (2 or 4 bytes) past a 16-byte boundary"""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    out = buf[1:].copy_(t.detach())
+    assert out.data_ptr() % 16 == t.element_size()
+    return out
+
+
+@pytest.mark.parametrize("kind", ["adamw", "prodigy"])
+def test_tensors_one_element_off_the_16_byte_boundary_give_the_aligned_tensors_bits(kind):
+    """Parameters and gradients that start one element off a 16-byte boundary take the one-element walk of
+    ltx_adamw_multi_sr, of ltx_prodigy_moments_multi's mixed mode and of ltx_prodigy_apply_multi_sr (each with
+    the clip and the shadow column); the aligned copies of the same values take the 16-byte walk with its
+    single-element tail. Parameters, moments, s and shadows are bitwise the same after each of 3 steps."""
+    from ltx_amd.training import EMASchedule, FusedAdamW, FusedProdigy
+    cls, kw, scale = (FusedAdamW, dict(lr=LR, weight_decay=WD), 1.0) if kind == "adamw" else (FusedProdigy, {}, SMALL)
+    pa = make_params(3, DEV, scale=scale, sizes=OFF_SIZES)
+    pb = [torch.nn.Parameter(_one_element_off(p)) for p in pa]
+    a, b = (cls(ps, max_grad_norm=0.5, ema=EMASchedule(0.999), bf16_update="stochastic", sr_seed=SEED, **kw)
+            for ps in (pa, pb))
+    for k in range(3):
+        grads = make_grads(30 + k, DEV, sizes=OFF_SIZES)
+        for x, y, g in zip(pa, pb, grads):
+            x.grad, y.grad = g.clone(), _one_element_off(g)
+            assert x.data_ptr() % 16 == 0 and x.grad.data_ptr() % 16 == 0
+        a.step()
+        b.step()
+        assert 0.0 < float(a.clip_coef) < 1.0 and float(a.clip_coef) == float(b.clip_coef)
+        for i, (x, y) in enumerate(zip(pa, pb)):
+            assert torch.equal(x.detach(), y.detach()), (kind, k, i, "param")
+            keys = [key for key, v in a.state[x].items() if torch.is_tensor(v)]
+            assert "ema" in keys and "exp_avg_sq" in keys and ("s" in keys) == (kind == "prodigy")
+            for key in keys:
+                assert torch.equal(a.state[x][key], b.state[y][key]), (kind, k, i, key)
+    start = make_params(3, DEV, scale=scale, sizes=OFF_SIZES)
+    assert all(not torch.equal(x.detach(), p) for x, p in zip(pa[4:], start[4:]))  # the large tensors moved
+
+
 # ---------------------------------------------------------------------------------------------
 # the tiny model through train_loop
 # ---------------------------------------------------------------------------------------------

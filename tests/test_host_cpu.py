@@ -643,3 +643,56 @@ def test_block_saved_tensors_come_back_by_name():
             got = getattr(sv, k)
             assert len(got) == len(groups[k]) and all(a is b for a, b in zip(got, groups[k])), (k, a2, a1, ff)
         assert sv.x2 is x2
+
+
+def test_chunk_table_rows_of_the_five_layouts():
+    """training.chunk_rows / tensor_fields: for tensors of 1, 2048, 2049 and 2 * 2048 + 13 elements the
+    rows of each of the five chunk-table layouts are the rows written out here by hand -- pointers in their
+    columns, `start` a multiple of 2048 and `count` what is left (at most 2048), zeros where a layout has
+    none, the ordinal in the last column of the stochastic and Prodigy rows."""
+    from ltx_amd.training import LAYOUTS, FusedAdamW, chunk_rows, table_rows, tensor_fields
+    C = FusedAdamW.CHUNK
+    assert C == 2048
+    sizes = [1, 2048, 2049, 2 * 2048 + 13]
+    # the pure function on plain integers: head + (start, count) + tail
+    got = chunk_rows([(n, (10 * i + 1, 10 * i + 2), (10 * i + 3,)) for i, n in enumerate(sizes)], C)
+    assert got == [(1, 2, 0, 1, 3),
+                   (11, 12, 0, 2048, 13),
+                   (21, 22, 0, 2048, 23), (21, 22, 2048, 1, 23),
+                   (31, 32, 0, 2048, 33), (31, 32, 2048, 2048, 33), (31, 32, 4096, 13, 33)]
+    assert chunk_rows([(0, (1,), (2,))], C) == [] and chunk_rows([], C) == []
+    # the layouts, over CPU tensors (their pointers are as good as a device's)
+    names = ("p", "g", "exp_avg", "exp_avg_sq", "s", "p0", "ema", "stash")
+    T = [{k: torch.zeros(n) for k in names} for n in sizes]
+    items = [(t["p"], t["g"], t) for t in T]
+    ordinals = {t["p"]: 5 + 2 * i for i, t in enumerate(T)}
+    chunks = [[(0, 1)], [(0, 2048)], [(0, 2048), (2048, 1)], [(0, 2048), (2048, 2048), (4096, 13)]]
+    P = lambda t, k: t[k].data_ptr()  # noqa: E731
+
+    def want(row_of):
+        return [row_of(t, i, start, count) for i, t in enumerate(T) for start, count in chunks[i]]
+
+    base = lambda t: (P(t, "p"), P(t, "g"), P(t, "exp_avg"), P(t, "exp_avg_sq"))  # noqa: E731
+    cases = {
+        "adamw": (tensor_fields("adamw", items), lambda t, i, a, n: base(t) + (a, n)),
+        "ema": (tensor_fields("ema", items), lambda t, i, a, n: base(t) + (a, n, P(t, "ema"), 0)),
+        "sr": (tensor_fields("sr", items, True, ordinals), lambda t, i, a, n: base(t) + (a, n, P(t, "ema"), 5 + 2 * i)),
+        "sr without shadows": (tensor_fields("sr", items, False, ordinals),
+                               lambda t, i, a, n: base(t) + (a, n, 0, 5 + 2 * i)),
+        "swap": (tensor_fields("swap", [(t["p"], t["ema"], t["stash"]) for t in T]),
+                 lambda t, i, a, n: (P(t, "p"), 0, 0, 0, a, n, P(t, "ema"), P(t, "stash"))),
+        "prodigy": (tensor_fields("prodigy", items, True, ordinals),
+                    lambda t, i, a, n: base(t) + (a, n, P(t, "s"), P(t, "p0"), P(t, "ema"), 5 + 2 * i)),
+        "prodigy nearest, no shadows": (tensor_fields("prodigy", items),
+                                        lambda t, i, a, n: base(t) + (a, n, P(t, "s"), P(t, "p0"), 0, 0)),
+    }
+    assert {c.split()[0] for c in cases} == set(LAYOUTS)
+    for name, (fields, row_of) in cases.items():
+        rows = table_rows(fields, C)
+        assert rows == want(row_of), name
+        layout = LAYOUTS[name.split()[0]]
+        assert len(rows) == 7 and all(len(r) == len(layout) for r in rows), name
+        assert layout.index("start") == 4 and layout.index("count") == 5
+        # a zero of the layout's statement is a zero in every row
+        assert all(r[k] == 0 for r in rows for k, f in enumerate(layout) if f == 0), name
+    assert [len(LAYOUTS[k]) for k in ("adamw", "ema", "sr", "swap", "prodigy")] == [6, 8, 8, 8, 10]

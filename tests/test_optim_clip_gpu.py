@@ -156,10 +156,10 @@ def test_adamw_multi_clip_is_adamw_multi_on_the_scaled_gradient(coef):
         for dt in (torch.float32, torch.bfloat16):
             idx = [i for i, d in enumerate(DTYPES) if d == dt]
             bf = 1 if dt == torch.bfloat16 else 0
-            dev, rows = ta._table([(pa[i], grads[i], sa[i]) for i in idx], dt)
+            dev, rows = ta._items_table("adamw", dt, [(pa[i], grads[i], sa[i]) for i in idx])
             assert rows == sum(-(-SIZES[i] // 2048) for i in idx)
             ops.call("ltx_adamw_multi_clip", ops._p(dev), rows, bf, *hyper, step, ops._p(c), ops._s())
-            dev, rows = tb._table([(pb[i], fed[i], sb[i]) for i in idx], dt)
+            dev, rows = tb._items_table("adamw", dt, [(pb[i], fed[i], sb[i]) for i in idx])
             ops.call("ltx_adamw_multi", ops._p(dev), rows, bf, *hyper, step, ops._s())
         for i in range(len(SIZES)):
             assert torch.equal(pa[i], pb[i]) and not torch.equal(pa[i], _params(7)[i]), (step, i)

@@ -93,7 +93,8 @@ def _pass1_and_update(opt, by_dtype, hyper, coef=None):
     behind the first's), then ltx_prodigy_d_update. Returns the partials as a [rows, 2] f64 tensor."""
     from ltx_amd import ops
     lr, b1, b2, b3, d0, d_coef, growth = hyper
-    tables = [opt._prodigy_table(items, dt) + (1 if dt == torch.bfloat16 else 0,) for dt, items in by_dtype.items()]
+    tables = [opt._items_table("prodigy", dt, items) + (1 if dt == torch.bfloat16 else 0,)
+              for dt, items in by_dtype.items()]
     total = sum(n for _, n, _ in tables)
     part = torch.full((2 * total,), float("nan"), dtype=torch.float64, device=DEV)  # overwritten, never accumulated into
     off = 0

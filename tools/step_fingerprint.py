@@ -1,4 +1,5 @@
-"""Fingerprint of one step per model configuration, to hold a refactor of the fused block to equality.
+"""Fingerprint of one step per model configuration (and, group `optim`, of three optimizer steps per
+optimizer condition), to hold a refactor to equality.
 
     python tools/step_fingerprint.py run --pkg <dir that holds ltx_amd/> --group <name> --out fp.json
     python tools/step_fingerprint.py compare old.json new.json [--md table.md]
@@ -40,6 +41,10 @@ GROUPS = {
     "lora_dy0": ({"LTX_LORA_DY": "0"}, ["all3"]),
     # one LTX-2B-width block, B = 8, N = 1024 (M = 8192: past the token-sized gates), r = 16, 256 text tokens
     "2b": ({}, ["2b_all3", "2b_dora"]),
+    # the optimizer step alone, no model: the twelve conditions of tools/bf16_sr_bench.py, and AdamW with
+    # clip + EMA followed by ema_swap_in / ema_swap_out
+    "optim": ({}, [f"{kind}{variant}_{mode}" for kind in ("adamw", "prodigy") for variant in ("", "_clip", "_ema")
+                   for mode in ("nearest", "stochastic")] + ["adamw_clip_ema_swap"]),
 }
 
 
@@ -169,6 +174,56 @@ def _one(name, case, torch):
     return rec
 
 
+def _optim_one(name, torch):
+    """Three steps of one optimizer condition on the tensors of tests/bf16_sr_utils.py (BF16_SIZES bf16
+    tensors and one f32 tensor of F32_SIZE) with seeded gradients. In the record's shape: "kernels" are the
+    launch timer's names and the entry points called, in order, "output" is the
+    hash of the last clip record, "loss" of the Prodigy record, "grads" holds every parameter, state
+    tensor and shadow (and, for the swap, the weights while swapped in)."""
+    from bf16_sr_utils import make_grads, make_params
+    from ltx_amd import ops
+    from ltx_amd.training import EMASchedule, FusedAdamW, FusedProdigy
+    swap = name == "adamw_clip_ema_swap"
+    kind, mode = name.split("_")[0], "stochastic" if name.endswith("_stochastic") else "nearest"
+    cls, lr = (FusedProdigy, 1.0) if kind == "prodigy" else (FusedAdamW, 1e-3)
+    ps = make_params(1, "cuda")
+    opt = cls(ps, lr=lr, max_grad_norm=0.5 if "_clip" in name else None,
+              ema=EMASchedule(0.999) if "_ema" in name else None, bf16_update=mode, sr_seed=0x5EED0123456789AB)
+    grads = [make_grads(10 + k, "cuda") for k in range(3)]
+    hashes = {}
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    timer = ops.LaunchTimer()
+    ops.set_launch_timer(timer)
+    # the launch timer labels GEMM and attention launches only: the optimizer's sequence is the entry points
+    # ops.call is given
+    calls, inner = [], ops.call
+    ops.call = lambda fn, *args: (calls.append(fn), inner(fn, *args))[1]
+    try:
+        for gs in grads:
+            for p, g in zip(ps, gs):
+                p.grad = g
+            opt.step()
+        if swap:
+            opt.ema_swap_in()
+            hashes.update({f"swapped_in.{i}": _sha(p) for i, p in enumerate(ps)})
+            opt.ema_swap_out()
+    finally:
+        ops.call = inner
+        ops.set_launch_timer(None)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
+    for i, p in enumerate(ps):
+        hashes[f"param.{i}"] = _sha(p)
+        for key, v in sorted(opt.state[p].items()):
+            hashes[f"state.{i}.{key}"] = _sha(v if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float64))
+    clip = None if opt.clip_sumsq is None else _sha(torch.stack([opt.clip_sumsq, opt.grad_norm.double(),
+                                                                 opt.clip_coef.double()]))
+    record = getattr(opt, "record", None)
+    return {"kernels": [r[0] for r in timer.records] + calls, "peak_bytes": peak, "output": clip,
+            "loss": None if record is None else _sha(record), "grads": hashes}
+
+
 def run(args):
     env, names = GROUPS[args.group]
     os.environ.update(env)
@@ -179,10 +234,11 @@ def run(args):
     from ltx_amd import _lib
     _lib.ensure_device("cuda:0")
     torch.cuda.set_device(0)
-    case = _2b_case() if args.group == "2b" else _tiny_case()
+    case = None if args.group == "optim" else _2b_case() if args.group == "2b" else _tiny_case()
     out = {"pkg": os.path.dirname(os.path.abspath(ltx_amd.__file__)), "env": env, "configs": {}}
     for name in names:
-        out["configs"][f"{args.group}/{name}"] = _one(name, case, torch)
+        rec = _optim_one(name, torch) if case is None else _one(name, case, torch)
+        out["configs"][f"{args.group}/{name}"] = rec
         gc.collect()
         torch.cuda.empty_cache()
         print(f"{args.group}/{name}: {len(out['configs'][f'{args.group}/{name}']['kernels'])} launches", flush=True)

@@ -1,6 +1,6 @@
-// The per-element AdamW update shared by the optimizer kernels (elementwise.hip: ltx_adamw_step /
-// ltx_adamw_multi; optim.hip: ltx_adamw_multi_clip / ltx_adamw_multi_ema), so every entry point runs one
-// arithmetic.
+// The per-element AdamW update shared by the optimizer kernels (elementwise.hip: ltx_adamw_step; optim.hip:
+// ltx_adamw_multi / ltx_adamw_multi_clip / ltx_adamw_multi_ema / ltx_adamw_multi_sr), so every entry point
+// runs one arithmetic; the shadow's step (ema_update) serves prodigy.hip too.
 #pragma once
 #include <cmath>
 

@@ -1,6 +1,10 @@
-// Register-level access to the rows of the optimizer chunk tables (optim.hip, prodigy.hip): N consecutive
-// elements of a bf16 or f32 tensor as f32 values, one element per lane or 16 bytes per access.
+// What the kernels over the optimizer chunk tables (optim.hip, prodigy.hip) share: register-level access to
+// a row's tensors (N consecutive elements of a bf16 or f32 tensor as f32 values, one element per lane or 16
+// bytes per access), the walk of a row's elements, the fixed-order sums behind the f64 partials, and the
+// host's choice of a kernel instantiation from run-time flags.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "philox.h"
 
@@ -76,6 +80,71 @@ __device__ __forceinline__ void st_sr(void* base, int64_t i, float (&x)[N], cons
     }
     *(u32x4*)((bf16_t*)base + i) = w;
   }
+}
+
+// The block's walk of one row, `count` elements from element `start`, calling at(N, i) for N consecutive
+// elements at i (N a std::integral_constant). With `vector_ok` (the caller's: every tensor touched 16-byte
+// aligned, and whatever else its stores need) count / VEC steps of VEC elements, thread-strided, then the
+// row's last count % VEC elements one per lane; otherwise one element per lane throughout.
+template <int VEC, class At>
+__device__ __forceinline__ void walk_row(int64_t start, int64_t count, bool vector_ok, At&& at) {
+  if (vector_ok) {
+    const int64_t nvec = count / VEC;
+    for (int64_t q = threadIdx.x; q < nvec; q += 256) at(std::integral_constant<int, VEC>{}, start + q * VEC);
+    const int64_t i = start + nvec * VEC + threadIdx.x;
+    if (i < start + count) at(std::integral_constant<int, 1>{}, i);
+  } else {
+    for (int64_t i = start + threadIdx.x; i < start + count; i += 256) at(std::integral_constant<int, 1>{}, i);
+  }
+}
+
+// the block's sum of one f64 per thread: wave butterfly, then the four waves in order; valid in thread 0
+__device__ __forceinline__ double block_sum_ordered(double x, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// One block's sums of K interleaved f64 columns of `n` rows (part[K * i + c]), left in red[c][0]: each of
+// the 256 threads adds its strided rows in order, then a fixed-shape tree. Eight loads per column are in
+// flight at a time, added in the strided order (a row past the end reads as 0): one block walks ~10^4
+// partials, and with one load per add it took 11 us against 4.7 us this way.
+template <int K>
+__device__ __forceinline__ void strided_partials_sum(const double* __restrict__ part, int n, double (&red)[K][256]) {
+  double s[K] = {};
+  for (int64_t base = threadIdx.x; base < n; base += 8 * 256) {
+    double v[K][8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = base + k * 256;
+#pragma unroll
+      for (int c = 0; c < K; ++c) v[c][k] = i < n ? part[K * i + c] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+#pragma unroll
+      for (int c = 0; c < K; ++c) s[c] += v[c][k];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < K; ++c) red[c][threadIdx.x] = s[c];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+#pragma unroll
+      for (int c = 0; c < K; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+}
+
+// host: f(std::true_type) or f(std::false_type) by a run-time flag, nested once per template parameter
+template <class F>
+static inline void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 }  // namespace ltx

@@ -455,22 +455,6 @@ __global__ void adamw_kernel(void* __restrict__ param, const void* __restrict__ 
     adamw_elem<BF16>(param, grad, m_, v_, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps);
 }
 
-// every trainable tensor of one dtype in one launch: a block per table entry
-// (param, grad, exp_avg, exp_avg_sq, first element, count <= 2048), the same per-element math
-template <bool BF16>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ table, float decay, float w1,
-                                                          float b2, float w2, float step_size, float bc2_sqrt,
-                                                          float eps) {
-  const int64_t* e = table + (int64_t)blockIdx.x * 6;
-  void* param = (void*)e[0];
-  const void* grad = (const void*)e[1];
-  void* m = (void*)e[2];
-  void* v = (void*)e[3];
-  const int64_t start = e[4], end = e[4] + e[5];
-  for (int64_t i = start + threadIdx.x; i < end; i += 256)
-    adamw_elem<BF16>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps);
-}
-
 static inline unsigned grid_for(int64_t n, int threads = 256, int64_t cap = 8192) {
   int64_t g = (n + threads - 1) / threads;
   if (g > cap) g = cap;
@@ -693,20 +677,6 @@ int ltx_mse_fwd_bwd(const void* out, const void* v, void* dout, float* stats, in
   hipLaunchKernelGGL(mse_kernel, dim3(MSE_BLOCKS), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)out,
                      (const bf16_t*)v, (bf16_t*)dout, stats, n, norm, grad_scale);
   hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
-}
-
-int ltx_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2, float eps,
-                    float weight_decay, int64_t step, void* stream) {
-  LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi: bad args");
-  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
-  if (is_bf16)
-    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
-                       a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps);
-  else
-    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
-                       a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

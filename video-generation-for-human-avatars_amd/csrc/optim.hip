@@ -1,19 +1,21 @@
-// Global gradient-norm clipping for the multi-tensor optimizer step (ltx_amd/training.py FusedAdamW with
-// max_grad_norm): the LoRA gradients are hundreds of separate tensors of two dtypes (f32 adapters and DoRA
-// magnitudes, the bf16 caption projection), so the norm walks the chunk table the AdamW launch already has --
-// rows of (param, grad, exp_avg, exp_avg_sq, first element, count <= 2048), one block per row -- instead of
-// one reduction per tensor:
-//   1. grad_sumsq_multi_kernel: block b -> part[b], the f64 sum of squares of its row's gradient elements
-//      (one launch per dtype, the second dtype's partials behind the first's);
-//   2. grad_clip_coef_kernel: one block adds all partials and writes the record {sumsq, norm, coef};
-//   3. adamw_multi_clip_kernel: adamw_multi_kernel on g' = R(g * coef), coef read from the record.
+// The multi-tensor AdamW step of the LoRA path (ltx_amd/training.py FusedAdamW) and what rides on it. The
+// LoRA gradients are hundreds of separate tensors of two dtypes (f32 adapters and DoRA magnitudes, the bf16
+// caption projection), so every kernel here walks a chunk table -- int64 rows of (param, grad, exp_avg,
+// exp_avg_sq, first element, count <= 2048), two more fields per row for the EMA, the swap and the
+// stochastic step -- one block per row:
+//   adamw_multi_kernel<BF16, CLIP, EMA>: the AdamW update of a row (ltx_adamw_multi); CLIP on g' = R(g * coef)
+//     with coef read from the clip record (ltx_adamw_multi_clip); EMA with the f32 shadow update fused in, on
+//     8-field rows (ltx_adamw_multi_ema);
+//   the global gradient-norm clip in front of it:
+//     1. grad_sumsq_multi_kernel: block b -> part[b], the f64 sum of squares of its row's gradient elements
+//        (one launch per bucket, the next bucket's partials behind the previous one's);
+//     2. grad_clip_coef_kernel: one block adds all partials and writes the record {sumsq, norm, coef};
+//   ema_swap_multi_kernel: installs the averaged weights for an evaluation or an export and puts the live
+//     ones back;
+//   adamw_multi_sr_kernel: the mixed step of a bf16 parameter with f32 moments and a stochastically rounded
+//     store (FusedAdamW(bf16_update="stochastic"), ltx_adamw_multi_sr).
 // Every sum has a fixed order and there are no atomics, so the record is bitwise reproducible; nothing here
 // reads a value back to the host.
-// Below them, the exponential moving average of the trainable weights (FusedAdamW with ema): the AdamW
-// launch with the f32 shadow update fused in (ltx_adamw_multi_ema), and the two swap kernels that install
-// the averaged weights for an evaluation or an export and put the live ones back.
-// Last, the mixed step of a bf16 parameter with f32 moments and a stochastically rounded store
-// (FusedAdamW(bf16_update="stochastic"), ltx_adamw_multi_sr).
 #include <cmath>
 
 #include "adamw_elem.h"
@@ -45,40 +47,19 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const int64_t* __
     const double v = BF16 ? (double)bf2f(((const bf16_t*)grad)[i]) : (double)((const float*)grad)[i];
     s += v * v;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  s = block_sum_ordered(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// 256 threads add strided partials in a fixed order, then a fixed-shape tree (as sumsq_finish_kernel); the
-// coefficient is clip_coef_kernel's f32 arithmetic with inv_world = 1
+// the sum of all partials (strided_partials_sum, as sumsq_finish_kernel); the coefficient is
+// clip_coef_kernel's f32 arithmetic with inv_world = 1
 __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ part, int nparts,
                                                              float max_norm, ClipRecord* __restrict__ out) {
-  double s = 0.0;
-  // eight strided loads in flight at a time, added in the strided order (a partial past the end reads as 0):
-  // one block walks ~10^4 partials, and with one load per add it took 11 us against 4.7 us this way
-  for (int64_t base = threadIdx.x; base < nparts; base += 8 * 256) {
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = base + k * 256;
-      v[k] = i < nparts ? part[i] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += v[k];
-  }
-  __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  __shared__ double red[1][256];
+  strided_partials_sum<1>(part, nparts, red);
   if (threadIdx.x == 0) {
-    const double sumsq = red[0];
+    const double sumsq = red[0][0];
     const float norm = (float)sqrt(sumsq);
     float c = 1.0f;
     if (max_norm > 0.f) {
@@ -91,49 +72,31 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __res
   }
 }
 
-// adamw_multi_kernel (elementwise.hip) with the gradient scaled by *coef on the way in
-template <bool BF16>
-__global__ __launch_bounds__(256) void adamw_multi_clip_kernel(const int64_t* __restrict__ table, float decay,
-                                                               float w1, float b2, float w2, float step_size,
-                                                               float bc2_sqrt, float eps,
-                                                               const float* __restrict__ coef) {
-  const int64_t* e = table + (int64_t)blockIdx.x * 6;
-  void* param = (void*)e[0];
-  const void* grad = (const void*)e[1];
-  void* m = (void*)e[2];
-  void* v = (void*)e[3];
-  const int64_t start = e[4], end = e[4] + e[5];
-  const float c = *coef;
-  for (int64_t i = start + threadIdx.x; i < end; i += 256)
-    adamw_elem<BF16, true>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c);
-}
-
-// ---- EMA of the trainable weights (FusedAdamW(ema=...)) ----------------------------------------------
-// The EMA table has 8 int64 per row: the six fields above, then the row's tensor's f32 shadow and its
-// stash (a buffer of the parameter's dtype; 0 where an entry point does not use it). Rows index the shadow
-// and the stash like the parameter: element i of the tensor, first element .. first element + count.
-// Accesses are one element per lane (4 or 2 bytes, a wave's 64 lanes contiguous), as in the sibling
-// kernels: a row's first element has only its tensor's alignment, so 16-byte accesses would need a
-// per-row alignment guard and a peeled head / tail, and adamw_multi_kernel already moves its 28 B per
-// f32 element at 6 TB/s this way (profiles/grad_clip_bench.md).
+// Every trainable tensor of one dtype in one launch: a block per table row, the per-element math of the
+// per-tensor adamw_kernel (adamw_elem.h). CLIP: the gradient scaled by *coef on the way in. EMA: rows of 8
+// int64, the six fields above, then the row's tensor's f32 shadow and its stash (a buffer of the parameter's
+// dtype; 0 where an entry point does not use it); the shadow update rides on the parameter register. Rows
+// index the shadow and the stash like the parameter: element i of the tensor, first element .. first element
+// + count.
+// Accesses are one element per lane (4 or 2 bytes, a wave's 64 lanes contiguous): a row's first element has
+// only its tensor's alignment, so 16-byte accesses would need a per-row alignment guard and a peeled tail,
+// and this kernel already moves its 28 B per f32 element at 6 TB/s this way (profiles/grad_clip_bench.md).
 constexpr int EMA_ROW = 8;
 
-// adamw_multi_kernel / adamw_multi_clip_kernel with the shadow update riding on the parameter register
-template <bool BF16, bool CLIP>
-__global__ __launch_bounds__(256) void adamw_multi_ema_kernel(const int64_t* __restrict__ table, float decay,
-                                                              float w1, float b2, float w2, float step_size,
-                                                              float bc2_sqrt, float eps,
-                                                              const float* __restrict__ coef, float omd) {
-  const int64_t* e = table + (int64_t)blockIdx.x * EMA_ROW;
+template <bool BF16, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ table, float decay, float w1,
+                                                          float b2, float w2, float step_size, float bc2_sqrt,
+                                                          float eps, const float* __restrict__ coef, float omd) {
+  const int64_t* e = table + (int64_t)blockIdx.x * (EMA ? EMA_ROW : 6);
   void* param = (void*)e[0];
   const void* grad = (const void*)e[1];
   void* m = (void*)e[2];
   void* v = (void*)e[3];
   const int64_t start = e[4], end = e[4] + e[5];
-  float* shadow = (float*)e[6];
+  float* shadow = EMA ? (float*)e[6] : nullptr;
   const float c = CLIP ? *coef : 1.0f;
   for (int64_t i = start + threadIdx.x; i < end; i += 256)
-    adamw_elem<BF16, CLIP, true>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c, shadow, omd);
+    adamw_elem<BF16, CLIP, EMA>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c, shadow, omd);
 }
 
 // LOAD: stash <- param, param <- R(shadow) (R: round to nearest even to bf16 for bf16 parameters);
@@ -216,14 +179,30 @@ __global__ __launch_bounds__(256) void adamw_multi_sr_kernel(const int64_t* __re
   if (CLIP) c.coef = *coef;
   uint64_t bits = (uint64_t)e[0] | (uint64_t)e[1] | (uint64_t)e[2] | (uint64_t)e[3];
   if (EMA) bits |= (uint64_t)e[6];
-  if ((bits & 15) == 0 && (start & 7) == 0) {
-    const int64_t nvec = count / 8;
-    for (int64_t q = threadIdx.x; q < nvec; q += 256) adamw_sr_at<CLIP, EMA, 8>(e, start + q * 8, c);
-    const int64_t i = start + nvec * 8 + threadIdx.x;
-    if (i < start + count) adamw_sr_at<CLIP, EMA, 1>(e, i, c);
-  } else {
-    for (int64_t i = start + threadIdx.x; i < start + count; i += 256) adamw_sr_at<CLIP, EMA, 1>(e, i, c);
-  }
+  // st_sr's 8 elements share one generator call: a vector starts at a multiple of 8 in its tensor
+  walk_row<8>(start, count, (bits & 15) == 0 && (start & 7) == 0,
+              [&](auto n, int64_t i) { adamw_sr_at<CLIP, EMA, decltype(n)::value>(e, i, c); });
+}
+
+// the launch of adamw_multi_kernel<is_bf16, CLIP, EMA> behind the three nearest-mode entry points
+template <bool CLIP, bool EMA>
+static void launch_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                               float eps, float weight_decay, int64_t step, const float* coef, float omd,
+                               void* stream) {
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
+  with_flag(is_bf16, [&](auto bf) {
+    hipLaunchKernelGGL((adamw_multi_kernel<decltype(bf)::value, CLIP, EMA>), dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef,
+                       omd);
+  });
+}
+
+template <bool LOAD>
+static void launch_ema_swap(const int64_t* table, int64_t nchunks, int is_bf16, void* stream) {
+  with_flag(is_bf16, [&](auto bf) {
+    hipLaunchKernelGGL((ema_swap_multi_kernel<decltype(bf)::value, LOAD>), dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table);
+  });
 }
 
 }  // namespace ltx
@@ -234,12 +213,10 @@ extern "C" {
 
 int ltx_grad_sumsq_multi(const int64_t* table, int64_t nchunks, int is_bf16, double* part, void* stream) {
   LTX_CHECK_ARG(table && part && nchunks > 0 && nchunks < (1LL << 31), "grad_sumsq_multi: bad args");
-  if (is_bf16)
-    hipLaunchKernelGGL(grad_sumsq_multi_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
-                       table, part);
-  else
-    hipLaunchKernelGGL(grad_sumsq_multi_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
-                       table, part);
+  with_flag(is_bf16, [&](auto bf) {
+    hipLaunchKernelGGL(grad_sumsq_multi_kernel<decltype(bf)::value>, dim3((unsigned)nchunks), dim3(256), 0,
+                       (hipStream_t)stream, table, part);
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
@@ -253,16 +230,20 @@ int ltx_grad_clip_coef(const double* part, int64_t nparts, float max_norm, void*
   return LTX_OK;
 }
 
+int ltx_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, int64_t step, void* stream) {
+  LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi: bad args");
+  launch_adamw_multi<false, false>(table, nchunks, is_bf16, lr, beta1, beta2, eps, weight_decay, step, nullptr, 0.f,
+                                   stream);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
 int ltx_adamw_multi_clip(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
                          float eps, float weight_decay, int64_t step, const float* coef, void* stream) {
   LTX_CHECK_ARG(table && coef && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_clip: bad args");
-  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
-  if (is_bf16)
-    hipLaunchKernelGGL(adamw_multi_clip_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
-                       table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef);
-  else
-    hipLaunchKernelGGL(adamw_multi_clip_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream,
-                       table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef);
+  launch_adamw_multi<true, false>(table, nchunks, is_bf16, lr, beta1, beta2, eps, weight_decay, step, coef, 0.f,
+                                  stream);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
@@ -272,44 +253,24 @@ int ltx_adamw_multi_ema(const int64_t* table, int64_t nchunks, int is_bf16, floa
                         float one_minus_decay, void* stream) {
   LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_ema: bad args");
   LTX_CHECK_ARG(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "adamw_multi_ema: one_minus_decay outside [0, 1]");
-  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
-  const dim3 grid((unsigned)nchunks), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define LTX_EMA_LAUNCH(BF, CL)                                                                                    \
-  hipLaunchKernelGGL((adamw_multi_ema_kernel<BF, CL>), grid, block, 0, st, table, a.decay, a.w1, beta2, a.w2,     \
-                     a.step_size, a.bc2_sqrt, eps, coef_or_null, one_minus_decay)
-  if (is_bf16) {
-    if (coef_or_null) LTX_EMA_LAUNCH(true, true);
-    else LTX_EMA_LAUNCH(true, false);
-  } else {
-    if (coef_or_null) LTX_EMA_LAUNCH(false, true);
-    else LTX_EMA_LAUNCH(false, false);
-  }
-#undef LTX_EMA_LAUNCH
+  with_flag(coef_or_null != nullptr, [&](auto clip) {
+    launch_adamw_multi<decltype(clip)::value, true>(table, nchunks, is_bf16, lr, beta1, beta2, eps, weight_decay, step,
+                                                    coef_or_null, one_minus_decay, stream);
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
 
 int ltx_ema_load_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream) {
   LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31), "ema_load_multi: bad args");
-  if (is_bf16)
-    hipLaunchKernelGGL((ema_swap_multi_kernel<true, true>), dim3((unsigned)nchunks), dim3(256), 0,
-                       (hipStream_t)stream, table);
-  else
-    hipLaunchKernelGGL((ema_swap_multi_kernel<false, true>), dim3((unsigned)nchunks), dim3(256), 0,
-                       (hipStream_t)stream, table);
+  launch_ema_swap<true>(table, nchunks, is_bf16, stream);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
 
 int ltx_ema_restore_multi(const int64_t* table, int64_t nchunks, int is_bf16, void* stream) {
   LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31), "ema_restore_multi: bad args");
-  if (is_bf16)
-    hipLaunchKernelGGL((ema_swap_multi_kernel<true, false>), dim3((unsigned)nchunks), dim3(256), 0,
-                       (hipStream_t)stream, table);
-  else
-    hipLaunchKernelGGL((ema_swap_multi_kernel<false, false>), dim3((unsigned)nchunks), dim3(256), 0,
-                       (hipStream_t)stream, table);
+  launch_ema_swap<false>(table, nchunks, is_bf16, stream);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
@@ -323,18 +284,12 @@ int ltx_adamw_multi_sr(const int64_t* table, int64_t nchunks, float lr, float be
   const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
   const AdamWSr c = {a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, 1.0f, ema ? one_minus_decay : 0.f,
                      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)((uint64_t)step & 0xffffffffu)};
-  const dim3 grid((unsigned)nchunks), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define LTX_SR_LAUNCH(CL, EM) \
-  hipLaunchKernelGGL((adamw_multi_sr_kernel<CL, EM>), grid, block, 0, st, table, c, coef_or_null)
-  if (coef_or_null) {
-    if (ema) LTX_SR_LAUNCH(true, true);
-    else LTX_SR_LAUNCH(true, false);
-  } else {
-    if (ema) LTX_SR_LAUNCH(false, true);
-    else LTX_SR_LAUNCH(false, false);
-  }
-#undef LTX_SR_LAUNCH
+  with_flag(coef_or_null != nullptr, [&](auto clip) {
+    with_flag(ema, [&](auto em) {
+      hipLaunchKernelGGL((adamw_multi_sr_kernel<decltype(clip)::value, decltype(em)::value>), dim3((unsigned)nchunks),
+                         dim3(256), 0, (hipStream_t)stream, table, c, coef_or_null);
+    });
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

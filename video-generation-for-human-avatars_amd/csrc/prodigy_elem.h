@@ -45,17 +45,17 @@ struct ProdigyMoments {
   float a2;          // (float)(d d (1 - beta2))
   float a3;          // (float)((d / d0) (safeguard_warmup ? d : dlr))
   float wd;          // (float)weight_decay of the coupled form (COUPLED only)
-  float coef;        // the clip coefficient (CLIP only)
+  float coef;        // the clip coefficient, applied by the caller in the gradient's dtype
 };
 
-// One element of pass 1, all with the step's old d. g is the gradient as loaded; m, v, s are updated in
-// place; num and den are the element's terms of the two sums, R(p0 - p) * g as an f32 product and the
-// stored |s|.
-template <bool BF16, bool CLIP, bool COUPLED>
+// One element of pass 1, all with the step's old d. g is the gradient as loaded (under the clip, scaled
+// and rounded to its dtype); m, v, s are updated in place; num and den are the element's terms of the two
+// sums, R(p0 - p) * g as an f32 product and the stored |s|. BF16: the dtype of the state, whose arithmetic
+// this is.
+template <bool BF16, bool COUPLED>
 __device__ __forceinline__ void prodigy_moments_elem(float p, float g, float p0, float& m, float& v, float& s,
                                                      const ProdigyMoments& c, float& num, float& den) {
   auto R = [](float x) { return BF16 ? rbf(x) : x; };
-  if (CLIP) g = R(g * c.coef);
   if (COUPLED) g = R(fmaf(c.wd, p, g));
   num = R(p0 - p) * g;
   m = R(fmaf(c.a1, g, R(m * c.b1)));
@@ -69,20 +69,16 @@ struct ProdigyApply {
   float deps;   // (float)(d_new eps)
   float decay;  // (float)(-weight_decay dlr) of the decoupled form (DECAY only)
   float step;   // (float)(-dlr)
-  float omd;    // (float)(1 - EMA decay) (EMA only)
+  float omd;    // (float)(1 - EMA decay) of the caller's shadow update (adamw_elem.h ema_update)
 };
 
-// One element of pass 2: returns the new parameter; with EMA the f32 shadow follows the value stored,
-// shadow - omd (shadow - p') as three separately rounded operations (adamw_elem's EMA).
-template <bool BF16, bool DECAY, bool EMA>
-__device__ __forceinline__ float prodigy_apply_elem(float p, float m, float v, const ProdigyApply& c,
-                                                    float& shadow) {
+// One element of pass 2: returns the new parameter, before the store
+template <bool BF16, bool DECAY>
+__device__ __forceinline__ float prodigy_apply_elem(float p, float m, float v, const ProdigyApply& c) {
   auto R = [](float x) { return BF16 ? rbf(x) : x; };
   const float den = R(R(sqrtf(v)) + c.deps);
   if (DECAY) p = R(fmaf(c.decay, p, p));
-  p = R(fmaf(c.step, m / den, p));
-  if (EMA) shadow = __fsub_rn(shadow, __fmul_rn(c.omd, __fsub_rn(shadow, p)));
-  return p;
+  return R(fmaf(c.step, m / den, p));
 }
 
 }  // namespace ltx

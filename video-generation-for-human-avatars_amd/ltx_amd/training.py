@@ -13,6 +13,7 @@ Differences that are deliberate and documented:
     quantile clamp takes the bounds as 0-dim device tensors instead of `float(t_low)`, which gives
     the same f32 result without the device->host round trip in every micro-step.
 """
+import collections
 import contextlib
 import ctypes
 import functools
@@ -312,6 +313,59 @@ def stochastic_round_bf16(x_f32, seed, ordinal, step, r=None):
     return bits
 
 
+# ---- the chunk tables of the optimizer step -----------------------------------------------------
+# Every table kernel of FusedAdamW / FusedProdigy walks int64 rows, one block per row of at most CHUNK
+# elements of one tensor. The five layouts (`start`, `count`: chunk_rows' two fields; 0: a zero):
+LAYOUTS = {
+    "adamw": ("param", "grad", "exp_avg", "exp_avg_sq", "start", "count"),  # also what the norm pass reads
+    "ema": ("param", "grad", "exp_avg", "exp_avg_sq", "start", "count", "ema", 0),
+    "sr": ("param", "grad", "exp_avg", "exp_avg_sq", "start", "count", "ema or 0", "ordinal"),
+    "swap": ("param", 0, 0, 0, "start", "count", "ema", "stash"),
+    "prodigy": ("param", "grad", "exp_avg", "exp_avg_sq", "start", "count", "s", "p0", "ema or 0", "ordinal or 0"),
+}
+
+
+def chunk_rows(tensors, chunk):
+    """The rows of a chunk table: for every (numel, head fields, tail fields) of `tensors`, in order, one
+    row head + (start, count) + tail per `chunk` elements, count = min(chunk, numel - start). Pure: needs
+    no device."""
+    return [tuple(head) + (start, min(chunk, numel - start)) + tuple(tail)
+            for numel, head, tail in tensors for start in range(0, numel, chunk)]
+
+
+def tensor_fields(layout, items, ema=False, ordinals=None):
+    """Per tensor of `items` the flat tuple (numel, the four fields in front of start, the fields behind
+    count) of LAYOUTS[layout], pointers as integers: what a table is cached on and built from. `items`
+    are (parameter, gradient, state) -- for "swap" (parameter, shadow, stash); `ema`: the shadow column
+    of "sr" / "prodigy" is in use; `ordinals`: parameter -> ordinal (None: 0)."""
+    if layout == "swap":
+        return tuple([(p.numel(), p.data_ptr(), 0, 0, 0, s.data_ptr(), t.data_ptr()) for p, s, t in items])
+    if layout == "adamw":
+        return tuple([(p.numel(), p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr())
+                      for p, g, st in items])
+    if layout == "ema":
+        return tuple([(p.numel(), p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                       st["ema"].data_ptr(), 0) for p, g, st in items])
+    if layout == "sr":
+        return tuple([(p.numel(), p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                       st["ema"].data_ptr() if ema else 0, ordinals[p]) for p, g, st in items])
+    assert layout == "prodigy", layout
+    return tuple([(p.numel(), p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                   st["s"].data_ptr(), st["p0"].data_ptr(), st["ema"].data_ptr() if ema else 0,
+                   0 if ordinals is None else ordinals[p]) for p, g, st in items])
+
+
+def table_rows(fields, chunk):
+    """chunk_rows of tensor_fields' flat tuples"""
+    return chunk_rows([(t[0], t[1:5], t[5:]) for t in fields], chunk)
+
+
+# One launch of the table step: the bucket's device table and its rows, 0 f32 / 1 bf16 / 2 bf16 with f32
+# state and the stochastic store, the param group, the bucket's step count (None where the kernels take
+# none) and the 6-field table of the norm pass (None when nothing is clipped)
+_Launch = collections.namedtuple("_Launch", "table nrows mode group step norm_table")
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW (defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2; the
     reference constructs AdamW(trainable, lr) at training.py:270-271) with one ltx_adamw_step
@@ -364,8 +418,8 @@ class FusedAdamW(torch.optim.Optimizer):
             defaults.update(bf16_update=self.bf16_update, sr_seed=self.sr_seed)
         super().__init__(params, defaults)
         self.multi_tensor = multi_tensor
-        self._tables = []  # pinned host tables of the last builds (alive until their H2D lands)
-        self._table_cache = {}  # dtype -> (buffer pointers, device table, rows)
+        self._tables = []  # pinned host tables of the last two builds (alive until their H2D lands)
+        self._table_cache = {}  # (layout, slot) -> (tensor_fields, device table, rows, pinned host table)
         self._clip_part = None  # f64 per-row partial sums of the norm pass
         # the last clipped step's device record: f64 sum of squares, f32 pre-clip norm, f32 coefficient
         self.clip_sumsq = self.grad_norm = self.clip_coef = None
@@ -385,13 +439,178 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError(f"max_grad_norm must be >= 0, got {v}")
         return v
 
+    # What a subclass states: the chunk-table layout of its step (None: AdamW's, by mode), the state key it
+    # creates last, whether a nearest-mode bucket is split by step count (its kernels take the step), and
+    # whether a step that finds no gradient still counts as an EMA step.
+    _LAYOUT = None
+    _LAST_STATE_KEY = "exp_avg_sq"
+    _BUCKET_BY_STEP = True
+    _EMPTY_STEP_TICKS = True
+
     @torch.no_grad()
     def step(self, closure=None):
+        """The table step of both optimizers: guard, collect and validate, bucket by (param group, dtype or
+        "sr", step) with the state created on the way, tables, the clip's launches when max_grad_norm is
+        set, the EMA tick, the optimizer's own launches (_launch), bump_weight_generation."""
         if self._ema_swapped is not None:
-            raise RuntimeError("FusedAdamW.step() while the EMA weights are swapped in: call ema_swap_out() first")
+            raise RuntimeError(f"{type(self).__name__}.step() while the EMA weights are swapped in: call "
+                               f"ema_swap_out() first")
         max_norm = self._max_grad_norm()
+        if self._step_without_tables(max_norm):
+            return
+        device = self._check_params(*self._names(max_norm))
+        ema, sr = self.ema, self.bf16_update == "stochastic"
+        ordinals = self._ordinals() if sr else None
+        last_key, by_step = self._LAST_STATE_KEY, self._BUCKET_BY_STEP
+        launches = []
+        for gi, group in enumerate(self.param_groups):
+            buckets = {}  # (dtype or "sr", step) or, where the kernels take no step, dtype -> items, in order
+            for p in group["params"]:
+                g = p.grad
+                if g is None or p.numel() == 0:
+                    continue
+                st = self.state[p]
+                kind = p.dtype
+                mixed = sr and kind is torch.bfloat16
+                if mixed:
+                    self._mixed_state(g, st)
+                    kind = "sr"
+                if last_key not in st or (ema is not None and "ema" not in st):
+                    self._make_state(p, st, mixed)
+                st["step"] += 1
+                # the step count is part of a mixed bucket's rounding counter
+                key = (kind, st["step"]) if (by_step or mixed) else kind
+                buckets.setdefault(key, []).append((p, g.contiguous(), st))
+            seen = {}
+            for key, items in buckets.items():
+                kind, step = key if type(key) is tuple else (key, None)
+                j = seen[kind] = seen.get(kind, -1) + 1
+                layout = self._LAYOUT or ("sr" if kind == "sr" else "adamw" if ema is None else "ema")
+                # slot (kind, 0, 0) is also the unclipped fast path's: the usual case (one group, one step
+                # count) switches between the two without a rebuild
+                dev, nrows = self._items_table(layout, (kind, gi, j), items, ordinals)
+                # the norm kernel walks 6-field rows and reads the gradient, first element and count only
+                norm = dev if layout == "adamw" else None
+                if max_norm > 0 and norm is None:
+                    norm = self._items_table("adamw", (kind, gi, j), items)[0]
+                launches.append(_Launch(dev, nrows, 2 if kind == "sr" else 1 if kind is torch.bfloat16 else 0, group,
+                                        step, norm))
+        if launches:
+            self._ready(device)
+        omd = self._ema_tick() if (launches or self._EMPTY_STEP_TICKS) else None
+        if not launches:
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            return
+        stream = ops._s()
+        coef = self._clip_pass(launches, max_norm, device, stream)
+        self._launch(launches, coef, omd, device, stream)
+        ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
+
+    def _names(self, max_norm):
+        """(what, kernels, sums) of _check_params' messages"""
+        if max_norm > 0:
+            return "FusedAdamW(max_grad_norm)", "clip kernels", "the global norm"
+        if self.ema is not None:
+            return "FusedAdamW(ema)", "EMA kernels", "the global norm"
+        return "FusedAdamW(bf16_update)", "stochastic-rounding kernels", "the global norm"
+
+    def _check_params(self, what, kernels, sums=None):
+        """Every parameter with a gradient is an f32 or bf16 ROCm device tensor, all on one device, which is
+        returned. `sums` None (the swap): every parameter with a shadow instead, on any devices."""
+        from . import _lib
+        swap, device = sums is None, None
+        for group in self.param_groups:
+            for p in group["params"]:
+                if ("ema" not in self.state.get(p, ())) if swap else (p.grad is None):
+                    continue
+                if not p.is_cuda:
+                    raise _lib.LtxHipError(f"{what}: the {kernels} need ROCm device parameters, got one on {p.device}")
+                if p.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError(f"{what}: expected f32 or bf16 parameters, got {p.dtype}")
+                if device is None:
+                    device = p.device
+                elif p.device != device and not swap:
+                    raise ValueError(f"{what}: parameters on {device} and {p.device}; the table kernels (and "
+                                     f"{sums}) run on one device")
+        return device
+
+    def _make_state(self, p, st, mixed):
+        """The lazy state of a parameter's first step (or what a restore left out): the moments in the
+        parameter's dtype, f32 for a mixed step; the subclass's own (_extra_state); with the EMA the f32
+        shadow, the value before the step."""
+        if not st:
+            mdtype = torch.float32 if mixed else p.dtype
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, dtype=mdtype)
+            st["exp_avg_sq"] = torch.zeros_like(p, dtype=mdtype)
+        self._extra_state(p, st, mixed)
+        if self.ema is not None and "ema" not in st:
+            # with the moments; later only where a restore brought moments without shadows
+            st["ema"] = p.detach().float().clone()
+
+    def _extra_state(self, p, st, mixed):
+        pass
+
+    def _ready(self, device):
+        """Before the first launch of a step that has something to step."""
+
+    def _ema_tick(self):
+        """Count an EMA step; returns 1 - decay in double (the entry points take it as one f32), None
+        without an EMA."""
+        if self.ema is None:
+            return None
+        self.ema_steps += 1
+        self.ema_decay = self.ema.decay_at(self.ema_steps)
+        return 1.0 - self.ema_decay
+
+    def _clip_pass(self, launches, max_norm, device, stream):
+        """With max_norm > 0 the norm launches of all buckets (each writes its per-row partials behind the
+        previous bucket's) and the coefficient launch; sets clip_sumsq / grad_norm / clip_coef and returns
+        the coefficient's pointer. Otherwise clears the three and returns None."""
+        if not max_norm > 0:
+            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            return None
+        total = sum(l.nrows for l in launches)
+        if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
+            self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
+        part = self._clip_part
+        # the record {f64 sumsq, f32 norm, f32 coef}: a fresh one per step, so a norm somebody holds keeps
+        # its value
+        rec = torch.empty(2, dtype=torch.float64, device=device)
+        tail = rec[1:].view(torch.float32)
+        off = 0
+        for _, nrows, mode, _, _, norm_table in launches:
+            ops.call("ltx_grad_sumsq_multi", ops._p(norm_table), nrows, 1 if mode else 0,
+                     ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
+            off += nrows
+        ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
+        self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
+        return ops._p(tail[1])
+
+    def _launch(self, launches, coef, omd, device, stream):
+        """One AdamW launch per bucket: ltx_adamw_multi_clip, with the EMA ltx_adamw_multi_ema (given the
+        coefficient when clipping), for a mixed bucket ltx_adamw_multi_sr (the coefficient and the shadow
+        as arguments), and for an f32 bucket of the stochastic mode without clip or EMA ltx_adamw_multi."""
+        ema = self.ema is not None
+        for table, nrows, mode, group, step, _ in launches:
+            b1, b2 = group["betas"]
+            hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                     int(step))
+            if mode == 2:
+                ops.call("ltx_adamw_multi_sr", ops._p(table), nrows, *hyper, coef, 1 if ema else 0,
+                         0.0 if omd is None else omd, self.sr_seed, stream)
+            elif ema:
+                ops.call("ltx_adamw_multi_ema", ops._p(table), nrows, mode, *hyper, coef, omd, stream)
+            elif coef is not None:
+                ops.call("ltx_adamw_multi_clip", ops._p(table), nrows, mode, *hyper, coef, stream)
+            else:
+                ops.call("ltx_adamw_multi", ops._p(table), nrows, mode, *hyper, stream)
+
+    def _step_without_tables(self, max_norm):
+        """The unclipped, EMA-less, nearest step: ltx_adamw_multi per dtype group of more than one tensor,
+        ltx_adamw_step otherwise, CPU parameters included. False when the step needs the table path."""
         if max_norm > 0 or self.ema is not None or self.bf16_update == "stochastic":
-            return self._step_tables(max_norm)
+            return False
         for group in self.param_groups:
             b1, b2 = group["betas"]
             todo = []
@@ -417,38 +636,37 @@ class FusedAdamW(torch.optim.Optimizer):
                     ops.adamw_step(p, g, st["exp_avg"], st["exp_avg_sq"], group["lr"], b1, b2,
                                    group["eps"], group["weight_decay"], st["step"])
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
+        return True
 
-    def _table(self, items, dtype, slot=None, ema=False):
-        """(device chunk table, rows) of `items`: int64 rows of (param, grad, exp_avg, exp_avg_sq,
-        first element, count <= CHUNK). The table (~10^4 rows at LTX-2B: milliseconds of host time)
-        is built once per set of buffers and reused while the parameter / grad / state storages
-        stay the same; `slot` is the cache entry (the dtype, for the one group the LoRA path has).
-        `ema`: the 8-field rows of the EMA entry points, (..., shadow = st["ema"], stash = 0), in a
-        cache entry of their own whose key holds the shadow pointers too."""
-        slot = dtype if slot is None else slot
-        if ema:
-            slot = ("ema", slot)
-            ptrs = [(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                     p.numel(), st["ema"].data_ptr()) for p, g, st in items]
-        else:
-            ptrs = [(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                     p.numel()) for p, g, st in items]
-        key = (dtype, tuple(ptrs))
+    def _multi(self, items, dtype, group, b1, b2, step):
+        """One ltx_adamw_multi launch for all tensors of a dtype (bitwise the per-tensor math)."""
+        dev, nrows = self._items_table("adamw", (dtype, 0, 0), items)
+        ops.call("ltx_adamw_multi", ops._p(dev), nrows, 1 if dtype == torch.bfloat16 else 0,
+                 float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                 float(group["weight_decay"]), int(step), ops._s())
+
+    def _items_table(self, layout, slot, items, ordinals=None):
+        """(device chunk table, rows) of `items` in LAYOUTS[layout] (tensor_fields' items), cached in the
+        entry (layout, slot)."""
+        fields = tensor_fields(layout, items, self.ema is not None, ordinals)
+        return self._chunk_table((layout, slot), fields, items)
+
+    def _chunk_table(self, slot, fields, items):
+        """(device table, rows) of the tensors `fields` (tensor_fields' tuples of `items`, on whose first
+        tensor's device the table goes). A table (~10^4 rows at
+        LTX-2B: milliseconds of host time) is built once per set of buffers and reused while the cache
+        entry `slot` holds the same fields, that is while the parameter / gradient / state storages stay
+        the same. The pinned host copy stays alive until its H2D copy has landed: the cache entry holds
+        it, and so do the last two builds, for an entry that is rebuilt at once."""
         hit = self._table_cache.get(slot)
-        if hit is not None and hit[0] == key:
+        if hit is not None and hit[0] == fields:
             return hit[1], hit[2]
-        rows = []
-        for pp, gp, ap, sp, n, *shadow in ptrs:
-            for start in range(0, n, self.CHUNK):
-                rows.append((pp, gp, ap, sp, start, min(self.CHUNK, n - start)) + ((shadow[0], 0) if ema else ()))
+        rows = table_rows(fields, self.CHUNK)
         host = torch.tensor(rows, dtype=torch.int64).pin_memory()
         dev = host.to(items[0][0].device, non_blocking=True)
-        nrows = len(rows)
-        # the pinned host copy stays alive until its H2D has landed (two steps later, and while
-        # the cache entry holds it)
         self._tables = (self._tables + [(host, dev)])[-2:]
-        self._table_cache[slot] = (key, dev, nrows, host)
-        return dev, nrows
+        self._table_cache[slot] = (fields, dev, len(rows), host)
+        return dev, len(rows)
 
     def _ordinals(self):
         """parameter -> its index in the concatenation of param_groups[*]["params"] (torch's state_dict
@@ -459,148 +677,14 @@ class FusedAdamW(torch.optim.Optimizer):
                 out[p] = len(out)
         return out
 
-    def _mixed_state(self, p, st):
+    def _mixed_state(self, grad, st):
         """The checks of a bf16 parameter's stochastic step: a bf16 gradient, f32 moments."""
-        if p.grad.dtype != torch.bfloat16:
+        if grad.dtype != torch.bfloat16:
             raise TypeError(f"{type(self).__name__}(bf16_update='stochastic'): a bf16 parameter's gradient must "
-                            f"be bf16, got {p.grad.dtype}")
+                            f"be bf16, got {grad.dtype}")
         if st and st["exp_avg"].dtype != torch.float32:
             raise ValueError(f"{type(self).__name__}(bf16_update='stochastic'): a bf16 parameter's moments are "
                              f"{st['exp_avg'].dtype}, from a run in nearest mode; they are not converted")
-
-    def _sr_table(self, items, slot, ordinals, ema):
-        """(device table, rows) of the stochastic step's 8-field rows (param, grad, exp_avg, exp_avg_sq,
-        first element, count <= CHUNK, shadow or 0, ordinal), cached like _table's."""
-        ptrs = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
-                      st["ema"].data_ptr() if ema else 0, ordinals[p]) for p, g, st in items)
-        hit = self._table_cache.get(slot)
-        if hit is not None and hit[0] == ptrs:
-            return hit[1], hit[2]
-        rows = [(pp, gp, ap, sp, start, min(self.CHUNK, n - start), ep, o)
-                for pp, gp, ap, sp, n, ep, o in ptrs for start in range(0, n, self.CHUNK)]
-        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-        dev = host.to(items[0][0].device, non_blocking=True)
-        self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
-        return dev, len(rows)
-
-    def _multi(self, items, dtype, group, b1, b2, step):
-        """One ltx_adamw_multi launch for all tensors of a dtype (bitwise the per-tensor math)."""
-        dev, nrows = self._table(items, dtype)
-        ops.call("ltx_adamw_multi", ops._p(dev), nrows, 1 if dtype == torch.bfloat16 else 0,
-                 float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                 float(group["weight_decay"]), int(step), ops._s())
-
-    def _step_tables(self, max_norm):
-        """The step under global-norm clipping (max_norm > 0) and / or with the EMA: every parameter
-        with a gradient goes through the table kernels, grouped by (param group, dtype, step). Launch
-        order: when clipping, the norm launches of all groups (each writes its per-row partials behind
-        the previous group's) and the coefficient launch; then one AdamW launch per group --
-        ltx_adamw_multi_clip, or with the EMA ltx_adamw_multi_ema (given the coefficient when clipping).
-        With bf16_update="stochastic" every step comes here: a group's bf16 parameters form buckets of
-        their own, stepped by ltx_adamw_multi_sr (the coefficient and the shadow as arguments), and an
-        f32 bucket without clip or EMA by ltx_adamw_multi."""
-        from . import _lib
-        ema = self.ema
-        sr = self.bf16_update == "stochastic"
-        what = ("FusedAdamW(max_grad_norm)" if max_norm > 0 else "FusedAdamW(ema)" if ema is not None
-                else "FusedAdamW(bf16_update)")
-        kernels = ("clip kernels" if max_norm > 0 else "EMA kernels" if ema is not None
-                   else "stochastic-rounding kernels")
-        todo, device = [], None
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda:
-                    raise _lib.LtxHipError(f"{what}: the {kernels} need ROCm device "
-                                           f"parameters, got one on {p.device}")
-                if p.dtype not in (torch.float32, torch.bfloat16):
-                    raise TypeError(f"{what}: expected f32 or bf16 parameters, got {p.dtype}")
-                if device is None:
-                    device = p.device
-                elif p.device != device:
-                    raise ValueError(f"{what}: parameters on {device} and {p.device}; the table kernels "
-                                     f"(and the global norm) run on one device")
-        ordinals = self._ordinals() if sr else None
-        # (device table, rows, 0 f32 / 1 bf16 / 2 bf16 with f32 moments and the stochastic store, group, step,
-        # the 6-field table of the norm pass)
-        launches = []
-        for gi, group in enumerate(self.param_groups):
-            buckets = {}  # (dtype or "sr", step) -> items, in order of first appearance
-            for p in group["params"]:
-                if p.grad is None or p.numel() == 0:
-                    continue
-                st = self.state[p]
-                mixed = sr and p.dtype == torch.bfloat16
-                if mixed:
-                    self._mixed_state(p, st)
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32 if mixed else p.dtype)
-                    st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32 if mixed else p.dtype)
-                if ema is not None and "ema" not in st:
-                    # with the moments; later only where a restore brought moments without shadows
-                    st["ema"] = p.detach().float().clone()
-                st["step"] += 1
-                buckets.setdefault(("sr" if mixed else p.dtype, st["step"]), []).append((p, p.grad.contiguous(), st))
-            seen = {}
-            for (dtype, step), items in buckets.items():
-                j = seen[dtype] = seen.get(dtype, -1) + 1
-                if dtype == "sr":
-                    dev, nrows = self._sr_table(items, ("sr", gi, j), ordinals, ema is not None)
-                    # the norm kernel reads a 6-field row's gradient, first element and count only
-                    norm_dev = self._table(items, torch.bfloat16, ("sr_norm", gi, j))[0] if max_norm > 0 else dev
-                    launches.append((dev, nrows, 2, group, step, norm_dev))
-                    continue
-                # the unclipped step's cache entry for the usual case: one group, one step count
-                slot = dtype if (gi, j) == (0, 0) else (dtype, gi, j)
-                dev, nrows = self._table(items, dtype, slot, ema=ema is not None)
-                # the norm kernel walks 6-field rows: with the EMA's 8-field table the clip keeps its own
-                norm_dev = self._table(items, dtype, slot)[0] if (ema is not None and max_norm > 0) else dev
-                launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, group, step, norm_dev))
-        omd = None
-        if ema is not None:
-            self.ema_steps += 1
-            self.ema_decay = ema.decay_at(self.ema_steps)
-            omd = 1.0 - self.ema_decay  # in double; the entry point takes it as one f32
-        if not launches:
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
-            return
-        stream = ops._s()
-        coef = None
-        if max_norm > 0:
-            total = sum(n for _, n, _, _, _, _ in launches)
-            if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
-                self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
-            part = self._clip_part
-            # the record {f64 sumsq, f32 norm, f32 coef}: a fresh one per step, so a norm somebody
-            # holds keeps its value
-            rec = torch.empty(2, dtype=torch.float64, device=device)
-            tail = rec[1:].view(torch.float32)
-            off = 0
-            for _, nrows, mode, _, _, dev in launches:
-                ops.call("ltx_grad_sumsq_multi", ops._p(dev), nrows, 1 if mode else 0,
-                         ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
-                off += nrows
-            ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
-            coef = ops._p(tail[1])
-            self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
-        else:
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
-        for dev, nrows, mode, group, step, _ in launches:
-            b1, b2 = group["betas"]
-            hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                     int(step))
-            if mode == 2:
-                ops.call("ltx_adamw_multi_sr", ops._p(dev), nrows, *hyper, coef, 1 if ema is not None else 0,
-                         0.0 if omd is None else omd, self.sr_seed, stream)
-            elif ema is not None:
-                ops.call("ltx_adamw_multi_ema", ops._p(dev), nrows, mode, *hyper, coef, omd, stream)
-            elif coef is not None:
-                ops.call("ltx_adamw_multi_clip", ops._p(dev), nrows, mode, *hyper, coef, stream)
-            else:  # an f32 bucket of the stochastic mode without clip or EMA
-                ops.call("ltx_adamw_multi", ops._p(dev), nrows, mode, *hyper, stream)
-        ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
     # ---- the averaged weights as the model's weights ---------------------------------------
     def _swap_tables(self):
@@ -617,38 +701,19 @@ class FusedAdamW(torch.optim.Optimizer):
                 if stash is None or stash.shape != p.shape or stash.dtype != p.dtype or stash.device != p.device:
                     stash = self._ema_stash[p] = torch.empty_like(p)
                 by_dtype.setdefault(p.dtype, []).append((p, st["ema"], stash))
-        out = []
-        for dtype, items in by_dtype.items():
-            ptrs = tuple((p.data_ptr(), s.data_ptr(), t.data_ptr(), p.numel()) for p, s, t in items)
-            slot = ("ema_swap", dtype)
-            hit = self._table_cache.get(slot)
-            if hit is None or hit[0] != ptrs:
-                rows = [(pp, 0, 0, 0, start, min(self.CHUNK, n - start), sp, tp)
-                        for pp, sp, tp, n in ptrs for start in range(0, n, self.CHUNK)]
-                host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-                dev = host.to(items[0][0].device, non_blocking=True)
-                hit = self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
-            out.append((hit[1], hit[2], 1 if dtype == torch.bfloat16 else 0))
-        return out
+        return [self._items_table("swap", dtype, items) + (1 if dtype == torch.bfloat16 else 0,)
+                for dtype, items in by_dtype.items()]
 
     @torch.no_grad()
     def ema_swap_in(self):
         """Stash the live value of every parameter that has a shadow and install the shadow in its
         place, rounded to the parameter's dtype (ltx_ema_load_multi, one launch per dtype); the
         weight-derived caches are invalidated. RuntimeError without an EMA or while swapped in."""
-        from . import _lib
         if self.ema is None:
             raise RuntimeError("FusedAdamW.ema_swap_in(): this optimizer keeps no EMA (ema=None)")
         if self._ema_swapped is not None:
             raise RuntimeError("FusedAdamW.ema_swap_in(): the EMA weights are swapped in already")
-        for group in self.param_groups:
-            for p in group["params"]:
-                if "ema" in self.state.get(p, ()):
-                    if not p.is_cuda:
-                        raise _lib.LtxHipError(f"FusedAdamW(ema): the EMA kernels need ROCm device parameters, "
-                                               f"got one on {p.device}")
-                    if p.dtype not in (torch.float32, torch.bfloat16):
-                        raise TypeError(f"FusedAdamW(ema): expected f32 or bf16 parameters, got {p.dtype}")
+        self._check_params("FusedAdamW(ema)", "EMA kernels")
         launches = self._swap_tables()
         stream = ops._s()
         for dev, nrows, is_bf16 in launches:
@@ -778,140 +843,64 @@ class FusedProdigy(FusedAdamW):
         """The step-size estimate: a 0-dim float64 view of the device record (float() syncs)."""
         return self.ensure_record()[0]
 
-    def _prodigy_table(self, items, dtype, slot=None, ordinals=None):
-        """(device table, rows) of ROW-field rows (param, grad, exp_avg, exp_avg_sq, first element, count,
-        s, p0, shadow or 0, 0 -- or, with `ordinals` for the stochastic step, the parameter's ordinal),
-        cached on the buffers' pointers like FusedAdamW._table."""
-        ptrs = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
-                      st["s"].data_ptr(), st["p0"].data_ptr(), st["ema"].data_ptr() if self.ema is not None else 0,
-                      0 if ordinals is None else ordinals[p])
-                     for p, g, st in items)
-        slot = ("prodigy", dtype) if slot is None else slot
-        hit = self._table_cache.get(slot)
-        if hit is not None and hit[0] == ptrs:
-            return hit[1], hit[2]
-        rows = [(pp, gp, ap, vp, start, min(self.CHUNK, n - start), sp, p0p, ep, o)
-                for pp, gp, ap, vp, n, sp, p0p, ep, o in ptrs for start in range(0, n, self.CHUNK)]
-        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-        dev = host.to(items[0][0].device, non_blocking=True)
-        self._table_cache[slot] = (ptrs, dev, len(rows), host)  # host: alive with the entry
-        return dev, len(rows)
+    _LAYOUT = "prodigy"
+    _LAST_STATE_KEY = "s"
+    _BUCKET_BY_STEP = False  # the nearest-mode kernels take no step count: one bucket per dtype
+    _EMPTY_STEP_TICKS = False  # a step without a gradient changes nothing
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        from . import _lib
-        if self._ema_swapped is not None:
-            raise RuntimeError("FusedProdigy.step() while the EMA weights are swapped in: call ema_swap_out() first")
-        group = self._one_group()
-        max_norm = self._max_grad_norm()
-        lr = float(group["lr"])
-        if lr == 0.0:
+    def _max_grad_norm(self):
+        self._one_group()
+        return super()._max_grad_norm()
+
+    def _names(self, max_norm):
+        return "FusedProdigy", "Prodigy kernels", "the sums behind d"
+
+    def _step_without_tables(self, max_norm):
+        if float(self.param_groups[0]["lr"]) == 0.0:
             # the published code returns before any state moves; nothing is launched
             self.clip_sumsq = self.grad_norm = self.clip_coef = None
-            return
-        ema = self.ema
-        device = None
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            if not p.is_cuda:
-                raise _lib.LtxHipError(f"FusedProdigy: the Prodigy kernels need ROCm device parameters, got one "
-                                       f"on {p.device}")
-            if p.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"FusedProdigy: expected f32 or bf16 parameters, got {p.dtype}")
-            if device is None:
-                device = p.device
-            elif p.device != device:
-                raise ValueError(f"FusedProdigy: parameters on {device} and {p.device}; the table kernels (and "
-                                 f"the sums behind d) run on one device")
-        sr = self.bf16_update == "stochastic"
-        ordinals = self._ordinals() if sr else None
-        # dtype -> items, in order of first appearance; the stochastic step's bf16 parameters under
-        # ("sr", step): the step count is part of their rounding's counter
-        buckets = {}
-        for p in group["params"]:
-            if p.grad is None or p.numel() == 0:
-                continue
-            st = self.state[p]
-            mixed = sr and p.dtype == torch.bfloat16
-            if mixed:
-                self._mixed_state(p, st)
-            mdtype = torch.float32 if mixed else p.dtype
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, dtype=mdtype)
-                st["exp_avg_sq"] = torch.zeros_like(p, dtype=mdtype)
-            if "s" not in st:  # with the moments, before anything moves
-                st["s"] = torch.zeros_like(p, dtype=mdtype)
-                st["p0"] = p.detach().clone()
-            if ema is not None and "ema" not in st:
-                st["ema"] = p.detach().float().clone()
-            st["step"] += 1
-            buckets.setdefault(("sr", st["step"]) if mixed else p.dtype, []).append((p, p.grad.contiguous(), st))
-        if not buckets:
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
-            return
+            return True
+        return False
+
+    def _extra_state(self, p, st, mixed):
+        if "s" not in st:  # with the moments, before anything moves
+            st["s"] = torch.zeros_like(p, dtype=torch.float32 if mixed else p.dtype)
+            st["p0"] = p.detach().clone()
+
+    def _ready(self, device):
         rec = self.ensure_record(device)
         if rec.device != device:
             raise ValueError(f"FusedProdigy: the record is on {rec.device}, the parameters on {device}")
-        # (Prodigy table, rows, 0 f32 / 1 bf16 / 2 the stochastic step's bf16 with f32 state, the 6-field
-        # table of the norm pass or None, the step count of a mode-2 bucket)
-        launches = []
-        for j, (dtype, items) in enumerate(buckets.items()):
-            if isinstance(dtype, tuple):
-                dev, nrows = self._prodigy_table(items, torch.bfloat16, ("prodigy_sr", j), ordinals)
-                norm_dev = self._table(items, torch.bfloat16, ("sr_norm", j))[0] if max_norm > 0 else None
-                launches.append((dev, nrows, 2, norm_dev, dtype[1]))
-                continue
-            dev, nrows = self._prodigy_table(items, dtype)
-            norm_dev = self._table(items, dtype)[0] if max_norm > 0 else None
-            launches.append((dev, nrows, 1 if dtype == torch.bfloat16 else 0, norm_dev, None))
-        omd = 0.0
-        if ema is not None:
-            self.ema_steps += 1
-            self.ema_decay = ema.decay_at(self.ema_steps)
-            omd = 1.0 - self.ema_decay  # in double; the entry point takes it as one f32
-        total = sum(n for _, n, _, _, _ in launches)
+
+    def _launch(self, launches, coef, omd, device, stream):
+        """Pass 1 per bucket (each writes its (num, den) partials behind the previous bucket's), the d
+        update, pass 2 per bucket -- ltx_prodigy_apply_multi_sr for a mixed bucket."""
+        group, rec = launches[0].group, self.record
+        ema, omd = 1 if self.ema is not None else 0, 0.0 if omd is None else omd
+        total = sum(l.nrows for l in launches)
         if self._prodigy_part is None or self._prodigy_part.numel() < 2 * total or self._prodigy_part.device != device:
             self._prodigy_part = torch.empty(2 * total, dtype=torch.float64, device=device)
         part = self._prodigy_part
-        stream = ops._s()
-        coef = None
-        if max_norm > 0:
-            if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
-                self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
-            clip_rec = torch.empty(2, dtype=torch.float64, device=device)  # fresh per step, as FusedAdamW's
-            tail = clip_rec[1:].view(torch.float32)
-            off = 0
-            for _, nrows, mode, norm_dev, _ in launches:
-                ops.call("ltx_grad_sumsq_multi", ops._p(norm_dev), nrows, 1 if mode else 0,
-                         ctypes.c_void_p(self._clip_part.data_ptr() + 8 * off), stream)
-                off += nrows
-            ops.call("ltx_grad_clip_coef", ops._p(self._clip_part), total, float(max_norm), ops._p(clip_rec), stream)
-            self.clip_sumsq, self.grad_norm, self.clip_coef = clip_rec[0], tail[0], tail[1]
-            coef = ops._p(tail[1])
-        else:
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+        lr = float(group["lr"])
         b1, b2 = (float(b) for b in group["betas"])
         b3 = math.sqrt(b2) if group["beta3"] is None else float(group["beta3"])
         d0, wd = float(group["d0"]), float(group["weight_decay"])
         decouple, use_bc = bool(group["decouple"]), int(bool(group["use_bias_correction"]))
         off = 0
-        for dev, nrows, mode, _, _ in launches:
-            ops.call("ltx_prodigy_moments_multi", ops._p(dev), nrows, mode, ops._p(rec), lr, b1, b2, b3, d0,
+        for table, nrows, mode, _, _, _ in launches:
+            ops.call("ltx_prodigy_moments_multi", ops._p(table), nrows, mode, ops._p(rec), lr, b1, b2, b3, d0,
                      0.0 if decouple else wd, use_bc, int(bool(group["safeguard_warmup"])), coef,
                      ctypes.c_void_p(part.data_ptr() + 16 * off), stream)
             off += nrows
         ops.call("ltx_prodigy_d_update", ops._p(part), total, ops._p(rec), lr, b1, b2, b3, d0,
                  float(group["d_coef"]), float(group["growth_rate"]), use_bc, stream)
-        for dev, nrows, mode, _, step in launches:
+        for table, nrows, mode, _, step, _ in launches:
             if mode == 2:
-                ops.call("ltx_prodigy_apply_multi_sr", ops._p(dev), nrows, ops._p(rec), float(group["eps"]),
-                         wd if decouple else 0.0, 1 if ema is not None else 0, omd, self.sr_seed, int(step), stream)
+                ops.call("ltx_prodigy_apply_multi_sr", ops._p(table), nrows, ops._p(rec), float(group["eps"]),
+                         wd if decouple else 0.0, ema, omd, self.sr_seed, int(step), stream)
                 continue
-            ops.call("ltx_prodigy_apply_multi", ops._p(dev), nrows, mode, ops._p(rec), float(group["eps"]),
-                     wd if decouple else 0.0, 1 if ema is not None else 0, omd, stream)
-        ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
+            ops.call("ltx_prodigy_apply_multi", ops._p(table), nrows, mode, ops._p(rec), float(group["eps"]),
+                     wd if decouple else 0.0, ema, omd, stream)
 
 
 OPTIMIZERS = ("adamw", "prodigy")
