@@ -196,8 +196,25 @@ int ltx_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
                  int64_t H, int64_t Nq, int64_t Nk, int64_t kv_batch_rows, int64_t d, float scale,
                  void* stream);
 /* The attention path's LTX_ATTN_* A/B switches are read from the environment once, at the first
- * attention launch; this re-reads them (tests comparing two kernel paths in one process). */
+ * attention launch. A caller of this C API that changes an LTX_ATTN_* variable afterwards MUST call
+ * ltx_attn_reload_switches() for the change to take effect: it re-reads every switch and publishes
+ * the new table under a lock (a launch on another host thread sees the old table or the new one,
+ * never a mixture). ltx_attn_switch_name(i) is the environment name of switch i, NULL past the
+ * last one. */
 int ltx_attn_reload_switches(void);
+const char* ltx_attn_switch_name(int i);
+/* The demangled names (as rocprofv3 prints them, without the argument list) of the kernels
+ * ltx_attn_fwd (backward = 0) or ltx_attn_bwd_ex (backward = 1) would launch for this call on
+ * `stream`, joined by " + ": attn_delta_kernel first when it runs (delta_ready = 0), then the dK/dV
+ * kernel, then the dQ kernel; the finish kernel of the query-split one-pass backward last. Host
+ * only, nothing is launched: the same plan the entry points launch from, so it depends on the
+ * switches last read, the CU count (256 without a device) and the workspace of `stream`. The
+ * strides are those of the entry points (only the persistent backward kernels' limits read them);
+ * the forward ignores dq_is_f32, delta_ready and lddo. Writes a NUL-terminated string of at most
+ * len bytes. */
+int ltx_attn_describe(int backward, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
+                      int has_key_bias, int dq_is_f32, int delta_ready, int64_t ldq, int64_t ldk,
+                      int64_t ldv, int64_t lddo, void* stream, char* buf, int64_t len);
 /* Backward (deterministic, no atomics): delta[b,h,i] = sum_d dO*O (f32, caller workspace
  * [B,H,Nq]); dQ [B,Nq,H,d] (f32 if dq_is_f32 else bf16, row stride lddq), dK/dV bf16. lse as
  * written by ltx_attn_fwd (log2 units). */

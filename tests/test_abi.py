@@ -133,3 +133,155 @@ def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
     assert (np.diff(s1[n0:n0 + n1]) >= 0).all() and s1[n0:n0 + n1].max() >= cap
     bench.dump_outputs(str(tmp_path / "d"), {"x": whole})
     assert np.array_equal(np.load(tmp_path / "d" / "x.npy"), whole)
+
+
+@pytest.fixture
+def attn_switches():
+    """set(**{name without LTX_ATTN_: value}): exactly these switches in the environment, then
+    ltx_attn_reload_switches(). Afterwards the environment is restored and the library reads it
+    again, so later tests find the table their environment describes."""
+    from ltx_amd import _lib, ops
+    lib = _lib.load()
+    with pytest.MonkeyPatch.context() as mp:
+        def set_(**kw):
+            for name in ops._ATTN_ENV:
+                mp.delenv(name, raising=False)
+            for k, v in kw.items():
+                mp.setenv("LTX_ATTN_" + k, str(v))
+            assert lib.ltx_attn_reload_switches() == 0
+        yield set_
+    assert lib.ltx_attn_reload_switches() == 0
+
+
+def test_attn_switch_table_is_the_librarys():
+    """ops._ATTN_ENV (whose changes make ops reload the switches) is the library's own table."""
+    from ltx_amd import _lib, ops
+    lib = _lib.load()
+    names = []
+    while (n := lib.ltx_attn_switch_name(len(names))) is not None:
+        names.append(n.decode())
+    assert lib.ltx_attn_switch_name(-1) is None
+    assert tuple(names) == ops._ATTN_ENV and len(names) == 18 and len(set(names)) == 18
+    assert all(n.startswith("LTX_ATTN_") for n in names)
+
+
+# (switches, (B, H, Nq, Nk), call options, forward kernel or None, backward kernels or None), each
+# "ltx::" + the name; "ws": "big" a 128-MiB workspace on the call's stream, "small" 1 MiB, None none
+_W1P = "attn_dkdv_w1p_kernel<0> + attn_dq_w1p_kernel<0>"
+_SELF, _CROSS, _FEWBH = (2, 3, 1000, 512), (8, 32, 1792, 256), (2, 4, 1792, 256)
+_ATTN_DESCRIBE = [
+    # head dim 32 (the tiny config): the 4-wave tiled kernels, biased when Nk % 64 != 0
+    ({}, (1, 3, 100, 128), dict(d=32), "attn_q_kernel<32, 0, false, 4>",
+     "attn_dkdv_kernel<32, false, 4> + attn_q_kernel<32, 1, false, 4>"),
+    ({}, (1, 3, 100, 77), dict(d=32), "attn_q_kernel<32, 0, true, 4>",
+     "attn_dkdv_kernel<32, true, 4> + attn_q_kernel<32, 1, true, 4>"),
+    ({"W8": 3}, (1, 3, 100, 128), dict(d=32, bias=True), "attn_q_kernel<32, 0, true, 4>",
+     "attn_dkdv_kernel<32, true, 4> + attn_q_kernel<32, 1, true, 4>"),
+    # Nk <= 256: the one-pass kernels; H * B >= 128 is one workgroup per (batch, head)
+    ({}, _CROSS, {}, "attn_fwd1_kernel<64, false, true>", "attn_bwd1_kernel<64, false, false>"),
+    ({}, _CROSS, dict(bias=True), "attn_fwd1_kernel<64, true, true>", "attn_bwd1_kernel<64, true, false>"),
+    ({}, _CROSS, dict(ready=False), None, "attn_delta_kernel<64> + attn_bwd1_kernel<64, false, false>"),
+    ({"FWD1_ROWS": 0}, _CROSS, {}, "attn_fwd1_kernel<64, false, false>", None),
+    ({"FWD1_ROWS": 0}, _CROSS, dict(bias=True), "attn_fwd1_kernel<64, true, false>", None),
+    # H * B < 128 and >= 4 query tiles: split over the queries when the partials fit the workspace
+    ({}, _FEWBH, {}, "attn_fwd1_kernel<64, false, true>",
+     "attn_bwd1_kernel<64, false, false> + attn_bwd1_finish_kernel<64>"),
+    ({}, _FEWBH, dict(bias=True), "attn_fwd1_kernel<64, true, true>",
+     "attn_bwd1_kernel<64, true, false> + attn_bwd1_finish_kernel<64>"),
+    ({}, _FEWBH, dict(ws=None), None, "attn_bwd1_kernel<64, false, false>"),
+    ({}, _FEWBH, dict(ws=None, bias=True), None, "attn_bwd1_kernel<64, true, false>"),
+    ({}, _FEWBH, dict(ws="small"), None, "attn_bwd1_kernel<64, false, false>"),  # S = 14: 14.7 MB
+    ({}, (2, 4, 192, 256), {}, None, "attn_bwd1_kernel<64, false, false>"),      # 3 query tiles
+    ({"QSPLIT": 0}, _FEWBH, {}, None, "attn_bwd1_kernel<64, false, false>"),
+    ({"BWD1_QS": 1}, _CROSS, dict(bias=True), None, "attn_bwd1_kernel<64, true, true>"),
+    ({"BWD1_QS": 1}, _CROSS, {}, None, "attn_bwd1_kernel<64, false, false>"),
+    ({"BWD1_QS": 1}, _FEWBH, dict(bias=True), None,
+     "attn_bwd1_kernel<64, true, false> + attn_bwd1_finish_kernel<64>"),
+    ({"BWD1_QS": 1}, _FEWBH, dict(bias=True, ws=None), None, "attn_bwd1_kernel<64, true, true>"),
+    # ragged Nk = 200 and Nk = 128: biased instantiations without a key bias
+    ({}, (1, 2, 300, 200), dict(ws=None), "attn_fwd1_kernel<64, true, true>", "attn_bwd1_kernel<64, true, false>"),
+    ({}, (8, 32, 1792, 128), {}, "attn_fwd1_kernel<64, false, true>", "attn_bwd1_kernel<64, true, false>"),
+    # the one-pass paths off: the tiled / pipelined kernels at Nk = 256
+    ({"FWD1": 0}, _CROSS, {}, "attn_fwd_pipe_kernel<true>", None),
+    ({"FWD1": 0}, _CROSS, dict(bias=True), "attn_q_kernel<64, 0, true, 8>", None),
+    ({"BWD1": 0}, _CROSS, {}, None, _W1P),
+    ({"BWD1": 0}, _CROSS, dict(bias=True), None, "attn_dkdv_pipe_kernel<true, 4> + attn_q_kernel<64, 1, true, 4>"),
+    ({"BWD1": 0}, (1, 2, 300, 200), {}, None, "attn_dkdv_pipe_kernel<true, 4> + attn_q_kernel<64, 1, true, 4>"),
+    # Nk = 512 without bias: forward pipe; backward pipe / w1 / w1p per LTX_ATTN_{DKDV,DQ}_W1 0 / 1 / 2
+    ({}, _SELF, {}, "attn_fwd_pipe_kernel<true>", _W1P),
+    ({}, _SELF, dict(ready=False), None, "attn_delta_kernel<64> + " + _W1P),
+    ({"FWD_F32SUM": 0}, _SELF, {}, "attn_fwd_pipe_kernel<false>", None),
+    ({"FWD_PIPE": 0}, _SELF, {}, "attn_q_kernel<64, 0, false, 8>", None),
+    ({"FWD_PIPE": 0, "W8": 0}, _SELF, {}, "attn_q_kernel<64, 0, false, 4>", None),
+    ({"FWD_W1": 1}, _SELF, {}, "attn_fwd_pipe_kernel<true>", None),  # not a fwdw1 build
+    ({}, _SELF, dict(bias=True), "attn_q_kernel<64, 0, true, 8>",
+     "attn_dkdv_pipe_kernel<true, 4> + attn_q_kernel<64, 1, true, 4>"),
+    ({"DKDV_W1": 1}, _SELF, {}, None, "attn_dkdv_w1_kernel<0> + attn_dq_w1p_kernel<0>"),
+    ({"DKDV_W1": 0}, _SELF, {}, None, "attn_dkdv_pipe_kernel<false, 4> + attn_dq_w1p_kernel<0>"),
+    ({"DQ_W1": 1}, _SELF, {}, None, "attn_dkdv_w1p_kernel<0> + attn_dq_w1_kernel<0>"),
+    ({"DQ_W1": 0}, _SELF, {}, None, "attn_dkdv_w1p_kernel<0> + attn_dq_pipe_kernel<4>"),
+    ({"DQ_W1": "02"}, _SELF, {}, None, _W1P),  # atoi, not a string prefix
+    ({"DQ_W1": 0, "DQ_PIPE": 0}, _SELF, {}, None, "attn_dkdv_w1p_kernel<0> + attn_q_kernel<64, 1, false, 4>"),
+    ({"DQ_W1": 0, "DQ_NBUF": 3}, _SELF, {}, None, "attn_dkdv_w1p_kernel<0> + attn_dq_pipe_kernel<3>"),
+    ({"DKDV_W1": 0, "DKDV_NBUF": 3}, _SELF, {}, None, "attn_dkdv_pipe_kernel<false, 3> + attn_dq_w1p_kernel<0>"),
+    ({"DKDV_NBUF": 3}, _SELF, dict(bias=True), None, "attn_dkdv_pipe_kernel<true, 3> + attn_q_kernel<64, 1, true, 4>"),
+    # the stamped variants 12 / 13 / 22 exist in diag builds only: here the kernels they time
+    ({"DKDV_W1": 12, "DQ_W1": 13}, _SELF, {}, None, "attn_dkdv_w1_kernel<0> + attn_dq_w1_kernel<0>"),
+    ({"DKDV_W1": 22, "DQ_W1": 22}, _SELF, {}, None, _W1P),
+    # the persistent kernels' limits: f32 dQ, 63 items per workgroup (x 256 CUs), 4-GiB descriptors
+    ({}, _SELF, dict(f32=True), None, "attn_dkdv_w1p_kernel<0> + attn_dq_w1_kernel<0>"),
+    ({}, (8, 32, 16384, 512), {}, None, "attn_dkdv_w1p_kernel<0> + attn_dq_w1_kernel<0>"),
+    ({}, (8, 32, 512, 16384), {}, None, "attn_dkdv_w1_kernel<0> + attn_dq_w1p_kernel<0>"),
+    ({}, (1, 2, 512, 2048), dict(ldk=1 << 20), None, "attn_dkdv_w1p_kernel<0> + attn_dq_w1_kernel<0>"),
+    ({}, (1, 2, 2048, 512), dict(lddo=1 << 20), None, "attn_dkdv_w1_kernel<0> + attn_dq_w1p_kernel<0>"),
+    # LTX_ATTN_W8: bit 0 the 8-wave tiled forward, bit 1 the 8-wave dK/dV (with the plain dQ)
+    ({"W8": 0}, _SELF, dict(bias=True), "attn_q_kernel<64, 0, true, 4>",
+     "attn_dkdv_pipe_kernel<true, 4> + attn_q_kernel<64, 1, true, 4>"),
+    ({"W8": 1}, _SELF, {}, "attn_fwd_pipe_kernel<true>", _W1P),
+    ({"W8": 2}, _SELF, {}, "attn_fwd_pipe_kernel<true>", "attn_dkdv_kernel<64, false, 8> + attn_q_kernel<64, 1, false, 4>"),
+    ({"W8": 2}, _SELF, dict(bias=True), "attn_q_kernel<64, 0, true, 4>",
+     "attn_dkdv_kernel<64, true, 8> + attn_q_kernel<64, 1, true, 4>"),
+    ({"W8": 3}, _SELF, dict(bias=True), "attn_q_kernel<64, 0, true, 8>",
+     "attn_dkdv_kernel<64, true, 8> + attn_q_kernel<64, 1, true, 4>"),
+    ({"DKDV_PIPE": 0}, _SELF, {}, None, "attn_dkdv_kernel<64, false, 4> + attn_q_kernel<64, 1, false, 4>"),
+    ({"DKDV_PIPE": 0}, _SELF, dict(bias=True), None, "attn_dkdv_kernel<64, true, 4> + attn_q_kernel<64, 1, true, 4>"),
+    # switches that change a kernel's arguments, not the kernel
+    ({"XCD": 0, "SKIP": 0, "BWD1_FEW": 0}, _CROSS, dict(bias=True), "attn_fwd1_kernel<64, true, true>",
+     "attn_bwd1_kernel<64, true, false>"),
+]
+
+
+def test_attn_describe_names_the_dispatched_kernels(attn_switches):
+    """ltx_attn_describe (host only: the plan ltx_attn_fwd / ltx_attn_bwd_ex launch from) over a
+    table that reaches every branch of both planners. Without a device the CU count the persistent
+    kernels' item limit uses falls back to 256, the MI355X's own. The workspace is a never
+    dereferenced address registered under made-up stream handles; the default one is not touched."""
+    import ctypes
+    from ltx_amd import _lib
+    lib = _lib.load()
+    streams = {"big": (0x51A0, 128 << 20), "small": (0x51B0, 1 << 20), None: (0x51C0, 0)}
+    for handle, nbytes in streams.values():
+        assert lib.ltx_gemm_set_stream_workspace(ctypes.c_void_p(handle), ctypes.c_void_p(0x10000 if nbytes else 0),
+                                                 nbytes) == 0
+
+    def describe(backward, shape, d=64, bias=False, f32=False, ready=True, ws="big", ldk=0, lddo=0):
+        B, H, Nq, Nk = shape
+        buf = ctypes.create_string_buffer(512)
+        assert lib.ltx_attn_describe(backward, B, H, Nq, Nk, d, int(bias), int(f32), int(ready), H * d, ldk or H * d,
+                                     H * d, lddo or H * d, ctypes.c_void_p(streams[ws][0]), buf, 512) == 0
+        return buf.value.decode()
+
+    def named(kernels):
+        return " + ".join("ltx::" + k for k in kernels.split(" + "))
+    try:
+        for sw, shape, opts, fwd, bwd in _ATTN_DESCRIBE:
+            attn_switches(**sw)
+            if fwd is not None:
+                assert describe(0, shape, **opts) == named(fwd), (sw, shape, opts)
+            if bwd is not None:
+                assert describe(1, shape, **opts) == named(bwd), (sw, shape, opts)
+        buf = ctypes.create_string_buffer(8)
+        assert lib.ltx_attn_describe(0, 1, 1, 64, 64, 48, 0, 0, 1, 48, 48, 48, 48, None, buf, 8) != 0  # head dim
+    finally:
+        for handle, _ in streams.values():
+            lib.ltx_gemm_set_stream_workspace(ctypes.c_void_p(handle), None, 0)

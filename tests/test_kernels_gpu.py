@@ -262,6 +262,27 @@ def test_attention_fwd_bwd(B, H, Nq, Nk, d, masked):
     assert rel(dq32, qf.grad) <= 1.25 * rel(qh.grad, qf.grad) + 1e-3
 
 
+def _labelled(fn, *args, **kw):
+    """fn(*args, **kw) and the labels its attention launches recorded under a LaunchTimer: the
+    kernels the dispatcher planned (ltx_attn_describe). An A/B comparison whose two sides carry the
+    same label ran the same kernels on both."""
+    from ltx_amd import ops
+    saved, timer = ops._timer, ops.LaunchTimer()
+    ops.set_launch_timer(timer)
+    try:
+        out = fn(*args, **kw)
+    finally:
+        ops.set_launch_timer(saved)
+    return out, tuple(r[0] for r in timer.records)
+
+
+def _assert_ab_labels(labels, shape, same_plan):
+    """the two sides of an A/B comparison ran different kernels, except on the rows named in
+    same_plan, where the dispatcher picks one plan for both (the comparison proves nothing there)"""
+    a, b = labels
+    assert (a == b) == (shape in same_plan), (shape, a, b)
+
+
 def _cross_bias(Nk, Bk, valid):
     """Caption-style key bias bf16(-10000) on padded keys: `valid` None -> Nk - 5 - 3b keys of batch
     b kept; an int -> the first `valid` keys (the bench's prompt keeps 16 of 256)."""
@@ -308,35 +329,40 @@ def test_attention_bwd_one_pass(B, H, Nq, Nk, masked, shared, valid, monkeypatch
     refs32 = (qf.grad, batch_summed(kf.grad), batch_summed(vf.grad))
     refs16 = (qh.grad, batch_summed(kh.grad), batch_summed(vh.grad))
     e16 = tuple(rel(a, b_) for a, b_ in zip(refs16, refs32))
-    errs = {}
+    errs, labels = {}, {}
     for mode in ("1", "0"):
         monkeypatch.setenv("LTX_ATTN_BWD1", mode)
         for f32 in (False, True):
-            dq, dk, dv = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, dq_f32=f32,
-                                      kv_shared=shared)
+            (dq, dk, dv), labels[mode, f32] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale,
+                                                        key_bias=bias, dq_f32=f32, kv_shared=shared)
             errs[mode, f32] = tuple(rel(a, b_) for a, b_ in zip((dq, batch_summed(dk), batch_summed(dv)),
                                                                 refs32))
     for f32 in (False, True):
+        assert labels["1", f32] != labels["0", f32] and "attn_bwd1_kernel" in labels["1", f32][0], labels
         for e1, e0, er in zip(errs["1", f32], errs["0", f32], e16):
             assert e1 <= 1.25 * er + 1e-3 and e0 <= 1.25 * er + 1e-3, (errs, e16)
             assert e1 <= 1.25 * e0 + 1e-3, (errs, e16)
     if H * B < 128 and (Nq + 63) // 64 >= 4:  # the one-pass kernel split over the queries
         monkeypatch.setenv("LTX_ATTN_BWD1", "1")
         ops._gemm_workspace(q.device)  # its dK / dV partials live in the stream's workspace
-        outs = {}
+        outs, labels = {}, {}
         for qsplit in ("1", "0"):
             monkeypatch.setenv("LTX_ATTN_QSPLIT", qsplit)
-            outs[qsplit] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, kv_shared=shared)
+            outs[qsplit], labels[qsplit] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias,
+                                                     kv_shared=shared)
+        assert labels["1"] != labels["0"] and labels["1"][0].endswith("attn_bwd1_finish_kernel<64>"), labels
         assert torch.equal(outs["1"][0], outs["0"][0])  # dQ: per query tile, unaffected
         for a, b_ in zip(outs["1"][1:], outs["0"][1:]):  # dK / dV: f32 partials summed in order
             assert rel(a, b_) < 1e-3
     if masked:  # every unmasked key in one 32-key block: per-wave sub-tiles (bwd1_few_keys) against
         # the 8 x 32-key schedule: dQ bitwise, dK / dV to the order of the 8 waves' partial sums
         monkeypatch.setenv("LTX_ATTN_BWD1", "1")
-        outs = {}
+        outs, labels = {}, {}
         for few in ("1", "0"):
             monkeypatch.setenv("LTX_ATTN_BWD1_FEW", few)
-            outs[few] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, kv_shared=shared)
+            outs[few], labels[few] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias,
+                                               kv_shared=shared)
+        assert labels["1"] == labels["0"]  # one kernel: the switch sets its few_keys argument
         assert torch.equal(outs["1"][0], outs["0"][0])
         for a, b_, r32, er in zip(outs["1"][1:], outs["0"][1:], refs32[1:], e16[1:]):
             assert rel(a, b_) < 1e-2
@@ -344,11 +370,14 @@ def test_attention_bwd_one_pass(B, H, Nq, Nk, masked, shared, valid, monkeypatch
         monkeypatch.delenv("LTX_ATTN_BWD1_FEW")
     if Nk <= 128:  # the query-split one-pass kernel (QS) against the 8 x 32-key one: dQ bitwise
         monkeypatch.setenv("LTX_ATTN_BWD1", "1")
-        outs = {}
+        outs, labels = {}, {}
         for qs in ("1", "0"):
             monkeypatch.setenv("LTX_ATTN_BWD1_QS", qs)
-            outs[qs] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias,
-                                    kv_shared=shared)
+            outs[qs], labels[qs] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias,
+                                             kv_shared=shared)
+        # (LTX_ATTN_QSPLIT is still "0" from the block above where that block ran: otherwise H * B < 128
+        # with >= 4 query tiles would take the split-over-S kernel whatever LTX_ATTN_BWD1_QS says)
+        _assert_ab_labels((labels["1"], labels["0"]), (B, H, Nq, Nk), set())
         assert torch.equal(outs["1"][0], outs["0"][0])
         for a, r32, er in zip(outs["1"][1:], refs32[1:], e16[1:]):  # QS dK / dV: noise criterion
             assert rel(batch_summed(a), r32) <= 1.25 * er + 1e-3, (rel(batch_summed(a), r32), er)
@@ -372,14 +401,16 @@ def test_attention_fwd_one_pass(B, H, Nq, Nk, masked, shared, valid, monkeypatch
     v = g(Bk * Nk, H * d, seed=23)
     bias = _cross_bias(Nk, Bk, valid) if masked else None
     monkeypatch.setenv("LTX_ATTN_FWD1", "1")
-    o1, l1 = ops.attn_fwd(q, k, v, B, H, d, d ** -0.5, key_bias=bias, kv_shared=shared)
+    (o1, l1), lab1 = _labelled(ops.attn_fwd, q, k, v, B, H, d, d ** -0.5, key_bias=bias, kv_shared=shared)
     monkeypatch.setenv("LTX_ATTN_FWD1_ROWS", "0")  # O in 32-B pieces instead of LDS-staged rows
-    o2, l2 = ops.attn_fwd(q, k, v, B, H, d, d ** -0.5, key_bias=bias, kv_shared=shared)
+    (o2, l2), lab2 = _labelled(ops.attn_fwd, q, k, v, B, H, d, d ** -0.5, key_bias=bias, kv_shared=shared)
     monkeypatch.delenv("LTX_ATTN_FWD1_ROWS")
+    assert lab1 != lab2 and "attn_fwd1_kernel" in lab1[0] and "attn_fwd1_kernel" in lab2[0], (lab1, lab2)
     assert torch.equal(o1, o2) and torch.equal(l1, l2)
     monkeypatch.setenv("LTX_ATTN_FWD1", "0")
     monkeypatch.setenv("LTX_ATTN_FWD_PIPE", "0")  # the tiled kernel whose arithmetic fwd1 mirrors
-    o0, l0 = ops.attn_fwd(q, k, v, B, H, d, d ** -0.5, key_bias=bias, kv_shared=shared)
+    (o0, l0), lab0 = _labelled(ops.attn_fwd, q, k, v, B, H, d, d ** -0.5, key_bias=bias, kv_shared=shared)
+    assert lab0 != lab1 and "attn_q_kernel<64, 0, " in lab0[0], (lab0, lab1)
     assert torch.equal(o1, o0)
     assert torch.equal(l1, l0)
     kx = k.repeat(B, 1) if shared else k
@@ -407,22 +438,26 @@ def test_attention_padding_blocks_skipped_exactly(B, H, Nq, Nk, valid, shared, m
     do = g(B * Nq, H * d, seed=54)
     keep = torch.arange(Nk, device=DEV)[None, :] < (valid + torch.arange(Bk, device=DEV)[:, None])
     bias = ((1 - keep.to(torch.bfloat16)) * -10000.0).float()
-    res = {}
+    res, labels = {}, {}
     monkeypatch.setenv("LTX_ATTN_BWD1_QS", "0")  # the 8 x 32-key kernel: bitwise skip invariance
     monkeypatch.setenv("LTX_ATTN_BWD1_FEW", "0")
     for mode in ("1", "0"):
         monkeypatch.setenv("LTX_ATTN_SKIP", mode)
-        o, lse = ops.attn_fwd(q, k, v, B, H, d, scale, key_bias=bias, kv_shared=shared)
-        dq, dk, dv = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, kv_shared=shared)
-        res[mode] = (o, lse, dq, dk, dv)
+        (o, lse), lf = _labelled(ops.attn_fwd, q, k, v, B, H, d, scale, key_bias=bias, kv_shared=shared)
+        (dq, dk, dv), lb = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias,
+                                     kv_shared=shared)
+        res[mode], labels[mode] = (o, lse, dq, dk, dv), lf + lb
+    # the same one-pass kernels on both sides: LTX_ATTN_SKIP sets their skip_masked argument
+    assert labels["1"] == labels["0"] and "attn_fwd1_kernel" in labels["1"][0] and "attn_bwd1_kernel" in labels["1"][1]
     for a, b_ in zip(res["1"], res["0"]):
         assert torch.equal(a, b_)
     # one active 32-key block (bwd1_few_keys, the default there): dQ bitwise, dK / dV to the order
     # of the waves' partial sums, every padding key's rows exactly 0
     monkeypatch.setenv("LTX_ATTN_BWD1_FEW", "1")
     monkeypatch.setenv("LTX_ATTN_SKIP", "1")
-    dq3, dk3, dv3 = ops.attn_bwd(q, k, v, res["1"][0], do, res["1"][1], B, H, d, scale, key_bias=bias,
-                                 kv_shared=shared)
+    (dq3, dk3, dv3), lab3 = _labelled(ops.attn_bwd, q, k, v, res["1"][0], do, res["1"][1], B, H, d, scale,
+                                      key_bias=bias, kv_shared=shared)
+    assert lab3 == labels["1"][1:]  # few_keys is an argument of the same kernel
     assert torch.equal(dq3, res["1"][2])
     assert rel(dk3, res["1"][3]) < 1e-2 and rel(dv3, res["1"][4]) < 1e-2
     pad3 = ~(keep.repeat(B, 1) if shared else keep).reshape(-1)
@@ -434,7 +469,11 @@ def test_attention_padding_blocks_skipped_exactly(B, H, Nq, Nk, valid, shared, m
     monkeypatch.setenv("LTX_ATTN_SKIP", "1")
     monkeypatch.setenv("LTX_ATTN_BWD1_QS", "1")
     o, lse = res["1"][:2]
-    dq2, dk2, dv2 = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, kv_shared=shared)
+    (dq2, dk2, dv2), lab2 = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias,
+                                      kv_shared=shared)
+    # every row here has H * B < 128 and >= 4 query tiles: the split-over-S kernel runs with
+    # LTX_ATTN_BWD1_QS=1 as without it, so this comparison is of one plan with itself on all of them
+    _assert_ab_labels((lab2, labels["1"][1:]), (B, H, Nq, Nk), {(8, 4, 1792, 256), (2, 3, 300, 256), (2, 2, 200, 200)})
     assert torch.equal(dq2, res["1"][2])
     assert rel(dk2, res["1"][3]) < 1e-2 and rel(dv2, res["1"][4]) < 1e-2
     for t in (dk2, dv2):
@@ -939,10 +978,12 @@ def test_attention_dkdv_w1_matches_pipe_bitwise(B, H, Nq, Nk, monkeypatch):
     v = g(B * Nk, H * d, seed=73)
     do = g(B * Nq, H * d, seed=74)
     o, lse = ops.attn_fwd(q, k, v, B, H, d, scale)
-    outs = {}
+    outs, labels = {}, {}
     for w1 in ("0", "1"):
         monkeypatch.setenv("LTX_ATTN_DKDV_W1", w1)
-        outs[w1] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale)
+        outs[w1], labels[w1] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale)
+    # Nk <= 256 runs the one-pass attn_bwd1_kernel on both sides
+    _assert_ab_labels((labels["1"], labels["0"]), (B, H, Nq, Nk), {(1, 3, 64, 256), (1, 2, 129, 192)})
     for a, b_ in zip(outs["1"], outs["0"]):
         assert torch.equal(a, b_)
 
@@ -977,14 +1018,16 @@ def test_attention_fwd_w1_matches_pipe_bitwise(B, H, Nq, Nk, jump, monkeypatch):
         pytest.skip("the one-wave forward is not in the shipping library: `make -C csrc fwdw1` builds it")
     saved = L._lib
     L._lib = None
-    outs = {}
+    outs, labels = {}, {}
     try:
         L.load(lib)
         for w1 in ("0", "1"):
             monkeypatch.setenv("LTX_ATTN_FWD_W1", w1)
-            outs[w1] = ops.attn_fwd(q, k, v, B, H, d, scale)
+            outs[w1], labels[w1] = _labelled(ops.attn_fwd, q, k, v, B, H, d, scale)
     finally:
         L._lib = saved
+    # Nk = 256 runs the one-pass attn_fwd1_kernel on both sides
+    _assert_ab_labels((labels["1"], labels["0"]), (B, H, Nq, Nk), {(2, 4, 300, 256)})
     assert torch.equal(outs["1"][0], outs["0"][0])
     assert torch.equal(outs["1"][1], outs["0"][1])
 
@@ -1006,10 +1049,14 @@ def test_attention_dkdv_w1p_matches_w1_bitwise(B, H, Nq, Nk, monkeypatch):
     v = g(B * Nk, H * d, seed=93)
     do = g(B * Nq, H * d, seed=94)
     o, lse = ops.attn_fwd(q, k, v, B, H, d, scale)
-    outs = {}
+    outs, labels = {}, {}
     for w1 in ("1", "2"):
         monkeypatch.setenv("LTX_ATTN_DKDV_W1", w1)
-        outs[w1] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale)
+        outs[w1], labels[w1] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale)
+    # Nk <= 256 runs the one-pass attn_bwd1_kernel on both sides; Nk = 1300 is no multiple of 64, which
+    # keeps the biased attn_dkdv_pipe_kernel + attn_q_kernel pair on both
+    _assert_ab_labels((labels["2"], labels["1"]), (B, H, Nq, Nk),
+                      {(1, 3, 64, 256), (1, 2, 129, 192), (3, 40, 200, 1300)})
     for a, b_ in zip(outs["2"], outs["1"]):
         assert torch.equal(a, b_)
 
@@ -1029,10 +1076,13 @@ def test_attention_dq_w1p_matches_w1_bitwise(B, H, Nq, Nk, monkeypatch):
     v = g(B * Nk, H * d, seed=97)
     do = g(B * Nq, H * d, seed=98)
     o, lse = ops.attn_fwd(q, k, v, B, H, d, scale)
-    outs = {}
+    outs, labels = {}, {}
     for w1 in ("1", "2"):
         monkeypatch.setenv("LTX_ATTN_DQ_W1", w1)
-        outs[w1] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale)
+        outs[w1], labels[w1] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale)
+    # Nk <= 256 runs the one-pass attn_bwd1_kernel on both sides
+    _assert_ab_labels((labels["2"], labels["1"]), (B, H, Nq, Nk),
+                      {(1, 3, 300, 64), (1, 2, 129, 192), (3, 40, 1300, 200)})
     for a, b_ in zip(outs["2"], outs["1"]):
         assert torch.equal(a, b_)
 
@@ -1053,9 +1103,65 @@ def test_attention_dq_w1_matches_pipe_bitwise(B, H, Nq, Nk, monkeypatch):
     do = g(B * Nq, H * d, seed=84)
     o, lse = ops.attn_fwd(q, k, v, B, H, d, scale)
     for f32 in (False, True):
-        outs = {}
+        outs, labels = {}, {}
         for w1 in ("0", "1"):
             monkeypatch.setenv("LTX_ATTN_DQ_W1", w1)
-            outs[w1] = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, dq_f32=f32)
+            outs[w1], labels[w1] = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, dq_f32=f32)
+        # Nk <= 256 runs the one-pass attn_bwd1_kernel on both sides
+        _assert_ab_labels((labels["1"], labels["0"]), (B, H, Nq, Nk), {(1, 3, 300, 64), (1, 2, 129, 192)})
         for a, b_ in zip(outs["1"], outs["0"]):
             assert torch.equal(a, b_), f32
+
+
+# one default-switch shape per branch of the two planners (csrc/attn_plan.h): (B, H, Nq, Nk, d, key
+# bias, f32 dQ, forward kernel, backward kernels after the delta kernel)
+_W1P_PAIR = "ltx::attn_dkdv_w1p_kernel<0> + ltx::attn_dq_w1p_kernel<0>"
+_BIASED_PAIR = "ltx::attn_dkdv_pipe_kernel<true, 4> + ltx::attn_q_kernel<64, 1, true, 4>"
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,d,masked,f32,fwd,bwd", [
+    (1, 3, 100, 128, 32, False, False, "ltx::attn_q_kernel<32, 0, false, 4>",
+     "ltx::attn_dkdv_kernel<32, false, 4> + ltx::attn_q_kernel<32, 1, false, 4>"),
+    (1, 3, 100, 77, 32, True, False, "ltx::attn_q_kernel<32, 0, true, 4>",
+     "ltx::attn_dkdv_kernel<32, true, 4> + ltx::attn_q_kernel<32, 1, true, 4>"),
+    (2, 4, 100, 256, 64, False, False, "ltx::attn_fwd1_kernel<64, false, true>",
+     "ltx::attn_bwd1_kernel<64, false, false>"),
+    (2, 4, 100, 200, 64, True, False, "ltx::attn_fwd1_kernel<64, true, true>",
+     "ltx::attn_bwd1_kernel<64, true, false>"),
+    (2, 4, 256, 256, 64, False, False, "ltx::attn_fwd1_kernel<64, false, true>",  # H * B < 128, 4 query tiles
+     "ltx::attn_bwd1_kernel<64, false, false> + ltx::attn_bwd1_finish_kernel<64>"),
+    (1, 2, 256, 256, 64, True, False, "ltx::attn_fwd1_kernel<64, true, true>",
+     "ltx::attn_bwd1_kernel<64, true, false> + ltx::attn_bwd1_finish_kernel<64>"),
+    (2, 3, 300, 512, 64, False, False, "ltx::attn_fwd_pipe_kernel<true>", _W1P_PAIR),
+    (2, 3, 300, 512, 64, False, True, "ltx::attn_fwd_pipe_kernel<true>",
+     "ltx::attn_dkdv_w1p_kernel<0> + ltx::attn_dq_w1_kernel<0>"),
+    (1, 2, 300, 512, 64, True, False, "ltx::attn_q_kernel<64, 0, true, 8>", _BIASED_PAIR),
+    (1, 2, 129, 300, 64, False, False, "ltx::attn_q_kernel<64, 0, true, 8>", _BIASED_PAIR)])
+def test_attention_launch_labels_are_the_described_plan(B, H, Nq, Nk, d, masked, f32, fwd, bwd):
+    """Under a LaunchTimer ops.attn_fwd / ops.attn_bwd record exactly ltx_attn_describe's answer for
+    the call (behind the 'attention forward: ' / 'attention backward: ' prefixes), which at default
+    switches is the kernel named here; without a timer they never ask for it."""
+    import ctypes
+    from ltx_amd import _lib as L, ops
+    scale = d ** -0.5
+    q, do = g(B * Nq, H * d, seed=31), g(B * Nq, H * d, seed=34)
+    k, v = g(B * Nk, H * d, seed=32), g(B * Nk, H * d, seed=33)
+    bias = _cross_bias(Nk, B, None) if masked else None
+
+    def described(backward, ready):
+        buf = ctypes.create_string_buffer(512)
+        L.call("ltx_attn_describe", backward, B, H, Nq, Nk, d, int(masked), int(f32), int(ready), H * d, H * d,
+               H * d, H * d, L.stream_ptr(), buf, 512)
+        return buf.value.decode()
+    cached = len(ops._ATTN_LABELS)
+    o, lse = ops.attn_fwd(q, k, v, B, H, d, scale, key_bias=bias)
+    ops.attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, dq_f32=f32)
+    assert len(ops._ATTN_LABELS) == cached
+    _, lab = _labelled(ops.attn_fwd, q, k, v, B, H, d, scale, key_bias=bias)
+    assert lab == ("attention forward: " + fwd,) and described(0, True) == fwd
+    _, lab = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, dq_f32=f32)
+    assert lab == (f"attention backward: ltx::attn_delta_kernel<{d}> + " + bwd,)
+    assert described(1, False) == f"ltx::attn_delta_kernel<{d}> + " + bwd
+    delta = (do.float() * o.float()).view(B, Nq, H, d).sum(-1).permute(0, 2, 1).contiguous()
+    _, lab = _labelled(ops.attn_bwd, q, k, v, o, do, lse, B, H, d, scale, key_bias=bias, dq_f32=f32, delta=delta)
+    assert lab == ("attention backward: " + bwd,) and described(1, True) == bwd

@@ -1,5 +1,6 @@
 """Fingerprint of one step per model configuration (and, group `optim`, of three optimizer steps per
-optimizer condition), to hold a refactor to equality.
+optimizer condition; group `attn`, of direct attention calls per shape and LTX_ATTN_* switch), to hold a
+refactor to equality.
 
     python tools/step_fingerprint.py run --pkg <dir that holds ltx_amd/> --group <name> --out fp.json
     python tools/step_fingerprint.py compare old.json new.json [--md table.md]
@@ -46,6 +47,17 @@ GROUPS = {
     "optim": ({}, [f"{kind}{variant}_{mode}" for kind in ("adamw", "prodigy") for variant in ("", "_clip", "_ema")
                    for mode in ("nearest", "stochastic")] + ["adamw_clip_ema_swap"]),
 }
+# group `attn`: ops.attn_fwd + ops.attn_bwd alone, one small shape per branch of the attention planners
+# (csrc/attn_plan.h; B, H, Nq, Nk, head dim, key bias, f32 dQ), at default switches and at each single
+# non-default LTX_ATTN_* switch (set per configuration: ops reloads the library's table when one changes)
+ATTN_SHAPES = [(1, 3, 100, 128, 32, False, False), (1, 3, 100, 77, 32, True, False), (2, 4, 100, 256, 64, False, False),
+               (2, 4, 100, 200, 64, True, False), (2, 4, 256, 256, 64, False, False), (1, 2, 256, 256, 64, True, False),
+               (2, 3, 300, 512, 64, False, False), (2, 3, 300, 512, 64, False, True), (1, 2, 300, 512, 64, True, False),
+               (1, 2, 129, 300, 64, False, False)]
+ATTN_SWITCHES = ["default", "XCD=0", "BWD1=0", "W8=0", "SKIP=0", "FWD1=0", "FWD1_ROWS=0", "BWD1_QS=1", "BWD1_FEW=0",
+                 "QSPLIT=0", "DKDV_W1=1", "DKDV_W1=0", "DQ_W1=1", "DQ_W1=0", "DQ_PIPE=0", "DQ_NBUF=3", "FWD_W1=1",
+                 "FWD_PIPE=0", "FWD_F32SUM=0", "DKDV_PIPE=0", "DKDV_NBUF=3"]
+GROUPS["attn"] = ({}, [f"{'x'.join(str(int(v)) for v in shape)}/{sw}" for shape in ATTN_SHAPES for sw in ATTN_SWITCHES])
 
 
 def _sha(t):
@@ -224,6 +236,37 @@ def _optim_one(name, torch):
             "loss": None if record is None else _sha(record), "grads": hashes}
 
 
+def _attn_one(name, torch):
+    """One forward + backward of the configuration's shape under its switch: "kernels" the two labels,
+    "output" / "loss" the hashes of O / lse, "grads" those of dQ, dK and dV."""
+    from ltx_amd import ops
+    shape, sw = name.split("/")
+    B, H, Nq, Nk, d, masked, f32 = (int(v) for v in shape.split("x"))
+    gen = torch.Generator(device="cpu").manual_seed(Nq * 1000 + Nk)
+    q, do, k, v = (torch.randn(B * n, H * d, generator=gen).bfloat16().cuda() for n in (Nq, Nq, Nk, Nk))
+    bias = None
+    if masked:  # caption-style padding: batch b keeps its first Nk - 5 - 3 b keys
+        keep = torch.arange(Nk)[None, :] < (Nk - 5 - 3 * torch.arange(B)[:, None])
+        bias = ((1 - keep.float()) * -10000.0).cuda().contiguous()
+    env = dict([sw.split("=")]) if sw != "default" else {}
+    for key, val in env.items():
+        os.environ["LTX_ATTN_" + key] = val
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    timer = ops.LaunchTimer()
+    ops.set_launch_timer(timer)
+    try:
+        o, lse = ops.attn_fwd(q, k, v, B, H, d, d ** -0.5, key_bias=bias)
+        dq, dk, dv = ops.attn_bwd(q, k, v, o, do, lse, B, H, d, d ** -0.5, key_bias=bias, dq_f32=bool(f32))
+    finally:
+        ops.set_launch_timer(None)
+        for key in env:
+            del os.environ["LTX_ATTN_" + key]
+    torch.cuda.synchronize()
+    return {"kernels": [r[0] for r in timer.records], "peak_bytes": torch.cuda.max_memory_allocated(),
+            "output": _sha(o), "loss": _sha(lse), "grads": {"dq": _sha(dq), "dk": _sha(dk), "dv": _sha(dv)}}
+
+
 def run(args):
     env, names = GROUPS[args.group]
     os.environ.update(env)
@@ -234,10 +277,11 @@ def run(args):
     from ltx_amd import _lib
     _lib.ensure_device("cuda:0")
     torch.cuda.set_device(0)
-    case = None if args.group == "optim" else _2b_case() if args.group == "2b" else _tiny_case()
+    case = None if args.group in ("optim", "attn") else _2b_case() if args.group == "2b" else _tiny_case()
     out = {"pkg": os.path.dirname(os.path.abspath(ltx_amd.__file__)), "env": env, "configs": {}}
     for name in names:
-        rec = _optim_one(name, torch) if case is None else _one(name, case, torch)
+        rec = (_attn_one(name, torch) if args.group == "attn" else _optim_one(name, torch) if case is None
+               else _one(name, case, torch))
         out["configs"][f"{args.group}/{name}"] = rec
         gc.collect()
         torch.cuda.empty_cache()

@@ -24,6 +24,7 @@
 // f32 atomics a fused kernel needs for dQ (which on MI355X would be bound by the ~1.3 TB/s
 // atomic rate at these sizes).
 #include <cstdlib>
+#include <mutex>
 
 #include "attention_common.h"
 #include "ltx_hip.h"
@@ -477,9 +478,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void attn_dkdv_kernel(con
     }
 }
 
-// key ranges of at most this many run the one-pass kernels (one 8-wave workgroup holds them all)
-constexpr int BWD1_KEYS = 256;
-constexpr int BWD1_THREADS = 512;
 // key bias (log2 units) at or below which a key counts as padding for tile skipping: the caption
 // mask's bf16(-10000) * log2(e) = -14404, and -inf past Nk. Exact as long as the scaled scores of
 // a row differ by less than ~(14404 - 10000) - 150 log2 units from its unmasked maximum.
@@ -1351,210 +1349,79 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnParams p, flo
   }
 }
 
-static inline bool needs_bias(const AttnParams& p) { return p.key_bias != nullptr || (p.Nk % 64) != 0; }
-
-#ifndef LTX_ATTN_W8_DEFAULT
-#define LTX_ATTN_W8_DEFAULT 1
-#endif
-
+// The LTX_ATTN_* switch values (attn_plan.h ATTN_SWITCHES), read from the environment at the first
+// launch and again by ltx_attn_reload_switches(); every launch plans from a copy taken under the lock,
+// so a reload on one host thread never shows another thread's launch half a table.
 static AttnSwitches read_attn_switches() {
   AttnSwitches w;
-  auto num = [](const char* name, int dflt) {
-    const char* e = std::getenv(name);
-    return (e && e[0]) ? std::atoi(e) : dflt;
-  };
-  auto off0 = [](const char* name) {  // "0..." switches a default-on path off
-    const char* e = std::getenv(name);
-    return (e && e[0] == '0') ? 0 : 1;
-  };
-  w.xcd = off0("LTX_ATTN_XCD");
-  w.bwd1 = off0("LTX_ATTN_BWD1");
-  // bit 0 = 8-wave (256-query) tiled forward, bit 1 = 8-wave (256-key) dK/dV kernel; the default
-  // is the forward only (self-attention forward 297-305 vs 310-316 us, dK/dV 881-889 vs 857-862 us
-  // with 8 waves, tools/attn_bench.py)
-  w.w8 = num("LTX_ATTN_W8", LTX_ATTN_W8_DEFAULT);
-  w.skip = off0("LTX_ATTN_SKIP");
-  w.fwd1 = off0("LTX_ATTN_FWD1");
-  w.fwd1_rows = off0("LTX_ATTN_FWD1_ROWS");
-  {  // off by default: its step A/B was neutral, and with it dK / dV of the unmasked keys are the sum
-     // of two partials (f32 rounding away from the 8 x 32-key kernel; dQ stays bitwise)
-    const char* e = std::getenv("LTX_ATTN_BWD1_QS");
-    w.bwd1_qs = (e && e[0] == '1') ? 1 : 0;
-  }
-  w.bwd1_few = off0("LTX_ATTN_BWD1_FEW");
-  w.qsplit = off0("LTX_ATTN_QSPLIT");
-  w.dkdv_w1 = num("LTX_ATTN_DKDV_W1", 2);
-  w.dq_w1 = num("LTX_ATTN_DQ_W1", 2);
-  w.dq_pipe = num("LTX_ATTN_DQ_PIPE", 1) != 0;
-  {
-    const char* e = std::getenv("LTX_ATTN_DQ_NBUF");
-    w.dq_nbuf = (e && e[0] == '3') ? 3 : 4;
-  }
-  {
-    const char* e = std::getenv("LTX_ATTN_FWD_W1");
-    w.fwd_w1 = (e && e[0] && e[0] != '0') ? std::atoi(e) : 0;
-  }
-  w.fwd_pipe = num("LTX_ATTN_FWD_PIPE", 1) != 0;
-  w.fwd_f32sum = off0("LTX_ATTN_FWD_F32SUM");
-  w.dkdv_pipe = num("LTX_ATTN_DKDV_PIPE", 1) != 0;
-  {
-    const char* e = std::getenv("LTX_ATTN_DKDV_NBUF");
-    w.dkdv_nbuf = (e && e[0] == '3') ? 3 : 4;
-  }
+  for (const AttnSwitchDef& d : ATTN_SWITCHES) w.*d.field = parse_attn_switch(d.rule, std::getenv(d.env), w.*d.field);
   return w;
 }
-
+static std::mutex g_switch_mu;
 static AttnSwitches& switch_table() {
   static AttnSwitches w = read_attn_switches();
   return w;
 }
 
-const AttnSwitches& attn_switches() { return switch_table(); }
-
-static int xcd_order_flag() { return attn_switches().xcd; }
-static int bwd1_flag() { return attn_switches().bwd1; }
-static int waves8_flag(int bit) { return (attn_switches().w8 >> bit) & 1; }
-static int skip_flag() { return attn_switches().skip; }
-static int fwd1_flag() { return attn_switches().fwd1; }
-static int bwd1_qs_flag() { return attn_switches().bwd1_qs; }
-static int bwd1_few_flag() { return attn_switches().bwd1_few; }
-static int qsplit_flag() { return attn_switches().qsplit; }
-
-template <int HD>
-static int launch_fwd(AttnParams p, hipStream_t s) {
-  p.xcd_order = xcd_order_flag();
-  p.skip_masked = skip_flag();
-  if constexpr (HD == 64) {
-    if (p.Nk <= BWD1_KEYS && fwd1_flag()) {  // every key staged once per (batch, head)
-      // two workgroups per (batch, head) when that still leaves >= 8 slices each: 2 per CU
-      // (more when H * B leaves the chip short of 256 workgroups: inference, config X at B = 1)
-      const int nsl = (p.Nq + 31) / 32;
-      int z = nsl >= 16 ? 2 : 1;
-      if (z == 2 && p.H * p.B < 128) z = std::max(2, std::min(nsl / 8, (256 + p.H * p.B - 1) / (p.H * p.B)));
-      const dim3 g1((unsigned)p.H, (unsigned)p.B, (unsigned)z);
-      const bool rows = attn_switches().fwd1_rows != 0;
-      if (needs_bias(p)) {
-        if (rows) hipLaunchKernelGGL((attn_fwd1_kernel<HD, true, true>), g1, dim3(BWD1_THREADS), 0, s, p);
-        else hipLaunchKernelGGL((attn_fwd1_kernel<HD, true, false>), g1, dim3(BWD1_THREADS), 0, s, p);
-      } else {
-        if (rows) hipLaunchKernelGGL((attn_fwd1_kernel<HD, false, true>), g1, dim3(BWD1_THREADS), 0, s, p);
-        else hipLaunchKernelGGL((attn_fwd1_kernel<HD, false, false>), g1, dim3(BWD1_THREADS), 0, s, p);
-      }
-      LTX_LAUNCH_CHECK();
-      return LTX_OK;
-    }
+static int cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
   }
-  if constexpr (HD == 64) {
-    if (!needs_bias(p) && fwd_pipe_enabled()) return launch_fwd_pipe(p, s);
-    if (waves8_flag(0)) {
-      dim3 grid((unsigned)((p.Nq + 255) / 256), (unsigned)p.H, (unsigned)p.B);
-      if (needs_bias(p))
-        hipLaunchKernelGGL((attn_q_kernel<HD, 0, true, 8>), grid, dim3(512), 0, s, p);
-      else
-        hipLaunchKernelGGL((attn_q_kernel<HD, 0, false, 8>), grid, dim3(512), 0, s, p);
-      LTX_LAUNCH_CHECK();
-      return LTX_OK;
-    }
+  return n;
+}
+
+// everything a plan depends on besides the call itself
+static AttnSite attn_site(hipStream_t s) {
+  AttnSite e = {};
+  {
+    std::lock_guard<std::mutex> lock(g_switch_mu);
+    e.sw = switch_table();
   }
-  dim3 grid((unsigned)((p.Nq + 127) / 128), (unsigned)p.H, (unsigned)p.B);
-  if (needs_bias(p))
-    hipLaunchKernelGGL((attn_q_kernel<HD, 0, true>), grid, dim3(ATT_THREADS), 0, s, p);
-  else
-    hipLaunchKernelGGL((attn_q_kernel<HD, 0, false>), grid, dim3(ATT_THREADS), 0, s, p);
+  e.cus = cu_count();
+  e.ws = stream_workspace(s, &e.ws_bytes);
+#ifdef LTX_FWD_W1
+  e.fwd_w1 = true;
+#endif
+#ifdef LTX_DKDV_DIAG
+  e.diag = true;
+#endif
+  return e;
+}
+
+static int launch_kernel(const AttnLaunch& l, AttnParams p, hipStream_t s) {
+  p.part = l.part;
+  const dim3 g(l.gx, l.gy, l.gz);
+  switch (l.k) {
+#define LTX_X(id, threads, ...) \
+  case id: hipLaunchKernelGGL((__VA_ARGS__), g, dim3(threads), 0, s, p); break;
+    LTX_ATTN_KERNELS_MAIN(LTX_X)
+#undef LTX_X
+    default: return launch_pipe_kernel(l, p, s);
+  }
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
 
-template <int HD>
-static int launch_bwd(AttnParams p, float* delta, int delta_ready, hipStream_t s) {
-  if (!delta_ready) {
-    hipLaunchKernelGGL(attn_delta_kernel<HD>, dim3((unsigned)(((int64_t)p.B * p.Nq + 3) / 4)), dim3(256), 0, s,
-                       p, delta);
+static int launch_plan(const AttnPlan& pl, AttnParams p, float* delta, hipStream_t s) {
+  if (pl.err) return fail(LTX_ERR_BAD_ARG, pl.err);
+  if (pl.delta) {
+    const dim3 g((unsigned)(((int64_t)p.B * p.Nq + 3) / 4));
+    if (pl.HD == 64) hipLaunchKernelGGL(attn_delta_kernel<64>, g, dim3(256), 0, s, p, delta);
+    else hipLaunchKernelGGL(attn_delta_kernel<32>, g, dim3(256), 0, s, p, delta);
     LTX_LAUNCH_CHECK();
   }
   p.delta = delta;
-  p.xcd_order = xcd_order_flag();
-  p.skip_masked = skip_flag();
-  p.few_keys = p.skip_masked && bwd1_few_flag();
-  if constexpr (HD == 64) {  // (head dim 32, the tiny config, keeps the split kernels)
-    if (p.Nk <= BWD1_KEYS && bwd1_flag()) {  // every key in one workgroup: one-pass backward
-      // under 128 (batch, head) pairs the queries are split over S workgroups each (f32 dK / dV
-      // partials in the stream's workspace, summed in order by attn_bwd1_finish_kernel)
-      p.qsplit = 1;
-      const int ntot = (p.Nq + 63) / 64;
-      if (p.H * p.B < 128 && ntot >= 4 && qsplit_flag()) {
-        // S depends on the shape alone, so the dK / dV summation order does too; when its partials
-        // do not fit the stream's workspace the unsplit kernel runs instead (never a smaller S)
-        const int S = std::min(ntot / 2, (256 + p.H * p.B - 1) / (p.H * p.B));
-        size_t ws = 0;
-        float* part = stream_workspace(s, &ws);
-        if (S > 1 && part != nullptr && (size_t)2 * S * p.B * p.Nk * p.H * HD * sizeof(float) <= ws) {
-          p.qsplit = S;
-          p.part = part;
-          const dim3 gs((unsigned)p.H, (unsigned)p.B, (unsigned)S);
-          if (p.key_bias != nullptr || p.Nk != BWD1_KEYS)
-            hipLaunchKernelGGL((attn_bwd1_kernel<HD, true, false>), gs, dim3(BWD1_THREADS), 0, s, p);
-          else
-            hipLaunchKernelGGL((attn_bwd1_kernel<HD, false, false>), gs, dim3(BWD1_THREADS), 0, s, p);
-          LTX_LAUNCH_CHECK();
-          const int64_t n8 = (int64_t)p.B * p.Nk * p.H * HD / 8;
-          hipLaunchKernelGGL((attn_bwd1_finish_kernel<HD>), dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, p);
-          LTX_LAUNCH_CHECK();
-          return LTX_OK;
-        }
-      }
-      const dim3 g1((unsigned)p.H, (unsigned)p.B);
-      if ((p.key_bias != nullptr || p.Nk != BWD1_KEYS) && bwd1_qs_flag())
-        hipLaunchKernelGGL((attn_bwd1_kernel<HD, true, true>), g1, dim3(BWD1_THREADS), 0, s, p);
-      else if (p.key_bias != nullptr || p.Nk != BWD1_KEYS)
-        hipLaunchKernelGGL((attn_bwd1_kernel<HD, true, false>), g1, dim3(BWD1_THREADS), 0, s, p);
-      else
-        hipLaunchKernelGGL((attn_bwd1_kernel<HD, false, false>), g1, dim3(BWD1_THREADS), 0, s, p);
-      LTX_LAUNCH_CHECK();
-      return LTX_OK;
-    }
+  p.xcd_order = pl.xcd_order;
+  p.skip_masked = pl.skip_masked;
+  p.few_keys = pl.few_keys;
+  p.qsplit = pl.qsplit;
+  for (int i = 0; i < pl.n; ++i) {
+    const int rc = launch_kernel(pl.l[i], p, s);
+    if (rc != LTX_OK) return rc;
   }
-  dim3 gq((unsigned)((p.Nq + 127) / 128), (unsigned)p.H, (unsigned)p.B);
-  bool k8 = false;
-  if constexpr (HD == 64) k8 = waves8_flag(1);
-  dim3 gk((unsigned)(k8 ? (p.Nk + 255) / 256 : (p.Nk + 127) / 128), (unsigned)p.H, (unsigned)p.B);
-  if (HD == 64 && !k8 && dkdv_pipe_enabled()) {
-    if (needs_bias(p)) {
-      hipLaunchKernelGGL((attn_q_kernel<HD, 1, true>), gq, dim3(ATT_THREADS), 0, s, p);
-      LTX_LAUNCH_CHECK();
-    } else if (dq_w1p_enabled() && dq_w1p_applies(p)) {
-      const int rc = launch_dq_w1p(p, s);
-      if (rc != LTX_OK) return rc;
-    } else if (dq_w1_enabled()) {
-      const int rc = launch_dq_w1(p, s);
-      if (rc != LTX_OK) return rc;
-    } else if (dq_pipe_enabled()) {
-      const int rc = launch_dq_pipe(p, s);
-      if (rc != LTX_OK) return rc;
-    } else {
-      hipLaunchKernelGGL((attn_q_kernel<HD, 1, false>), gq, dim3(ATT_THREADS), 0, s, p);
-      LTX_LAUNCH_CHECK();
-    }
-    if (!needs_bias(p) && dkdv_w1p_enabled() && dkdv_w1p_applies(p)) return launch_dkdv_w1p(p, s);
-    if (!needs_bias(p) && dkdv_w1_enabled()) return launch_dkdv_w1(p, s);
-    return launch_dkdv_pipe(p, s);
-  }
-  if (needs_bias(p)) {
-    hipLaunchKernelGGL((attn_q_kernel<HD, 1, true>), gq, dim3(ATT_THREADS), 0, s, p);
-    LTX_LAUNCH_CHECK();
-    if (k8)
-      hipLaunchKernelGGL((attn_dkdv_kernel<HD, true, HD == 64 ? 8 : 4>), gk, dim3(512), 0, s, p);
-    else
-      hipLaunchKernelGGL((attn_dkdv_kernel<HD, true>), gk, dim3(ATT_THREADS), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((attn_q_kernel<HD, 1, false>), gq, dim3(ATT_THREADS), 0, s, p);
-    LTX_LAUNCH_CHECK();
-    if (k8)
-      hipLaunchKernelGGL((attn_dkdv_kernel<HD, false, HD == 64 ? 8 : 4>), gk, dim3(512), 0, s, p);
-    else
-      hipLaunchKernelGGL((attn_dkdv_kernel<HD, false>), gk, dim3(ATT_THREADS), 0, s, p);
-  }
-  LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
 
@@ -1573,6 +1440,11 @@ static int check_common(const void* q, int64_t ldq, const void* k, int64_t ldk, 
 
 using namespace ltx;
 
+static AttnCall attn_call(const AttnParams& p, int64_t d, int delta_ready) {
+  return AttnCall{(int)d, p.B, p.H, p.Nq, p.Nk, p.key_bias != nullptr, p.dq_f32 != 0, delta_ready != 0,
+                  p.ldq, p.ldk, p.ldv, p.lddo};
+}
+
 extern "C" int ltx_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                             void* o, int64_t ldo, float* lse, const float* key_bias, int64_t B, int64_t H,
                             int64_t Nq, int64_t Nk, int64_t kv_batch_rows, int64_t d, float scale, void* stream) {
@@ -1584,8 +1456,8 @@ extern "C" int ltx_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t l
   p.q = (const bf16_t*)q; p.ldq = ldq; p.k = (const bf16_t*)k; p.ldk = ldk; p.v = (const bf16_t*)v; p.ldv = ldv;
   p.o_out = (bf16_t*)o; p.ldo = ldo; p.lse = lse; p.key_bias = key_bias;
   p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)Nk; p.kvb = (int)kv_batch_rows; p.scale = scale;
-  p.qsplit = 1;
-  return d == 64 ? launch_fwd<64>(p, (hipStream_t)stream) : launch_fwd<32>(p, (hipStream_t)stream);
+  const hipStream_t s = (hipStream_t)stream;
+  return launch_plan(plan_attn_fwd(attn_call(p, d, 1), attn_site(s)), p, nullptr, s);
 }
 
 extern "C" int ltx_attn_bwd_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
@@ -1606,9 +1478,8 @@ extern "C" int ltx_attn_bwd_ex(const void* q, int64_t ldq, const void* k, int64_
   p.dq = dq; p.lddq = lddq; p.dq_f32 = dq_is_f32;
   p.dk = (bf16_t*)dk; p.lddk = lddk; p.dv = (bf16_t*)dv; p.lddv = lddv;
   p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)Nk; p.kvb = (int)kv_batch_rows; p.scale = scale;
-  p.qsplit = 1;
-  return d == 64 ? launch_bwd<64>(p, delta_ws, delta_ready, (hipStream_t)stream)
-                 : launch_bwd<32>(p, delta_ws, delta_ready, (hipStream_t)stream);
+  const hipStream_t s = (hipStream_t)stream;
+  return launch_plan(plan_attn_bwd(attn_call(p, d, delta_ready), attn_site(s)), p, delta_ws, s);
 }
 
 extern "C" int ltx_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
@@ -1621,6 +1492,24 @@ extern "C" int ltx_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t l
 }
 
 extern "C" int ltx_attn_reload_switches(void) {
-  ltx::switch_table() = ltx::read_attn_switches();
+  const AttnSwitches w = read_attn_switches();
+  std::lock_guard<std::mutex> lock(g_switch_mu);
+  switch_table() = w;
+  return LTX_OK;
+}
+
+extern "C" const char* ltx_attn_switch_name(int i) {
+  return (i >= 0 && i < ATTN_NSWITCH) ? ATTN_SWITCHES[i].env : nullptr;
+}
+
+extern "C" int ltx_attn_describe(int backward, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
+                                 int has_key_bias, int dq_is_f32, int delta_ready, int64_t ldq, int64_t ldk,
+                                 int64_t ldv, int64_t lddo, void* stream, char* buf, int64_t len) {
+  LTX_CHECK_ARG(buf && len > 0 && (d == 32 || d == 64) && B > 0 && H > 0 && Nq > 0 && Nk > 0,
+                "attn_describe: bad args");
+  const AttnCall c{(int)d, (int)B, (int)H, (int)Nq, (int)Nk, has_key_bias != 0, dq_is_f32 != 0, delta_ready != 0,
+                   ldq, ldk, ldv, lddo};
+  const AttnSite e = attn_site((hipStream_t)stream);
+  describe_attn_plan(backward ? plan_attn_bwd(c, e) : plan_attn_fwd(c, e), buf, (size_t)len);
   return LTX_OK;
 }

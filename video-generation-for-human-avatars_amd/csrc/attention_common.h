@@ -2,6 +2,7 @@
 // fragment reads for v_mfma_f32_32x32x16_bf16 in the swapped orientation, the parameter block,
 // row-statistic helpers and the XCD-aware block order. See attention.hip for the design notes.
 #pragma once
+#include "attn_plan.h"
 #include "common.h"
 
 namespace ltx {
@@ -139,32 +140,6 @@ __device__ __forceinline__ void dma4(const void* gsrc, uint32_t lds) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(gsrc), "s"(lds) : "memory");
 }
-
-// The attention path's A/B switches (LTX_ATTN_*), read from the environment ONCE (first launch)
-// into this table; ltx_attn_reload_switches() re-reads them (tests that compare two paths in one
-// process; ops.py calls it when it sees an LTX_ATTN_* variable change). Defaults are the shipping
-// configuration. Defined in attention.hip.
-struct AttnSwitches {
-  int xcd = 1;          // LTX_ATTN_XCD=0: hardware block order
-  int bwd1 = 1;         // LTX_ATTN_BWD1=0: split dQ + dK/dV kernels for every key range
-  int w8 = 1;           // LTX_ATTN_W8: bit 0 8-wave tiled forward, bit 1 8-wave dK/dV
-  int skip = 1;         // LTX_ATTN_SKIP=0: one-pass kernels keep all-padding key blocks
-  int fwd1 = 1;         // LTX_ATTN_FWD1=0: tiled forward for every key range
-  int fwd1_rows = 1;    // LTX_ATTN_FWD1_ROWS=0: the one-pass forward stores O in 32-B pieces
-  int bwd1_qs = 0;      // LTX_ATTN_BWD1_QS=1: query-split one-pass backward for biased ranges
-  int bwd1_few = 1;     // LTX_ATTN_BWD1_FEW=0: keep the 8 x 32-key schedule for few unmasked keys
-  int qsplit = 1;       // LTX_ATTN_QSPLIT=0: one workgroup per (batch, head) at any H * B
-  int dkdv_w1 = 2;      // LTX_ATTN_DKDV_W1: 2 persistent, 1 per block, 0 pipe, 12..16 / 22 diagnostic
-  int dq_w1 = 2;        // LTX_ATTN_DQ_W1: likewise for dQ
-  int dq_pipe = 1;      // LTX_ATTN_DQ_PIPE=0: the plain dQ kernel
-  int dq_nbuf = 4;      // LTX_ATTN_DQ_NBUF=3: 3-buffer ring
-  int fwd_w1 = 0;       // LTX_ATTN_FWD_W1 (only in `make fwdw1` builds)
-  int fwd_pipe = 1;     // LTX_ATTN_FWD_PIPE=0: attn_q_kernel<64, 0, false, 8>
-  int fwd_f32sum = 1;   // LTX_ATTN_FWD_F32SUM=0: row sums by v_dot2c over the bf16 weights
-  int dkdv_pipe = 1;    // LTX_ATTN_DKDV_PIPE=0: the plain dK/dV kernel
-  int dkdv_nbuf = 4;    // LTX_ATTN_DKDV_NBUF=3: 3-buffer ring
-};
-const AttnSwitches& attn_switches();
 
 struct AttnParams {
   const bf16_t* q; int64_t ldq;
@@ -346,28 +321,8 @@ __device__ __forceinline__ void store_row_swap(const f32x16* acc, float scale, b
     }
 }
 
-// the dK/dV kernel with the software-pipelined, LDS-DMA-staged loop (attention_dkdv.hip)
-int launch_dkdv_pipe(const AttnParams& p, hipStream_t s);
-bool dkdv_pipe_enabled();
-// the dQ kernel with the same structure, for key ranges without bias (Nk % 64 == 0)
-int launch_dq_pipe(const AttnParams& p, hipStream_t s);
-bool dq_pipe_enabled();
-// the dK/dV kernel at one wave per SIMD (hand-scheduled loop, attn_bwd_body.h): no key bias, head dim 64
-int launch_dkdv_w1(const AttnParams& p, hipStream_t s);
-bool dkdv_w1_enabled();
-// the persistent dK/dV kernel (one workgroup per CU walking 256-key blocks; attn_bwd_body.h)
-int launch_dkdv_w1p(const AttnParams& p, hipStream_t s);
-bool dkdv_w1p_enabled();
-bool dkdv_w1p_applies(const AttnParams& p);
-// the persistent dQ kernel (one workgroup per CU walking 256-query blocks; bf16 dQ)
-int launch_dq_w1p(const AttnParams& p, hipStream_t s);
-bool dq_w1p_enabled();
-bool dq_w1p_applies(const AttnParams& p);
-// the dQ kernel at one wave per SIMD (hand-scheduled loop, attn_bwd_body.h): no key bias, head dim 64
-int launch_dq_w1(const AttnParams& p, hipStream_t s);
-bool dq_w1_enabled();
-// the forward with K / V by LDS-DMA and one barrier per tile (no key bias, Nk % 64 == 0)
-int launch_fwd_pipe(const AttnParams& p, hipStream_t s);
-bool fwd_pipe_enabled();
+// launches the kernels of attn_plan.h's LTX_ATTN_KERNELS_PIPE table (and of the fwdw1 / diag builds'
+// tables), which live in attention_pipe.hip
+int launch_pipe_kernel(const AttnLaunch& l, const AttnParams& p, hipStream_t s);
 
 }  // namespace ltx

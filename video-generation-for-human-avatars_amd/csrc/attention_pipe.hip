@@ -338,10 +338,6 @@ __global__ __launch_bounds__(256, 2) void attn_dkdv_pipe_kernel(const AttnParams
 // out-of-range handling of ragged query tiles are described there). Same arithmetic, fragment
 // layouts and MFMA accumulation order as attn_dkdv_pipe_kernel: dK / dV are bitwise equal to it.
 // =============================================================================================
-namespace {
-constexpr int W1_KEYS = 256;  // keys per workgroup
-}
-
 __device__ __forceinline__ uint64_t srd_half(const u32x4& d, int hi) {
   return hi ? ((uint64_t)d[3] << 32 | d[2]) : ((uint64_t)d[1] << 32 | d[0]);
 }
@@ -465,38 +461,6 @@ __global__ __launch_bounds__(256, 1) void attn_dkdv_w1_kernel(const AttnParams p
   if constexpr (V > 0) es.stop(p);
 }
 
-// LTX_ATTN_DKDV_W1 (attn_switches()): unset / 2 the persistent one-wave kernel (attn_dkdv_w1p_kernel), 1
-// one workgroup per key block (attn_dkdv_w1_kernel), 0 attn_dkdv_pipe_kernel, 12..16 / 22 the stamped
-// diagnostic variants (`make diag` builds)
-static int dkdv_w1_mode() { return attn_switches().dkdv_w1; }
-bool dkdv_w1_enabled() { return dkdv_w1_mode() != 0; }
-// LTX_ATTN_DKDV_W1=2 (22: its stamped diagnostic variant): the persistent kernel
-bool dkdv_w1p_enabled() { return dkdv_w1_mode() == 2 || dkdv_w1_mode() == 22; }
-
-int launch_dkdv_w1(const AttnParams& p, hipStream_t s) {
-  const dim3 g((unsigned)((p.Nk + W1_KEYS - 1) / W1_KEYS), (unsigned)p.H, (unsigned)p.B);
-  const int mode = dkdv_w1_mode();
-#ifdef LTX_DKDV_DIAG
-  if (mode >= 12 && mode <= 16) {  // phase stamps into the stream's workspace (8 u64 per wave)
-    AttnParams q = p;
-    size_t ws = 0;
-    q.part = stream_workspace(s, &ws);
-    if (q.part == nullptr || ws < (size_t)g.x * g.y * g.z * 4 * 12 * 8) return fail(LTX_ERR_BAD_ARG, "stamps: workspace");
-    if (mode == 12) hipLaunchKernelGGL(attn_dkdv_w1_kernel<1>, g, dim3(256), 0, s, q);
-    if (mode == 13) hipLaunchKernelGGL(attn_dkdv_w1_kernel<2>, g, dim3(256), 0, s, q);
-    if (mode == 14) hipLaunchKernelGGL(attn_dkdv_w1_kernel<3>, g, dim3(256), 0, s, q);
-    if (mode == 15) hipLaunchKernelGGL(attn_dkdv_w1_kernel<4>, g, dim3(256), 0, s, q);
-    if (mode == 16) hipLaunchKernelGGL(attn_dkdv_w1_kernel<5>, g, dim3(256), 0, s, q);
-    LTX_LAUNCH_CHECK();
-    return LTX_OK;
-  }
-#endif
-  (void)mode;
-  hipLaunchKernelGGL(attn_dkdv_w1_kernel<0>, g, dim3(256), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
-}
-
 // =============================================================================================
 // dK / dV, PERSISTENT (attn_bwd_body.h LTX_DKDV_W1P_BODY, tools/gen_attn_bwd.py dkdv_p_body): one
 // workgroup per CU walks the items L = blockIdx.x + i * gridDim.x (a 256-key block of one (batch,
@@ -504,7 +468,6 @@ int launch_dkdv_w1(const AttnParams& p, hipStream_t s) {
 // stores of item i. Per item the same loop as attn_dkdv_w1_kernel: dK / dV bitwise equal to it.
 // =============================================================================================
 namespace {
-constexpr int W1P_MAXIT = 63;  // items per workgroup (table rows, + the null row)
 constexpr int W1P_LDS = LTX_DKDV_W1P_TAB + (W1P_MAXIT + 1) * LTX_DKDV_W1P_ITEM;
 }
 
@@ -564,7 +527,7 @@ __global__ __launch_bounds__(256, 1) void attn_dkdv_w1p_kernel(const AttnParams 
   }
   __syncthreads();
   // sizes (words 2, 3) of the Q, dO and stats descriptors: the same for every item
-  // (< 4 GiB: dkdv_w1p_applies)
+  // (< 4 GiB: attn_plan.h attn_w1p_fits)
   const uint32_t sq2 = __builtin_amdgcn_readfirstlane((uint32_t)(((p.Nq - 1) * (uint32_t)p.ldq + HD) * 2));
   const uint32_t so2 = __builtin_amdgcn_readfirstlane((uint32_t)(((p.Nq - 1) * (uint32_t)p.lddo + HD) * 2));
   const uint32_t ss2 = __builtin_amdgcn_readfirstlane((uint32_t)(p.Nq * 4));
@@ -619,42 +582,6 @@ __global__ __launch_bounds__(256, 1) void attn_dkdv_w1p_kernel(const AttnParams 
 #endif
 #undef LTX_W1P_OPERANDS
   if constexpr (V > 0) es.stop(p);
-}
-
-static int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
-// the persistent kernel applies when every workgroup's items fit its table
-bool dkdv_w1p_applies(const AttnParams& p) {
-  const int64_t I = (int64_t)((p.Nk + W1_KEYS - 1) / W1_KEYS) * p.H * p.B;
-  const uint64_t span = (uint64_t)p.Nq * (uint64_t)std::max<int64_t>(p.ldq, p.lddo) * 2;  // Q / dO descriptor sizes
-  return I <= (int64_t)W1P_MAXIT * cu_count() && span < 0xffffffffull;
-}
-
-int launch_dkdv_w1p(const AttnParams& p, hipStream_t s) {
-  const int I = ((p.Nk + W1_KEYS - 1) / W1_KEYS) * p.H * p.B;
-  const dim3 g((unsigned)min(I, cu_count()));
-#ifdef LTX_DKDV_DIAG
-  if (dkdv_w1_mode() == 22) {
-    AttnParams q = p;
-    size_t ws = 0;
-    q.part = stream_workspace(s, &ws);
-    if (q.part == nullptr || ws < (size_t)g.x * 4 * 12 * 8) return fail(LTX_ERR_BAD_ARG, "stamps: workspace");
-    hipLaunchKernelGGL(attn_dkdv_w1p_kernel<1>, g, dim3(256), 0, s, q);
-    LTX_LAUNCH_CHECK();
-    return LTX_OK;
-  }
-#endif
-  hipLaunchKernelGGL(attn_dkdv_w1p_kernel<0>, g, dim3(256), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
 }
 
 // =============================================================================================
@@ -760,7 +687,6 @@ __global__ __launch_bounds__(256, 1) void attn_dq_w1_kernel(const AttnParams p) 
 // CU walks 256-query blocks as attn_dkdv_w1p_kernel walks key blocks; per block attn_dq_w1_kernel's
 // loop (dQ bitwise equal to it). bf16 dQ only (the f32 output stays on attn_dq_w1_kernel).
 // =============================================================================================
-static int dq_w1_mode();
 namespace {
 constexpr int DQP_LDS = LTX_DQ_W1P_TAB + (W1P_MAXIT + 1) * LTX_DKDV_W1P_ITEM;
 }
@@ -840,58 +766,6 @@ __global__ __launch_bounds__(256, 1) void attn_dq_w1p_kernel(const AttnParams p)
 #endif
 #undef LTX_DQP_OPERANDS
   if constexpr (V > 0) es.stop(p);
-}
-
-bool dq_w1p_applies(const AttnParams& p) {
-  const int64_t I = (int64_t)((p.Nq + 255) / 256) * p.H * p.B;
-  const uint64_t span = (uint64_t)p.Nk * (uint64_t)std::max<int64_t>(p.ldk, p.ldv) * 2;  // K / V descriptor sizes
-  return !p.dq_f32 && I <= (int64_t)W1P_MAXIT * cu_count() && span < 0xffffffffull;
-}
-
-int launch_dq_w1p(const AttnParams& p, hipStream_t s) {
-  const int I = ((p.Nq + 255) / 256) * p.H * p.B;
-  const dim3 g((unsigned)min(I, cu_count()));
-#ifdef LTX_DKDV_DIAG
-  if (dq_w1_mode() == 22) {
-    AttnParams q = p;
-    size_t ws = 0;
-    q.part = stream_workspace(s, &ws);
-    if (q.part == nullptr || ws < (size_t)g.x * 4 * 12 * 8) return fail(LTX_ERR_BAD_ARG, "stamps: workspace");
-    hipLaunchKernelGGL(attn_dq_w1p_kernel<1>, g, dim3(256), 0, s, q);
-    LTX_LAUNCH_CHECK();
-    return LTX_OK;
-  }
-#endif
-  hipLaunchKernelGGL(attn_dq_w1p_kernel<0>, g, dim3(256), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
-}
-
-// LTX_ATTN_DQ_W1 (attn_switches()): unset / 2 the persistent one-wave kernel (bf16 dQ), 1 one workgroup per
-// query block, 0 attn_dq_pipe_kernel, 12 / 13 / 22 the stamped diagnostic variants (`make diag` builds)
-static int dq_w1_mode() { return attn_switches().dq_w1; }
-bool dq_w1_enabled() { return dq_w1_mode() != 0; }
-// LTX_ATTN_DQ_W1=2 (22: its stamped diagnostic variant): the persistent kernel
-bool dq_w1p_enabled() { return dq_w1_mode() == 2 || dq_w1_mode() == 22; }
-
-int launch_dq_w1(const AttnParams& p, hipStream_t s) {
-  const dim3 g((unsigned)((p.Nq + 255) / 256), (unsigned)p.H, (unsigned)p.B);
-#ifdef LTX_DKDV_DIAG
-  const int mode = dq_w1_mode();
-  if (mode == 12 || mode == 13) {
-    AttnParams q = p;
-    size_t ws = 0;
-    q.part = stream_workspace(s, &ws);
-    if (q.part == nullptr || ws < (size_t)g.x * g.y * g.z * 4 * 12 * 8) return fail(LTX_ERR_BAD_ARG, "stamps: workspace");
-    if (mode == 12) hipLaunchKernelGGL(attn_dq_w1_kernel<1>, g, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL(attn_dq_w1_kernel<2>, g, dim3(256), 0, s, q);
-    LTX_LAUNCH_CHECK();
-    return LTX_OK;
-  }
-#endif
-  hipLaunchKernelGGL(attn_dq_w1_kernel<0>, g, dim3(256), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
 }
 
 // =============================================================================================
@@ -1118,20 +992,6 @@ __global__ __launch_bounds__(256, 2) void attn_dq_pipe_kernel(const AttnParams p
         *(u32x2*)(qrow + d * 32 + 8 * g + 4 * h) = w;
       }
   }
-}
-
-bool dq_pipe_enabled() { return attn_switches().dq_pipe != 0; }  // LTX_ATTN_DQ_PIPE=0: the plain dQ kernel
-
-static int dq_nbuf() { return attn_switches().dq_nbuf; }  // LTX_ATTN_DQ_NBUF=3: the 3-buffer ring
-
-int launch_dq_pipe(const AttnParams& p, hipStream_t s) {
-  const dim3 g((unsigned)((p.Nq + D_QUERIES - 1) / D_QUERIES), (unsigned)p.H, (unsigned)p.B);
-  if (dq_nbuf() == 4)
-    hipLaunchKernelGGL(attn_dq_pipe_kernel<4>, g, dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL(attn_dq_pipe_kernel<3>, g, dim3(256), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
 }
 
 // =============================================================================================
@@ -1382,66 +1242,23 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const AttnParams p)
   }
 }
 
-// LTX_ATTN_FWD_W1 (attn_switches(), `make fwdw1` builds only): 1 the one-wave forward where it applies; unset / 0 the pipelined
-// kernel (12: the diagnostic bodies of tools/build_fwd_variant.sh, stamps into the stream's workspace).
-// Not the default: its loop measures 2008 cycles per 64-key unit against 1024 of MFMA (1284 without
-// the softmax VALU, profiles/r05d_fwd_w1_stamps.txt) -- at two exponentials per MFMA the one-wave
-// schedule adds the VALU to the MFMA time almost linearly, and the eight-wave kernel is faster
-// (220 vs 236 us per layer at config A)
-bool fwd_w1_enabled(const AttnParams& p) {
-  const int on = attn_switches().fwd_w1;
-  return on != 0 && p.Nk % 64 == 0 && p.Nk >= 256;
-}
-
-int launch_fwd_w1(const AttnParams& p, hipStream_t s) {
-  const dim3 g((unsigned)((p.Nq + 255) / 256), (unsigned)p.H, (unsigned)p.B);
-  if (attn_switches().fwd_w1 == 12) {
-    AttnParams q = p;
-    size_t ws = 0;
-    q.part = stream_workspace(s, &ws);
-    if (q.part == nullptr || ws < (size_t)g.x * g.y * g.z * 4 * 8 * 8) return fail(LTX_ERR_BAD_ARG, "stamps: workspace");
-    hipLaunchKernelGGL(attn_fwd_w1_kernel, g, dim3(256), 0, s, q);
-    LTX_LAUNCH_CHECK();
-    return LTX_OK;
-  }
-  hipLaunchKernelGGL(attn_fwd_w1_kernel, g, dim3(256), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
-}
-
-#else
-static bool fwd_w1_enabled(const AttnParams&) { return false; }
-static int launch_fwd_w1(const AttnParams&, hipStream_t) { return LTX_OK; }
 #endif  // LTX_FWD_W1
 
-bool fwd_pipe_enabled() { return attn_switches().fwd_pipe != 0; }  // LTX_ATTN_FWD_PIPE=0: attn_q_kernel<64, 0, false, 8>
-
-static bool fwd_f32sum() { return attn_switches().fwd_f32sum != 0; }  // LTX_ATTN_FWD_F32SUM=0: v_dot2c row sums
-
-int launch_fwd_pipe(const AttnParams& p, hipStream_t s) {
-  if (fwd_w1_enabled(p)) return launch_fwd_w1(p, s);
-  const dim3 g((unsigned)((p.Nq + F_QUERIES - 1) / F_QUERIES), (unsigned)p.H, (unsigned)p.B);
-  if (fwd_f32sum())
-    hipLaunchKernelGGL(attn_fwd_pipe_kernel<true>, g, dim3(512), 0, s, p);
-  else
-    hipLaunchKernelGGL(attn_fwd_pipe_kernel<false>, g, dim3(512), 0, s, p);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
-}
-
-bool dkdv_pipe_enabled() { return attn_switches().dkdv_pipe != 0; }  // LTX_ATTN_DKDV_PIPE=0: the plain dK/dV kernel
-
-static int dkdv_nbuf() { return attn_switches().dkdv_nbuf; }  // LTX_ATTN_DKDV_NBUF=3: the 3-buffer ring
-
-int launch_dkdv_pipe(const AttnParams& p, hipStream_t s) {
-  const dim3 g((unsigned)((p.Nk + P_KEYS - 1) / P_KEYS), (unsigned)p.H, (unsigned)p.B);
-  const bool bias = p.key_bias != nullptr || (p.Nk % 64) != 0;
-  if (dkdv_nbuf() == 4) {
-    if (bias) hipLaunchKernelGGL((attn_dkdv_pipe_kernel<true, 4>), g, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((attn_dkdv_pipe_kernel<false, 4>), g, dim3(256), 0, s, p);
-  } else {
-    if (bias) hipLaunchKernelGGL((attn_dkdv_pipe_kernel<true, 3>), g, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((attn_dkdv_pipe_kernel<false, 3>), g, dim3(256), 0, s, p);
+// the launch switch over this file's kernels (attention.hip launch_kernel has the others)
+int launch_pipe_kernel(const AttnLaunch& l, const AttnParams& p, hipStream_t s) {
+  const dim3 g(l.gx, l.gy, l.gz);
+  switch (l.k) {
+#define LTX_X(id, threads, ...) \
+  case id: hipLaunchKernelGGL((__VA_ARGS__), g, dim3(threads), 0, s, p); break;
+    LTX_ATTN_KERNELS_PIPE(LTX_X)
+#ifdef LTX_FWD_W1
+    LTX_ATTN_KERNELS_FWD_W1(LTX_X)
+#endif
+#ifdef LTX_DKDV_DIAG
+    LTX_ATTN_KERNELS_DIAG(LTX_X)
+#endif
+#undef LTX_X
+    default: return fail(LTX_ERR_BAD_ARG, "attn: the plan names a kernel this build does not carry");
   }
   LTX_LAUNCH_CHECK();
   return LTX_OK;

@@ -53,6 +53,8 @@ _SIGNATURES = {
     "ltx_attn_bwd": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i32,
                      _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _p],
     "ltx_attn_reload_switches": [],
+    "ltx_attn_describe": [_i32, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _p,
+                          _p, _i64],
     "ltx_attn_bwd_ex": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p,
                         _i64, _i32, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
                         _p],
@@ -164,12 +166,14 @@ def load(path: str = None):
             fn.restype = _i32
         lib.ltx_last_error.argtypes = []
         lib.ltx_last_error.restype = ctypes.c_char_p
+        lib.ltx_attn_switch_name.argtypes = [_i32]
+        lib.ltx_attn_switch_name.restype = ctypes.c_char_p
         _lib = lib
         return lib
 
 
 def exported_symbols():
-    return list(_SIGNATURES) + ["ltx_last_error"]
+    return list(_SIGNATURES) + ["ltx_last_error", "ltx_attn_switch_name"]
 
 
 def check(rc: int, what: str):

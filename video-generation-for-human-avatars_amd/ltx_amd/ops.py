@@ -351,27 +351,52 @@ def qk_norm_bwd_grouped(dy, dy_gs, x, x_gs, weights, rstd, dx, dx_gs):
 # ---------------------------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------------------------
-def _env_on(var):
-    """A/B switch the library reads per call (attention_pipe.hip): unset or non-zero = on."""
-    v = os.environ.get(var)
-    return v is None or v.strip() not in ("0", "")
+@functools.lru_cache(maxsize=None)
+def _attn_env_names():
+    """The LTX_ATTN_* variables the library reads, from its own table (ltx_attn_switch_name)."""
+    lib, names = _lib.load(), []
+    while (name := lib.ltx_attn_switch_name(len(names))) is not None:
+        names.append(name.decode())
+    return tuple(names)
 
 
-_ATTN_ENV = ("LTX_ATTN_XCD", "LTX_ATTN_BWD1", "LTX_ATTN_W8", "LTX_ATTN_SKIP", "LTX_ATTN_FWD1",
-             "LTX_ATTN_BWD1_QS", "LTX_ATTN_BWD1_FEW", "LTX_ATTN_QSPLIT", "LTX_ATTN_DKDV_W1",
-             "LTX_ATTN_DQ_W1", "LTX_ATTN_DQ_PIPE", "LTX_ATTN_DQ_NBUF", "LTX_ATTN_FWD_W1",
-             "LTX_ATTN_FWD_PIPE", "LTX_ATTN_FWD_F32SUM", "LTX_ATTN_DKDV_PIPE", "LTX_ATTN_DKDV_NBUF",
-             "LTX_ATTN_FWD1_ROWS")
-_attn_env_seen = [None]
+def __getattr__(name):  # ops._ATTN_ENV: the library's table, read when first asked for
+    if name == "_ATTN_ENV":
+        return _attn_env_names()
+    raise AttributeError(name)
+
+
+_attn_env_seen = {}  # per loaded library: the switch values it last read
 
 
 def _attn_env_sync():
-    """The library reads its LTX_ATTN_* switches once (attention_common.h AttnSwitches); when this
-    process changed one since the last attention call (an A/B test), have it read them again."""
-    cur = tuple(os.environ.get(k) for k in _ATTN_ENV)
-    if cur != _attn_env_seen[0]:
+    """The library reads its LTX_ATTN_* switches once (attn_plan.h AttnSwitches); when this process
+    changed one since the last attention call (an A/B test), have it read them again. Returns the
+    values the library now holds."""
+    lib = _lib.load()
+    cur = tuple(os.environ.get(k) for k in _attn_env_names())
+    if cur != _attn_env_seen.get(lib):
         call("ltx_attn_reload_switches")
-        _attn_env_seen[0] = cur
+        _attn_env_seen[lib] = cur
+    return cur
+
+
+_ATTN_LABELS = {}
+
+
+def attn_kernel_label(backward, B, H, Nq, Nk, d, has_bias=False, dq_f32=False, delta_ready=False,
+                      ldq=0, ldk=0, ldv=0, lddo=0):
+    """"attention forward: " / "attention backward: " + the kernels ltx_attn_fwd / ltx_attn_bwd_ex
+    launch for this call on the current stream, as rocprofv3 names them (ltx_attn_describe: the
+    dispatcher's own plan). Cached per loaded library, stream and switch values."""
+    key = (_lib.load(), _s().value, _attn_env_sync(), backward, B, H, Nq, Nk, d, has_bias, dq_f32,
+           delta_ready, ldq, ldk, ldv, lddo)
+    if key not in _ATTN_LABELS:
+        buf = ctypes.create_string_buffer(512)
+        call("ltx_attn_describe", 1 if backward else 0, B, H, Nq, Nk, d, int(has_bias), int(dq_f32),
+             int(delta_ready), ldq or H * d, ldk or H * d, ldv or H * d, lddo or H * d, _s(), buf, 512)
+        _ATTN_LABELS[key] = ("attention backward: " if backward else "attention forward: ") + buf.value.decode()
+    return _ATTN_LABELS[key]
 
 
 def attn_fwd(q, k, v, B, H, d, scale, key_bias=None, out=None, kv_shared=False):
@@ -383,17 +408,10 @@ def attn_fwd(q, k, v, B, H, d, scale, key_bias=None, out=None, kv_shared=False):
     _gemm_workspace(q.device)  # split-query partials / diagnostic stamps use the stream's workspace
     o = torch.empty(B * Nq, H * d, dtype=BF16, device=q.device) if out is None else out
     lse = torch.empty(B, H, Nq, dtype=F32, device=q.device)
-    bias = "true" if (key_bias is not None or Nk % 64) else "false"
-    if d == 64 and Nk <= 256 and os.environ.get("LTX_ATTN_FWD1", "1") != "0":
-        label = f"attention forward: ltx::attn_fwd1_kernel<{d}, {bias}>"  # K/V staged once
-    elif d == 64 and bias == "false" and _env_on("LTX_ATTN_FWD_PIPE"):  # attention_pipe.hip
-        f32sum = "false" if os.environ.get("LTX_ATTN_FWD_F32SUM", "1")[:1] == "0" else "true"
-        label = f"attention forward: ltx::attn_fwd_pipe_kernel<{f32sum}>"
-    elif d == 64 and int(os.environ.get("LTX_ATTN_W8", "1")) & 1:  # 8 waves x 32 queries
-        label = f"attention forward: ltx::attn_q_kernel<{d}, 0, {bias}, 8>"
-    else:
-        label = f"attention forward: ltx::attn_q_kernel<{d}, 0, {bias}, 4>"
-    timer = _timer if (_timer is not None and _timer.wants(label)) else None
+    timer = _timer
+    if timer is not None:
+        label = attn_kernel_label(False, B, H, Nq, Nk, d, key_bias is not None)
+        timer = timer if timer.wants(label) else None
     ev0 = timer.start() if timer is not None else None
     call("ltx_attn_fwd", _p(q), _rows(q, "q"), _p(k), _rows(k, "k"), _p(v), _rows(v, "v"), _p(o),
          _rows(o, "o"), _p(lse), _p(key_bias), B, H, Nq, Nk, 0 if kv_shared else Nk, d, scale, _s())
@@ -421,38 +439,11 @@ def attn_bwd(q, k, v, o, do, lse, B, H, d, scale, key_bias=None, dq_f32=False, d
         assert delta.dtype == F32 and delta.is_contiguous() and delta.numel() == B * H * Nq
     else:
         delta = torch.empty(B, H, Nq, dtype=F32, device=dev)
-    bias = "true" if key_bias is not None else "false"
-    if d == 64 and Nk <= 256 and os.environ.get("LTX_ATTN_BWD1", "1") != "0":
-        # every key in one workgroup: the one-pass kernel (attention.hip attn_bwd1_kernel)
-        # the name rocprofv3 prints: <d, biased, query-split>, the split read from the same switch
-        # the library reads (attention.hip bwd1_qs_flag: on only with LTX_ATTN_BWD1_QS=1)
-        biased = key_bias is not None or Nk != 256
-        qs = "true" if (biased and os.environ.get("LTX_ATTN_BWD1_QS", "0") == "1") else "false"
-        kern = f"ltx::attn_bwd1_kernel<{d}, {'true' if biased else 'false'}, {qs}>"
-    elif d == 64 and _env_on("LTX_ATTN_DKDV_PIPE"):  # the pipelined kernels (attention_pipe.hip)
-        kb = "true" if (key_bias is not None or Nk % 64) else "false"
-        # LDS buffers of the pipelined kernels (attention_pipe.hip dq_nbuf / dkdv_nbuf: 4 unless "3")
-        nq = "3" if os.environ.get("LTX_ATTN_DQ_NBUF", "4")[:1] == "3" else "4"
-        nk = "3" if os.environ.get("LTX_ATTN_DKDV_NBUF", "4")[:1] == "3" else "4"
-        # one wave per SIMD, hand-scheduled loops (attention_pipe.hip): LTX_ATTN_DQ_W1 /
-        # LTX_ATTN_DKDV_W1 = 2 (default) the persistent kernels, 1 one workgroup per block
-        dq_mode = os.environ.get("LTX_ATTN_DQ_W1", "2").strip() or "2"
-        dk_mode = os.environ.get("LTX_ATTN_DKDV_W1", "2").strip() or "2"
-        if kb == "false" and dq_mode[:1] != "0":
-            dqk = ("ltx::attn_dq_w1p_kernel<0>" if dq_mode == "2" and dq.dtype != F32
-                   else "ltx::attn_dq_w1_kernel<0>")
-        else:
-            dqk = (f"ltx::attn_dq_pipe_kernel<{nq}>" if kb == "false" and _env_on("LTX_ATTN_DQ_PIPE")
-                   else f"ltx::attn_q_kernel<{d}, 1, {kb}, 4>")
-        if kb == "false" and dk_mode != "0":
-            dkk = "ltx::attn_dkdv_w1p_kernel<0>" if dk_mode == "2" else "ltx::attn_dkdv_w1_kernel<0>"
-            kern = f"{dkk} + {dqk}"
-        else:
-            kern = f"ltx::attn_dkdv_pipe_kernel<{kb}, {nk}> + {dqk}"
-    else:
-        kern = f"ltx::attn_dkdv_kernel<{d}, {bias}, 4> + ltx::attn_q_kernel<{d}, 1, {bias}, 4>"
-    label = ("attention backward: " + ("" if ready else f"ltx::attn_delta_kernel<{d}> + ") + kern)
-    timer = _timer if (_timer is not None and _timer.wants(label)) else None
+    timer = _timer
+    if timer is not None:
+        label = attn_kernel_label(True, B, H, Nq, Nk, d, key_bias is not None, dq.dtype == F32, ready,
+                                  _rows(q, "q"), _rows(k, "k"), _rows(v, "v"), _rows(do, "do"))
+        timer = timer if timer.wants(label) else None
     ev0 = timer.start() if timer is not None else None
     call("ltx_attn_bwd_ex", _p(q), _rows(q, "q"), _p(k), _rows(k, "k"), _p(v), _rows(v, "v"),
          _p(o), _rows(o, "o") if o is not None else 0, _p(do), _rows(do, "do"), _p(lse),
@@ -530,7 +521,7 @@ _GEMM_NAMES = {}
 
 def gemm_kernel_name(M, N, K, K2, epilogue, rank=0):
     """The kernel ltx_gemm_bf16_nt_ext launches for this call on the current stream."""
-    key = (M, N, K, K2, epilogue, rank, _s().value)
+    key = (_lib.load(), M, N, K, K2, epilogue, rank, _s().value)
     if key not in _GEMM_NAMES:
         buf = ctypes.create_string_buffer(256)
         call("ltx_gemm_describe", M, N, K, K2, EPI[epilogue], rank, _s(), buf, 256)
@@ -543,14 +534,15 @@ GEMM_WS_BYTES = 128 << 20  # split-K partials: S x M x N f32 (S=4 at 2048 x 2048
 
 
 def _gemm_workspace(device):
-    """The split-K workspace of the current stream, handed to the library once per (device,
-    stream) (caller-owned memory): the default stream's doubles as the library default, other
-    streams (the text side stream) get their own, so concurrent GEMMs never share partials."""
+    """The split-K workspace of the current stream, handed to the library once per (loaded
+    library, device, stream) (caller-owned memory): the default stream's doubles as the library
+    default, other streams (the text side stream) get their own, so concurrent GEMMs never share
+    partials; a second library loaded beside the first (an A/B build) gets its own."""
     stream = _s()
-    key = (str(device), stream.value)
+    key = (_lib.load(), str(device), stream.value)
     if key not in _GEMM_WS:
         ws = torch.empty(GEMM_WS_BYTES // 4, dtype=F32, device=device)
-        if not any(k[0] == key[0] for k in _GEMM_WS):
+        if not any(k[:2] == key[:2] for k in _GEMM_WS):
             call("ltx_gemm_set_workspace", _p(ws), GEMM_WS_BYTES)
         call("ltx_gemm_set_stream_workspace", stream, _p(ws), GEMM_WS_BYTES)
         _GEMM_WS[key] = ws
