@@ -595,6 +595,44 @@ int ltx_prodigy_apply_multi_sr(const int64_t* table, int64_t nchunks, const doub
                                double decoupled_weight_decay, int ema, float one_minus_decay, uint64_t seed,
                                int64_t step, void* stream);
 
+/* ---- the non-finite guard of the optimizer step (csrc/optim.hip, csrc/prodigy.hip, csrc/chunk_io.h) -- */
+/* A step whose gradients are not all finite is skipped on the device: it writes the guard record and
+ * nothing else. The record: 32 device bytes, 8-byte aligned, { f64 sumsq; f32 norm; f32 coef; i32 applied;
+ * i32 0; i64 skipped } -- ltx_grad_clip_coef's record in its first 16 bytes.
+ *
+ * ltx_grad_guard_record takes ltx_grad_clip_coef's place behind ltx_grad_sumsq_multi: the same fixed-order
+ * sum of part[0 .. nparts) and the same { sumsq, norm, coef } (max_norm <= 0: coef = 1), then
+ * applied = 1 when sumsq is finite, else 0 (a NaN element makes the sum NaN, an infinite one +inf or NaN,
+ * and finite f32 / bf16 elements cannot overflow f64: the test is exact), and
+ * skipped = (prev_or_null ? its skipped : 0) + (1 - applied). prev_or_null, the previous step's record, is
+ * read before out is written and may be out itself. */
+int ltx_grad_guard_record(const double* part, int64_t nparts, float max_norm, const void* prev_or_null, void* out,
+                          void* stream);
+/* ltx_adamw_multi (coef_or_null == null, ema == 0), ltx_adamw_multi_clip (coef_or_null) or
+ * ltx_adamw_multi_ema (ema != 0, on the 8-field table) behind the guard: every workgroup reads
+ * guard->applied once and returns before its first store when it is 0; when it is 1 the step is bitwise
+ * the unguarded entry point's (the same row function). coef_or_null is usually &guard->coef. */
+int ltx_adamw_multi_guard(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int64_t step, const float* coef_or_null, int ema,
+                          float one_minus_decay, const void* guard, void* stream);
+/* ltx_adamw_multi_sr behind the guard, in the same way. */
+int ltx_adamw_multi_sr_guard(const int64_t* table, int64_t nchunks, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int64_t step, const float* coef_or_null, int ema,
+                             float one_minus_decay, uint64_t seed, const void* guard, void* stream);
+/* ltx_prodigy_moments_multi behind the guard: a skipped step's pass 1 writes neither exp_avg, exp_avg_sq
+ * and s nor its row partials. */
+int ltx_prodigy_moments_multi_guard(const int64_t* table, int64_t nchunks, int is_bf16, const double* record,
+                                    double lr, double beta1, double beta2, double beta3, double d0,
+                                    double coupled_weight_decay, int use_bias_correction, int safeguard_warmup,
+                                    const float* coef_or_null, double* part, const void* guard, void* stream);
+/* ltx_prodigy_d_update behind the guard: a skipped step does not read part, sets the record's applied to 0
+ * and leaves d, d_max, d_numerator, d_denom, d_hat, dlr and k. ltx_prodigy_apply_multi and
+ * ltx_prodigy_apply_multi_sr are gated on that field already (a no-op when applied is 0), so pass 2 has no
+ * guarded entry point of its own. */
+int ltx_prodigy_d_update_guard(const double* part, int64_t nrows, double* record, double lr, double beta1,
+                               double beta2, double beta3, double d0, double d_coef, double growth_rate,
+                               int use_bias_correction, const void* guard, void* stream);
+
 /* ---- train_mode='full' parameter gradients (csrc/paramgrad.hip) --------- */
 /* Weight gradient of the q/k RMSNorm weights: partials[(which * splits + s) * D + d] (f32) =
  * sum over row split s of bf16(dn * bf16(x_raw * rstd)), dn = RoPE^T of the incoming gradient (the

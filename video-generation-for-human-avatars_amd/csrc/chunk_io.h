@@ -140,6 +140,22 @@ __device__ __forceinline__ void strided_partials_sum(const double* __restrict__ 
   }
 }
 
+// The device record of ltx_grad_guard_record (32 bytes; the host views it as four f64): the clip record's
+// three fields in the clip record's places, then the guard's own. A guarded update kernel reads `applied`
+// once per workgroup (step_applied: the same address in every lane, a uniform load) and returns before its
+// first store when it is 0, so a skipped step writes this record and nothing else.
+struct GuardRecord {
+  double sumsq;     // sum of squares of every gradient element, f64: finite iff every element is finite
+  float norm;       // (float)sqrt(sumsq): the pre-clip global norm
+  float coef;       // grad_clip_coef_kernel's coefficient; 1 without a max_norm
+  int32_t applied;  // 1 when sumsq is finite (the step runs), 0 when it is skipped
+  int32_t pad;
+  int64_t skipped;  // steps skipped so far, this one included: the previous record's count carried on
+};
+static_assert(sizeof(GuardRecord) == 32, "GuardRecord layout");
+
+__device__ __forceinline__ bool step_applied(const GuardRecord* __restrict__ guard) { return guard->applied != 0; }
+
 // host: f(std::true_type) or f(std::false_type) by a run-time flag, nested once per template parameter
 template <class F>
 static inline void with_flag(bool flag, F&& f) {

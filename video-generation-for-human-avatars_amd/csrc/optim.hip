@@ -13,7 +13,11 @@
 //   ema_swap_multi_kernel: installs the averaged weights for an evaluation or an export and puts the live
 //     ones back;
 //   adamw_multi_sr_kernel: the mixed step of a bf16 parameter with f32 moments and a stochastically rounded
-//     store (FusedAdamW(bf16_update="stochastic"), ltx_adamw_multi_sr).
+//     store (FusedAdamW(bf16_update="stochastic"), ltx_adamw_multi_sr);
+//   the non-finite guard (FusedAdamW(skip_nonfinite=True)): grad_guard_record_kernel in the coefficient
+//     kernel's place writes the wider GuardRecord (chunk_io.h) from the same partials, and
+//     adamw_multi_guard_kernel / adamw_multi_sr_guard_kernel run the row bodies of the kernels above behind
+//     one read of the record's `applied` (ltx_adamw_multi_guard, ltx_adamw_multi_sr_guard).
 // Every sum has a fixed order and there are no atomics, so the record is bitwise reproducible; nothing here
 // reads a value back to the host.
 #include <cmath>
@@ -52,23 +56,45 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const int64_t* __
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// the sum of all partials (strided_partials_sum, as sumsq_finish_kernel); the coefficient is
-// clip_coef_kernel's f32 arithmetic with inv_world = 1
+// the record of a sum of squares: the coefficient is clip_coef_kernel's f32 arithmetic with inv_world = 1
+__device__ __forceinline__ ClipRecord clip_record(double sumsq, float max_norm) {
+  const float norm = (float)sqrt(sumsq);
+  float c = 1.0f;
+  if (max_norm > 0.f) {
+    const float cc = max_norm / (norm + 1e-6f);
+    if (cc < 1.0f) c = cc;
+  }
+  return {sumsq, norm, c};
+}
+
+// the sum of all partials (strided_partials_sum, as sumsq_finish_kernel)
 __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ part, int nparts,
                                                              float max_norm, ClipRecord* __restrict__ out) {
   __shared__ double red[1][256];
   strided_partials_sum<1>(part, nparts, red);
+  if (threadIdx.x == 0) *out = clip_record(red[0][0], max_norm);
+}
+
+// grad_clip_coef_kernel's sum and record, and the guard's decision: a NaN element makes the sum NaN, an
+// infinite one +inf (or NaN), and no finite f32 or bf16 gradient set overflows f64, so the sum is finite
+// iff every element is. The test is on the exponent bits. `prev` (the last step's record, or null) carries
+// the skipped count; it is read before `out` is written, so the two may be one record.
+__global__ __launch_bounds__(256) void grad_guard_record_kernel(const double* __restrict__ part, int nparts,
+                                                                float max_norm, const GuardRecord* prev,
+                                                                GuardRecord* out) {
+  __shared__ double red[1][256];
+  strided_partials_sum<1>(part, nparts, red);
   if (threadIdx.x == 0) {
-    const double sumsq = red[0][0];
-    const float norm = (float)sqrt(sumsq);
-    float c = 1.0f;
-    if (max_norm > 0.f) {
-      const float cc = max_norm / (norm + 1e-6f);
-      if (cc < 1.0f) c = cc;
-    }
-    out->sumsq = sumsq;
-    out->norm = norm;
-    out->coef = c;
+    const ClipRecord c = clip_record(red[0][0], max_norm);
+    const uint64_t exponent = 0x7ff0000000000000ull;
+    const bool finite = ((uint64_t)__double_as_longlong(c.sumsq) & exponent) != exponent;
+    const int64_t skipped = (prev ? prev->skipped : 0) + (finite ? 0 : 1);
+    out->sumsq = c.sumsq;
+    out->norm = c.norm;
+    out->coef = c.coef;
+    out->applied = finite ? 1 : 0;
+    out->pad = 0;
+    out->skipped = skipped;
   }
 }
 
@@ -84,9 +110,9 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __res
 constexpr int EMA_ROW = 8;
 
 template <bool BF16, bool CLIP, bool EMA>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ table, float decay, float w1,
-                                                          float b2, float w2, float step_size, float bc2_sqrt,
-                                                          float eps, const float* __restrict__ coef, float omd) {
+__device__ __forceinline__ void adamw_multi_row(const int64_t* __restrict__ table, float decay, float w1, float b2,
+                                                float w2, float step_size, float bc2_sqrt, float eps,
+                                                const float* __restrict__ coef, float omd) {
   const int64_t* e = table + (int64_t)blockIdx.x * (EMA ? EMA_ROW : 6);
   void* param = (void*)e[0];
   const void* grad = (const void*)e[1];
@@ -97,6 +123,24 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
   const float c = CLIP ? *coef : 1.0f;
   for (int64_t i = start + threadIdx.x; i < end; i += 256)
     adamw_elem<BF16, CLIP, EMA>(param, grad, m, v, i, decay, w1, b2, w2, step_size, bc2_sqrt, eps, c, shadow, omd);
+}
+
+template <bool BF16, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ table, float decay, float w1,
+                                                          float b2, float w2, float step_size, float bc2_sqrt,
+                                                          float eps, const float* __restrict__ coef, float omd) {
+  adamw_multi_row<BF16, CLIP, EMA>(table, decay, w1, b2, w2, step_size, bc2_sqrt, eps, coef, omd);
+}
+
+// the same row behind the guard: a skipped step returns before the first load
+template <bool BF16, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_multi_guard_kernel(const int64_t* __restrict__ table, float decay,
+                                                                float w1, float b2, float w2, float step_size,
+                                                                float bc2_sqrt, float eps,
+                                                                const float* __restrict__ coef, float omd,
+                                                                const GuardRecord* __restrict__ guard) {
+  if (!step_applied(guard)) return;
+  adamw_multi_row<BF16, CLIP, EMA>(table, decay, w1, b2, w2, step_size, bc2_sqrt, eps, coef, omd);
 }
 
 // LOAD: stash <- param, param <- R(shadow) (R: round to nearest even to bf16 for bf16 parameters);
@@ -172,8 +216,8 @@ __device__ __forceinline__ void adamw_sr_at(const int64_t* __restrict__ e, int64
 }
 
 template <bool CLIP, bool EMA>
-__global__ __launch_bounds__(256) void adamw_multi_sr_kernel(const int64_t* __restrict__ table, AdamWSr c,
-                                                             const float* __restrict__ coef) {
+__device__ __forceinline__ void adamw_multi_sr_row(const int64_t* __restrict__ table, AdamWSr c,
+                                                   const float* __restrict__ coef) {
   const int64_t* e = table + (int64_t)blockIdx.x * SR_ROW;
   const int64_t start = e[4], count = e[5];
   if (CLIP) c.coef = *coef;
@@ -184,16 +228,55 @@ __global__ __launch_bounds__(256) void adamw_multi_sr_kernel(const int64_t* __re
               [&](auto n, int64_t i) { adamw_sr_at<CLIP, EMA, decltype(n)::value>(e, i, c); });
 }
 
-// the launch of adamw_multi_kernel<is_bf16, CLIP, EMA> behind the three nearest-mode entry points
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_multi_sr_kernel(const int64_t* __restrict__ table, AdamWSr c,
+                                                             const float* __restrict__ coef) {
+  adamw_multi_sr_row<CLIP, EMA>(table, c, coef);
+}
+
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_multi_sr_guard_kernel(const int64_t* __restrict__ table, AdamWSr c,
+                                                                   const float* __restrict__ coef,
+                                                                   const GuardRecord* __restrict__ guard) {
+  if (!step_applied(guard)) return;
+  adamw_multi_sr_row<CLIP, EMA>(table, c, coef);
+}
+
+// the launch of adamw_multi_kernel<is_bf16, CLIP, EMA> behind the three nearest-mode entry points, of
+// adamw_multi_guard_kernel behind the guarded one (guard != null)
 template <bool CLIP, bool EMA>
 static void launch_adamw_multi(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
                                float eps, float weight_decay, int64_t step, const float* coef, float omd,
-                               void* stream) {
+                               void* stream, const GuardRecord* guard = nullptr) {
   const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
   with_flag(is_bf16, [&](auto bf) {
-    hipLaunchKernelGGL((adamw_multi_kernel<decltype(bf)::value, CLIP, EMA>), dim3((unsigned)nchunks), dim3(256), 0,
-                       (hipStream_t)stream, table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef,
-                       omd);
+    if (guard)
+      hipLaunchKernelGGL((adamw_multi_guard_kernel<decltype(bf)::value, CLIP, EMA>), dim3((unsigned)nchunks),
+                         dim3(256), 0, (hipStream_t)stream, table, a.decay, a.w1, beta2, a.w2, a.step_size,
+                         a.bc2_sqrt, eps, coef, omd, guard);
+    else
+      hipLaunchKernelGGL((adamw_multi_kernel<decltype(bf)::value, CLIP, EMA>), dim3((unsigned)nchunks), dim3(256), 0,
+                         (hipStream_t)stream, table, a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, coef,
+                         omd);
+  });
+}
+
+// the launch of adamw_multi_sr_kernel<CLIP, EMA>, behind the guard when one is given
+static void launch_adamw_multi_sr(const int64_t* table, int64_t nchunks, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, int64_t step, const float* coef_or_null, int ema,
+                                  float one_minus_decay, uint64_t seed, void* stream, const GuardRecord* guard) {
+  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
+  const AdamWSr c = {a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, 1.0f, ema ? one_minus_decay : 0.f,
+                     (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)((uint64_t)step & 0xffffffffu)};
+  with_flag(coef_or_null != nullptr, [&](auto clip) {
+    with_flag(ema, [&](auto em) {
+      if (guard)
+        hipLaunchKernelGGL((adamw_multi_sr_guard_kernel<decltype(clip)::value, decltype(em)::value>),
+                           dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table, c, coef_or_null, guard);
+      else
+        hipLaunchKernelGGL((adamw_multi_sr_kernel<decltype(clip)::value, decltype(em)::value>), dim3((unsigned)nchunks),
+                           dim3(256), 0, (hipStream_t)stream, table, c, coef_or_null);
+    });
   });
 }
 
@@ -281,15 +364,51 @@ int ltx_adamw_multi_sr(const int64_t* table, int64_t nchunks, float lr, float be
   LTX_CHECK_ARG(table && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_sr: bad args");
   LTX_CHECK_ARG(!ema || (one_minus_decay >= 0.f && one_minus_decay <= 1.f),
                 "adamw_multi_sr: one_minus_decay outside [0, 1]");
-  const AdamWScalars a = adamw_scalars(lr, beta1, beta2, weight_decay, step);
-  const AdamWSr c = {a.decay, a.w1, beta2, a.w2, a.step_size, a.bc2_sqrt, eps, 1.0f, ema ? one_minus_decay : 0.f,
-                     (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)((uint64_t)step & 0xffffffffu)};
+  launch_adamw_multi_sr(table, nchunks, lr, beta1, beta2, eps, weight_decay, step, coef_or_null, ema, one_minus_decay,
+                        seed, stream, nullptr);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_grad_guard_record(const double* part, int64_t nparts, float max_norm, const void* prev_or_null, void* out,
+                          void* stream) {
+  LTX_CHECK_ARG(part && out && nparts > 0 && nparts < (1LL << 31), "grad_guard_record: bad args");
+  LTX_CHECK_ARG((((uintptr_t)out | (uintptr_t)prev_or_null) & 7) == 0,
+                "grad_guard_record: the records must be 8-byte aligned");
+  hipLaunchKernelGGL(grad_guard_record_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int)nparts, max_norm,
+                     (const GuardRecord*)prev_or_null, (GuardRecord*)out);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_adamw_multi_guard(const int64_t* table, int64_t nchunks, int is_bf16, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int64_t step, const float* coef_or_null, int ema,
+                          float one_minus_decay, const void* guard, void* stream) {
+  LTX_CHECK_ARG(table && guard && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_guard: bad args");
+  LTX_CHECK_ARG(((uintptr_t)guard & 7) == 0, "adamw_multi_guard: guard must be 8-byte aligned");
+  LTX_CHECK_ARG(!ema || (one_minus_decay >= 0.f && one_minus_decay <= 1.f),
+                "adamw_multi_guard: one_minus_decay outside [0, 1]");
   with_flag(coef_or_null != nullptr, [&](auto clip) {
     with_flag(ema, [&](auto em) {
-      hipLaunchKernelGGL((adamw_multi_sr_kernel<decltype(clip)::value, decltype(em)::value>), dim3((unsigned)nchunks),
-                         dim3(256), 0, (hipStream_t)stream, table, c, coef_or_null);
+      launch_adamw_multi<decltype(clip)::value, decltype(em)::value>(table, nchunks, is_bf16, lr, beta1, beta2, eps,
+                                                                     weight_decay, step, coef_or_null,
+                                                                     ema ? one_minus_decay : 0.f, stream,
+                                                                     (const GuardRecord*)guard);
     });
   });
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+int ltx_adamw_multi_sr_guard(const int64_t* table, int64_t nchunks, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int64_t step, const float* coef_or_null, int ema,
+                             float one_minus_decay, uint64_t seed, const void* guard, void* stream) {
+  LTX_CHECK_ARG(table && guard && nchunks > 0 && nchunks < (1LL << 31) && step >= 1, "adamw_multi_sr_guard: bad args");
+  LTX_CHECK_ARG(((uintptr_t)guard & 7) == 0, "adamw_multi_sr_guard: guard must be 8-byte aligned");
+  LTX_CHECK_ARG(!ema || (one_minus_decay >= 0.f && one_minus_decay <= 1.f),
+                "adamw_multi_sr_guard: one_minus_decay outside [0, 1]");
+  launch_adamw_multi_sr(table, nchunks, lr, beta1, beta2, eps, weight_decay, step, coef_or_null, ema, one_minus_decay,
+                        seed, stream, (const GuardRecord*)guard);
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

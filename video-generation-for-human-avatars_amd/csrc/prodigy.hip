@@ -12,6 +12,12 @@
 // Every sum has a fixed order and there are no atomics, so the record is bitwise reproducible and every
 // data-parallel rank computes the same d from the same (all-reduced) gradients.
 //
+// Behind the non-finite guard (FusedProdigy(skip_nonfinite=True); GuardRecord, chunk_io.h) pass 1 and the d
+// update run as prodigy_moments_multi_guard_kernel and prodigy_d_update_guard_kernel, the same bodies
+// behind one read of the guard's `applied`: a skipped step's pass 1 returns before its first load (its row
+// partials stay unwritten and unread), its d update sets the record's applied to 0 and leaves the other
+// seven fields, and pass 2 is then the no-op it already is under applied == 0.
+//
 // The table has 10 int64 per row: (param, grad, exp_avg, exp_avg_sq, first element, count <= 2048, s, p0,
 // shadow, ordinal); the shadow is 0 without the EMA, the ordinal 0 outside the stochastic step. A row whose
 // tensors are all 16-byte aligned is walked with 16-byte accesses (4 f32 or 8 bf16 per lane, the row's last
@@ -97,10 +103,9 @@ __device__ __forceinline__ void moments_at(const ProdigyRow& r, int64_t i, const
 }
 
 template <bool PBF, bool SBF, bool CLIP, bool COUPLED>
-__global__ __launch_bounds__(256) void prodigy_moments_multi_kernel(const int64_t* __restrict__ table,
-                                                                    const ProdigyRecord* __restrict__ rec,
-                                                                    ProdigyHyper h, const float* __restrict__ coef,
-                                                                    double* __restrict__ part) {
+__device__ __forceinline__ void prodigy_moments_row(const int64_t* __restrict__ table,
+                                                    const ProdigyRecord* __restrict__ rec, const ProdigyHyper& h,
+                                                    const float* __restrict__ coef, double* __restrict__ part) {
   const ProdigyRow r = prodigy_row(table, true, false);
   const double d = rec->d;
   const double dlr = prodigy_dlr(d, rec->k, h.lr, h.beta1, h.beta2, h.use_bias_correction);
@@ -126,11 +131,30 @@ __global__ __launch_bounds__(256) void prodigy_moments_multi_kernel(const int64_
   }
 }
 
+template <bool PBF, bool SBF, bool CLIP, bool COUPLED>
+__global__ __launch_bounds__(256) void prodigy_moments_multi_kernel(const int64_t* __restrict__ table,
+                                                                    const ProdigyRecord* __restrict__ rec,
+                                                                    ProdigyHyper h, const float* __restrict__ coef,
+                                                                    double* __restrict__ part) {
+  prodigy_moments_row<PBF, SBF, CLIP, COUPLED>(table, rec, h, coef, part);
+}
+
+template <bool PBF, bool SBF, bool CLIP, bool COUPLED>
+__global__ __launch_bounds__(256) void prodigy_moments_multi_guard_kernel(const int64_t* __restrict__ table,
+                                                                          const ProdigyRecord* __restrict__ rec,
+                                                                          ProdigyHyper h,
+                                                                          const float* __restrict__ coef,
+                                                                          double* __restrict__ part,
+                                                                          const GuardRecord* __restrict__ guard) {
+  if (!step_applied(guard)) return;
+  prodigy_moments_row<PBF, SBF, CLIP, COUPLED>(table, rec, h, coef, part);
+}
+
 // part holds (num, den) pairs, one per row, summed in a fixed order (strided_partials_sum, as
 // grad_clip_coef_kernel); thread 0 runs the update.
-__global__ __launch_bounds__(256) void prodigy_d_update_kernel(const double* __restrict__ part, int nrows,
-                                                               ProdigyRecord* __restrict__ rec, ProdigyHyper h,
-                                                               double d_coef, double growth_rate) {
+__device__ __forceinline__ void prodigy_d_update_block(const double* __restrict__ part, int nrows,
+                                                       ProdigyRecord* __restrict__ rec, const ProdigyHyper& h,
+                                                       double d_coef, double growth_rate) {
   __shared__ double red[2][256];
   strided_partials_sum<2>(part, nrows, red);
   if (threadIdx.x == 0) {
@@ -155,6 +179,24 @@ __global__ __launch_bounds__(256) void prodigy_d_update_kernel(const double* __r
       rec->applied = 1.0;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void prodigy_d_update_kernel(const double* __restrict__ part, int nrows,
+                                                               ProdigyRecord* __restrict__ rec, ProdigyHyper h,
+                                                               double d_coef, double growth_rate) {
+  prodigy_d_update_block(part, nrows, rec, h, d_coef, growth_rate);
+}
+
+// a skipped step: applied = 0, which makes pass 2 a no-op; d, d_max, d_numerator, d_denom, d_hat, dlr and k stay
+__global__ __launch_bounds__(256) void prodigy_d_update_guard_kernel(const double* __restrict__ part, int nrows,
+                                                                     ProdigyRecord* __restrict__ rec, ProdigyHyper h,
+                                                                     double d_coef, double growth_rate,
+                                                                     const GuardRecord* __restrict__ guard) {
+  if (!step_applied(guard)) {
+    if (threadIdx.x == 0) rec->applied = 0.0;
+    return;
+  }
+  prodigy_d_update_block(part, nrows, rec, h, d_coef, growth_rate);
 }
 
 // the stream of a row's stochastic rounding (the mixed step only)
@@ -222,28 +264,30 @@ static void launch_prodigy_apply(const int64_t* table, int64_t nchunks, const do
   });
 }
 
-}  // namespace ltx
-
-using namespace ltx;
-
-extern "C" {
-
-int ltx_prodigy_moments_multi(const int64_t* table, int64_t nchunks, int is_bf16, const double* record, double lr,
-                              double beta1, double beta2, double beta3, double d0, double coupled_weight_decay,
-                              int use_bias_correction, int safeguard_warmup, const float* coef_or_null, double* part,
-                              void* stream) {
+// pass 1 in the storage types of is_bf16 (0 f32, 1 bf16, 2 mixed), behind the guard when one is given
+static int launch_prodigy_moments(const int64_t* table, int64_t nchunks, int is_bf16,
+                                  const double* record, double lr, double beta1, double beta2, double beta3, double d0,
+                                  double coupled_weight_decay, int use_bias_correction, int safeguard_warmup,
+                                  const float* coef_or_null, double* part, const GuardRecord* guard, void* stream) {
   LTX_CHECK_ARG(table && record && part && nchunks > 0 && nchunks < (1LL << 31), "prodigy_moments_multi: bad args");
-  LTX_CHECK_ARG((((uintptr_t)record | (uintptr_t)part) & 7) == 0, "prodigy_moments_multi: record and part must be 8-byte aligned");
+  LTX_CHECK_ARG((((uintptr_t)record | (uintptr_t)part | (uintptr_t)guard) & 7) == 0,
+                "prodigy_moments_multi: record, part and guard must be 8-byte aligned");
   LTX_CHECK_ARG(d0 > 0.0, "prodigy_moments_multi: d0 must be > 0");
   const ProdigyHyper h = {lr, beta1, beta2, beta3, d0, coupled_weight_decay, use_bias_correction, safeguard_warmup};
   LTX_CHECK_ARG(is_bf16 >= 0 && is_bf16 <= 2, "prodigy_moments_multi: is_bf16 is 0 (f32), 1 (bf16) or 2 (mixed)");
   auto launch = [&](auto pbf, auto sbf) {
     with_flag(coef_or_null != nullptr, [&](auto clip) {
       with_flag(coupled_weight_decay != 0.0, [&](auto coupled) {
-        hipLaunchKernelGGL((prodigy_moments_multi_kernel<decltype(pbf)::value, decltype(sbf)::value,
-                                                         decltype(clip)::value, decltype(coupled)::value>),
-                           dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
-                           (const ProdigyRecord*)record, h, coef_or_null, part);
+        if (guard)
+          hipLaunchKernelGGL((prodigy_moments_multi_guard_kernel<decltype(pbf)::value, decltype(sbf)::value,
+                                                                 decltype(clip)::value, decltype(coupled)::value>),
+                             dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
+                             (const ProdigyRecord*)record, h, coef_or_null, part, guard);
+        else
+          hipLaunchKernelGGL((prodigy_moments_multi_kernel<decltype(pbf)::value, decltype(sbf)::value,
+                                                           decltype(clip)::value, decltype(coupled)::value>),
+                             dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, table,
+                             (const ProdigyRecord*)record, h, coef_or_null, part);
       });
     });
   };
@@ -254,17 +298,63 @@ int ltx_prodigy_moments_multi(const int64_t* table, int64_t nchunks, int is_bf16
   return LTX_OK;
 }
 
+// the d update, behind the guard when one is given
+static int launch_prodigy_d_update(const double* part, int64_t nrows, double* record, double lr, double beta1,
+                                   double beta2, double beta3, double d0, double d_coef, double growth_rate,
+                                   int use_bias_correction, const GuardRecord* guard, void* stream) {
+  LTX_CHECK_ARG(part && record && nrows > 0 && nrows < (1LL << 31), "prodigy_d_update: bad args");
+  LTX_CHECK_ARG((((uintptr_t)record | (uintptr_t)part | (uintptr_t)guard) & 7) == 0,
+                "prodigy_d_update: record, part and guard must be 8-byte aligned");
+  LTX_CHECK_ARG(d0 > 0.0, "prodigy_d_update: d0 must be > 0");
+  const ProdigyHyper h = {lr, beta1, beta2, beta3, d0, 0.0, use_bias_correction, 0};
+  if (guard)
+    hipLaunchKernelGGL(prodigy_d_update_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int)nrows,
+                       (ProdigyRecord*)record, h, d_coef, growth_rate, guard);
+  else
+    hipLaunchKernelGGL(prodigy_d_update_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int)nrows,
+                       (ProdigyRecord*)record, h, d_coef, growth_rate);
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
+
+}  // namespace ltx
+
+using namespace ltx;
+
+extern "C" {
+
+int ltx_prodigy_moments_multi(const int64_t* table, int64_t nchunks, int is_bf16, const double* record, double lr,
+                              double beta1, double beta2, double beta3, double d0, double coupled_weight_decay,
+                              int use_bias_correction, int safeguard_warmup, const float* coef_or_null, double* part,
+                              void* stream) {
+  return launch_prodigy_moments(table, nchunks, is_bf16, record, lr, beta1, beta2, beta3, d0,
+                                coupled_weight_decay, use_bias_correction, safeguard_warmup, coef_or_null, part,
+                                nullptr, stream);
+}
+
+int ltx_prodigy_moments_multi_guard(const int64_t* table, int64_t nchunks, int is_bf16, const double* record,
+                                    double lr, double beta1, double beta2, double beta3, double d0,
+                                    double coupled_weight_decay, int use_bias_correction, int safeguard_warmup,
+                                    const float* coef_or_null, double* part, const void* guard, void* stream) {
+  LTX_CHECK_ARG(guard, "prodigy_moments_multi_guard: guard is null");
+  return launch_prodigy_moments(table, nchunks, is_bf16, record, lr, beta1, beta2,
+                                beta3, d0, coupled_weight_decay, use_bias_correction, safeguard_warmup, coef_or_null,
+                                part, (const GuardRecord*)guard, stream);
+}
+
 int ltx_prodigy_d_update(const double* part, int64_t nrows, double* record, double lr, double beta1, double beta2,
                          double beta3, double d0, double d_coef, double growth_rate, int use_bias_correction,
                          void* stream) {
-  LTX_CHECK_ARG(part && record && nrows > 0 && nrows < (1LL << 31), "prodigy_d_update: bad args");
-  LTX_CHECK_ARG((((uintptr_t)record | (uintptr_t)part) & 7) == 0, "prodigy_d_update: record and part must be 8-byte aligned");
-  LTX_CHECK_ARG(d0 > 0.0, "prodigy_d_update: d0 must be > 0");
-  const ProdigyHyper h = {lr, beta1, beta2, beta3, d0, 0.0, use_bias_correction, 0};
-  hipLaunchKernelGGL(prodigy_d_update_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int)nrows,
-                     (ProdigyRecord*)record, h, d_coef, growth_rate);
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
+  return launch_prodigy_d_update(part, nrows, record, lr, beta1, beta2, beta3, d0, d_coef, growth_rate,
+                                 use_bias_correction, nullptr, stream);
+}
+
+int ltx_prodigy_d_update_guard(const double* part, int64_t nrows, double* record, double lr, double beta1,
+                               double beta2, double beta3, double d0, double d_coef, double growth_rate,
+                               int use_bias_correction, const void* guard, void* stream) {
+  LTX_CHECK_ARG(guard, "prodigy_d_update_guard: guard is null");
+  return launch_prodigy_d_update(part, nrows, record, lr, beta1, beta2, beta3, d0, d_coef, growth_rate,
+                                 use_bias_correction, (const GuardRecord*)guard, stream);
 }
 
 int ltx_prodigy_apply_multi(const int64_t* table, int64_t nchunks, int is_bf16, const double* record, double eps,

@@ -120,6 +120,13 @@ _SIGNATURES = {
     "ltx_prodigy_d_update": [_p, _i64, _p, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p],
     "ltx_prodigy_apply_multi": [_p, _i64, _i32, _p, _f64, _f64, _i32, _f32, _p],
     "ltx_prodigy_apply_multi_sr": [_p, _i64, _p, _f64, _f64, _i32, _f32, ctypes.c_uint64, _i64, _p],
+    "ltx_grad_guard_record": [_p, _i64, _f32, _p, _p, _p],
+    "ltx_adamw_multi_guard": [_p, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _p, _i32, _f32, _p, _p],
+    "ltx_adamw_multi_sr_guard": [_p, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _p, _i32, _f32, ctypes.c_uint64, _p,
+                                 _p],
+    "ltx_prodigy_moments_multi_guard": [_p, _i64, _i32, _p, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _i32, _p, _p,
+                                        _p, _p],
+    "ltx_prodigy_d_update_guard": [_p, _i64, _p, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p, _p],
     "ltx_qk_norm_wgrad": [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _p, _p, _p, _i64,
                           _i64, _i64, _i64, _i32, _i64, _p, _p],
     "ltx_group_colsum": [_p, _i64, _p, _i64, _p, _p, _i32, _i64, _i64, _i64, _i64, _p, _p],

@@ -186,4 +186,11 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
         setattr(config, "bf16_update", str(t["bf16_update"]))
     if "bf16_sr_seed" in t:
         setattr(config, "bf16_sr_seed", t["bf16_sr_seed"])
+    # and the two keys training.guard_from_config reads (and validates; the values are passed on as
+    # written, so a string or a fraction is refused there): `train.skip_nonfinite` (a bool, absent =
+    # false): the optimizer skips, on the device, every step whose gradients are not all finite;
+    # `train.max_consecutive_skips` (an integer >= 0, absent or 0 = no limit)
+    for key in ("skip_nonfinite", "max_consecutive_skips"):
+        if key in t:
+            setattr(config, key, t[key])
     return config

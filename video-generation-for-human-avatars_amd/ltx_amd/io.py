@@ -362,6 +362,11 @@ def _write_json(path, obj):
 _PRODIGY_STATE = ("s", "p0")
 
 
+def _is_guarded(optimizer):
+    """an optimizer whose parameter groups carry skip_nonfinite (training.FusedAdamW(skip_nonfinite=True))"""
+    return optimizer is not None and any(g.get("skip_nonfinite", False) for g in optimizer.param_groups)
+
+
 def _is_prodigy(optimizer):
     """training.FusedProdigy (or a subclass), without importing training here"""
     return optimizer is not None and hasattr(optimizer, "RECORD") and hasattr(optimizer, "ensure_record")
@@ -395,6 +400,11 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
     "record": the device record's float64 values as float.hex() strings}. A directory written with another
     optimizer has neither.
 
+    An optimizer that guards (FusedAdamW(skip_nonfinite=True)) is settled first (the last step's outcome is
+    waited for, so a skipped step's counters are rolled back before they are read); `skip_nonfinite` is among
+    its hyper-parameters and train_state.json gains the block "guard": {"skipped_steps": the count}. A
+    directory written without the guard has neither.
+
     Everything is written under `path`.tmp and moved into place with os.replace, so a checkpoint is
     complete or absent. Under torch.distributed every rank calls this (the RNG states are gathered);
     rank 0 writes."""
@@ -407,6 +417,8 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
     if getattr(optimizer, "_ema_swapped", None) is not None:
         raise RuntimeError("save_adapter_checkpoint: the optimizer's EMA weights are swapped in; the model "
                            "holds the averages, not the trained weights")
+    if hasattr(optimizer, "settle"):
+        optimizer.settle()  # every rank: a skipped last step leaves no trace in the host's counters
     # the one collective, before rank 0 goes its own way
     rng = _gathered_rng_states(_model_device(model)) if optimizer is not None else None
     if rank != 0:
@@ -443,6 +455,8 @@ def save_adapter_checkpoint(model, path, *, optimizer=None, train_state=None, lo
             record = optimizer.ensure_record(_model_device(model)).tolist()
             state["prodigy"] = {"hyper": optimizer.hyper(),
                                 "record": {k: float(v).hex() for k, v in zip(optimizer.RECORD, record)}}
+        if _is_guarded(optimizer):
+            state["guard"] = {"skipped_steps": int(optimizer.skipped_steps)}
     ema_tensors = None
     schedule = getattr(optimizer, "ema", None)
     if schedule is not None:
@@ -555,7 +569,11 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
 
     The moments come back in their stored dtype -- f32 for a bf16 parameter of an optimizer with
     bf16_update="stochastic". ValueError, before anything is written, when the directory was written in the
-    other bf16_update mode or with another sr_seed than the live optimizer's."""
+    other bf16_update mode or with another sr_seed than the live optimizer's.
+
+    An optimizer that guards (FusedAdamW(skip_nonfinite=True)) gets the skipped count of the "guard" block
+    back, on the host and in its device record. ValueError, before anything is written, when the directory
+    was written with the guard and the live optimizer has none, or the reverse."""
     from safetensors.torch import load_file
 
     from . import ops
@@ -583,6 +601,8 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
             raise ValueError(f"{path}: holds no EMA weights ({ADAPTER_EMA})")
     if getattr(optimizer, "_ema_swapped", None) is not None:
         raise RuntimeError("load_adapter_checkpoint: the optimizer's EMA weights are swapped in")
+    if hasattr(optimizer, "settle"):
+        optimizer.settle()  # a pending rollback belongs to the counters of before the restore
     fname = ADAPTER_EMA if weights == "ema" else ADAPTER_WEIGHTS
     tensors = load_file(os.path.join(path, fname))
     # the optimizer's EMA: (saved shadows or None, ema_steps) once the checks below have passed
@@ -606,6 +626,7 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
             raise ValueError(f"{path}: holds no optimizer state")
         _check_prodigy(path, optimizer, state)
         _check_bf16_update(path, optimizer, state)
+        _check_guard(path, optimizer, state)
         opt_tensors = load_file(os.path.join(path, ADAPTER_OPTIMIZER))
     want = (list(config["target_modules"]), block["groups"])
     have = _adapter_layout(model)
@@ -656,6 +677,8 @@ def load_adapter_checkpoint(model, path, *, optimizer=None, loader=None, strict=
                            state.get("prodigy"))
         if ema_plan is not None:
             _restore_ema(optimizer, plan, *ema_plan)
+        if _is_guarded(optimizer):
+            optimizer.restore_skipped_steps(state["guard"]["skipped_steps"], _model_device(model))
     if loader is not None and "loader" in state and hasattr(loader, "seed"):
         loader.seed = state["loader"]["seed"]
     if state.get("best_loss") is None:
@@ -695,6 +718,20 @@ def _check_bf16_update(path, optimizer, state):
         if have[1] != want[1]:
             raise ValueError(f"{path}: parameter group {i} was saved with sr_seed {want[1]}, the live "
                              f"optimizer's is {have[1]}")
+
+
+def _check_guard(path, optimizer, state):
+    """ValueError when the checkpoint was written with the non-finite guard (skip_nonfinite among the
+    hyper-parameters, a "guard" block) and the live optimizer has none, or the reverse: the run that wrote it
+    would not be the run that continues."""
+    saved = state["optimizer"].get("param_groups") or []
+    want = any(h.get("skip_nonfinite", False) for h in saved) or "guard" in state
+    have = _is_guarded(optimizer)
+    if want != have:
+        raise ValueError(f"{path}: was saved {'with' if want else 'without'} skip_nonfinite, the live optimizer "
+                         f"runs {'with' if have else 'without'} it")
+    if want and not isinstance((state.get("guard") or {}).get("skipped_steps"), int):
+        raise ValueError(f"{path}: saved with skip_nonfinite but holds no guard.skipped_steps count")
 
 
 def _optimizer_plan(path, optimizer, named, saved, opt_tensors, rank, strict):

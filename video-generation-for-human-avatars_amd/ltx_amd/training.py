@@ -247,6 +247,35 @@ def ema_from_config(config):
     return EMASchedule(decay, **kw)
 
 
+def guard_from_config(config):
+    """(skip_nonfinite, max_consecutive_skips or None) from the optional config keys (setattr, or
+    train.<key> in the YAML; not TrainConfig fields): `skip_nonfinite` (a bool; absent or false: off, and
+    the run is today's) makes FusedAdamW / FusedProdigy skip, on the device, every optimizer step whose
+    gradients are not all finite; `max_consecutive_skips` (an int >= 0; absent or 0: no limit) makes
+    train_one_epoch raise FloatingPointError once more steps than that were skipped in a row. ValueError for
+    a value that is not a bool / not an integer >= 0 and for the limit without the guard;
+    NotImplementedError outside train_mode 'lora_audio' or with use_deepspeed (the sharded Zero2AdamW step
+    is its own path)."""
+    on = getattr(config, "skip_nonfinite", None)
+    limit = getattr(config, "max_consecutive_skips", None)
+    if on is not None and not isinstance(on, bool):
+        raise ValueError(f"skip_nonfinite must be a bool, got {on!r}")
+    if limit is not None:
+        if isinstance(limit, bool) or not isinstance(limit, int) or limit < 0:
+            raise ValueError(f"max_consecutive_skips must be an integer >= 0, got {limit!r}")
+        if not on:
+            raise ValueError("max_consecutive_skips set without skip_nonfinite: true")
+    if not on:
+        return False, None
+    train_mode = getattr(config, "train_mode", "full")
+    if train_mode != "lora_audio" or getattr(config, "use_deepspeed", False):
+        raise NotImplementedError(f"skip_nonfinite with train_mode={train_mode!r}, use_deepspeed="
+                                  f"{bool(getattr(config, 'use_deepspeed', False))}: the guard rides the step of "
+                                  f"FusedAdamW and FusedProdigy, which step the lora_audio trainable set; the "
+                                  f"sharded Zero2AdamW path has none")
+    return True, (limit or None)
+
+
 BF16_UPDATES = ("nearest", "stochastic")
 
 
@@ -402,12 +431,28 @@ class FusedAdamW(torch.optim.Optimizer):
     param_groups[*]["params"], its state["step"], the element) -- through ltx_adamw_multi_sr, always the
     table kernels; the bf16 tensor stays the only copy of the weight, and the EMA shadow follows the value
     stored. f32 parameters are stepped bitwise as without the mode. The two values enter param_groups (and
-    with them a checkpoint's train_state.json) in stochastic mode only."""
+    with them a checkpoint's train_state.json) in stochastic mode only.
+
+    `skip_nonfinite` (False: today's step, call for call): a step whose gradients are not all finite is the
+    step that was never called. Every step takes the global f64 sum of squares of the gradients it is about
+    to use (the clip's norm pass; without max_grad_norm the guard adds it), which is finite iff every element
+    is; ltx_grad_guard_record writes the decision into a 32-byte device record beside the norm and the
+    coefficient, and the update launches (ltx_adamw_multi_guard, ltx_adamw_multi_sr_guard) read it and return
+    before their first store, so a skipped step writes nothing but that record -- no parameter, moment or
+    shadow, no stochastically rounded store -- and nothing syncs. Always the table kernels. The host's counts
+    (state["step"], ema_steps, ema_decay) are put back lagged: the step leaves a 16-byte copy of its outcome
+    on the way to pinned memory and an event behind it, and the next step() -- or settle(), which state_dict,
+    ema_swap_in and io.save_adapter_checkpoint call -- waits for that event and undoes the skipped step's
+    increments. After a guarded step `step_applied` is a 0-dim int32 device tensor (1 or 0), `grad_norm` the
+    pre-clip norm also without max_grad_norm, `clip_coef` as above when clipping; `skipped_steps` (a Python
+    int, settles first) counts the skipped steps and `consecutive_skips` those since the last applied one.
+    The value enters param_groups only when on."""
 
     CHUNK = 2048  # elements per block of the multi-tensor kernel
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 multi_tensor=True, max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0):
+                 multi_tensor=True, max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0,
+                 skip_nonfinite=False):
         if max_grad_norm is not None and not float(max_grad_norm) >= 0:
             raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
         if ema is not None and not isinstance(ema, EMASchedule):
@@ -416,6 +461,8 @@ class FusedAdamW(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         if self.bf16_update == "stochastic":
             defaults.update(bf16_update=self.bf16_update, sr_seed=self.sr_seed)
+        if skip_nonfinite:
+            defaults.update(skip_nonfinite=True)
         super().__init__(params, defaults)
         self.multi_tensor = multi_tensor
         self._tables = []  # pinned host tables of the last two builds (alive until their H2D lands)
@@ -428,6 +475,75 @@ class FusedAdamW(torch.optim.Optimizer):
         self.ema_decay = None  # the last step's decay (a Python float)
         self._ema_stash = {}  # parameter -> the buffer its live value waits in while swapped in
         self._ema_swapped = None  # the (device table, rows, is_bf16) launches of the swap-in to undo
+        # the non-finite guard: the last guarded step's flag (a 0-dim int32 device tensor), the device record
+        # that carries the skipped count, the pinned host slot its outcome is copied to, and what settle()
+        # needs to undo the host's counting of a step that turns out skipped
+        self.step_applied = None
+        self.consecutive_skips = 0  # skipped steps since the last applied one, as far as settled
+        self._guard_rec = None  # the last step's 32-byte record (4 f64), or a restored count's
+        self._guard_slot = None  # pinned int64[2]: applied (with the zero pad behind it), skipped
+        self._guard_pending = None  # (event, states incremented, (ema_steps, ema_decay) before the tick or None)
+        self._skipped_steps = 0  # the settled count
+
+    def _skip_nonfinite(self):
+        vals = {bool(g.get("skip_nonfinite", False)) for g in self.param_groups}
+        if len(vals) > 1:
+            raise ValueError("skip_nonfinite differs between parameter groups: the decision is global, over every "
+                             "gradient of the step")
+        return vals.pop() if vals else False
+
+    def settle(self):
+        """Wait for the last guarded step's outcome (an event recorded behind a 16-byte copy into pinned host
+        memory: the step's own work, not the queue behind it) and, when that step was skipped, put the host's
+        counters back where they were before it: every incremented state["step"], ema_steps, ema_decay. step()
+        calls this first, so does everything that reads those counters (state_dict, ema_swap_in,
+        io.save_adapter_checkpoint). Without a pending outcome it does nothing."""
+        pending = self._guard_pending
+        if pending is None:
+            return
+        self._guard_pending = None
+        event, touched, ema_before = pending
+        event.synchronize()
+        applied = int(self._guard_slot[0])
+        self._skipped_steps = int(self._guard_slot[1])
+        if applied:
+            self.consecutive_skips = 0
+            return
+        self.consecutive_skips += 1
+        for st in touched:
+            st["step"] -= 1
+        if ema_before is not None:
+            self.ema_steps, self.ema_decay = ema_before
+
+    @property
+    def outcome_pending(self):
+        """True while the last guarded step's outcome has not been settled."""
+        return self._guard_pending is not None
+
+    @property
+    def skipped_steps(self):
+        """Steps skipped for non-finite gradients so far (a Python int; settles first)."""
+        self.settle()
+        return self._skipped_steps
+
+    def _guard_record(self, device):
+        """The record the next guarded step reads the skipped count from: the last step's, or a zeroed one."""
+        if self._guard_rec is None or self._guard_rec.device != device:
+            self._guard_rec = torch.zeros(4, dtype=torch.float64, device=device)
+            self._guard_rec[3:].view(torch.int64).fill_(self._skipped_steps)
+        return self._guard_rec
+
+    def restore_skipped_steps(self, count, device):
+        """A checkpoint's skipped count, on the host and in a fresh device record (io.load_adapter_checkpoint,
+        which settles before it restores anything)."""
+        self._skipped_steps = int(count)
+        self.consecutive_skips = 0
+        self._guard_rec = None
+        self._guard_record(torch.device(device))
+
+    def state_dict(self):
+        self.settle()
+        return super().state_dict()
 
     def _max_grad_norm(self):
         vals = {float(g.get("max_grad_norm") or 0.0) for g in self.param_groups}
@@ -455,10 +571,14 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._ema_swapped is not None:
             raise RuntimeError(f"{type(self).__name__}.step() while the EMA weights are swapped in: call "
                                f"ema_swap_out() first")
+        guard = self._skip_nonfinite()
+        if guard:
+            self.settle()  # before any counter is read: the last step may not have happened
         max_norm = self._max_grad_norm()
         if self._step_without_tables(max_norm):
             return
         device = self._check_params(*self._names(max_norm))
+        touched = []  # under the guard: the states this step increments
         ema, sr = self.ema, self.bf16_update == "stochastic"
         ordinals = self._ordinals() if sr else None
         last_key, by_step = self._LAST_STATE_KEY, self._BUCKET_BY_STEP
@@ -478,6 +598,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 if last_key not in st or (ema is not None and "ema" not in st):
                     self._make_state(p, st, mixed)
                 st["step"] += 1
+                if guard:
+                    touched.append(st)
                 # the step count is part of a mixed bucket's rounding counter
                 key = (kind, st["step"]) if (by_step or mixed) else kind
                 buckets.setdefault(key, []).append((p, g.contiguous(), st))
@@ -491,25 +613,34 @@ class FusedAdamW(torch.optim.Optimizer):
                 dev, nrows = self._items_table(layout, (kind, gi, j), items, ordinals)
                 # the norm kernel walks 6-field rows and reads the gradient, first element and count only
                 norm = dev if layout == "adamw" else None
-                if max_norm > 0 and norm is None:
+                if (max_norm > 0 or guard) and norm is None:
                     norm = self._items_table("adamw", (kind, gi, j), items)[0]
                 launches.append(_Launch(dev, nrows, 2 if kind == "sr" else 1 if kind is torch.bfloat16 else 0, group,
                                         step, norm))
         if launches:
             self._ready(device)
+        ema_before = (self.ema_steps, self.ema_decay) if ema is not None else None
         omd = self._ema_tick() if (launches or self._EMPTY_STEP_TICKS) else None
         if not launches:
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            self.clip_sumsq = self.grad_norm = self.clip_coef = self.step_applied = None
             return
         stream = ops._s()
-        coef = self._clip_pass(launches, max_norm, device, stream)
-        self._launch(launches, coef, omd, device, stream)
+        if not guard:
+            self.step_applied = None
+            coef = self._clip_pass(launches, max_norm, device, stream)
+            self._launch(launches, coef, omd, device, stream)
+        else:
+            coef, rec = self._guard_pass(launches, max_norm, device, stream)
+            self._launch(launches, coef, omd, device, stream, ops._p(rec))
+            self._guard_outcome(rec, touched, ema_before)
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
     def _names(self, max_norm):
         """(what, kernels, sums) of _check_params' messages"""
         if max_norm > 0:
             return "FusedAdamW(max_grad_norm)", "clip kernels", "the global norm"
+        if self._skip_nonfinite():
+            return "FusedAdamW(skip_nonfinite)", "guard kernels", "the global norm"
         if self.ema is not None:
             return "FusedAdamW(ema)", "EMA kernels", "the global norm"
         return "FusedAdamW(bf16_update)", "stochastic-rounding kernels", "the global norm"
@@ -564,39 +695,84 @@ class FusedAdamW(torch.optim.Optimizer):
         return 1.0 - self.ema_decay
 
     def _clip_pass(self, launches, max_norm, device, stream):
-        """With max_norm > 0 the norm launches of all buckets (each writes its per-row partials behind the
-        previous bucket's) and the coefficient launch; sets clip_sumsq / grad_norm / clip_coef and returns
-        the coefficient's pointer. Otherwise clears the three and returns None."""
+        """With max_norm > 0 the norm launches of all buckets and the coefficient launch; sets clip_sumsq /
+        grad_norm / clip_coef and returns the coefficient's pointer. Otherwise clears the three and returns
+        None."""
         if not max_norm > 0:
             self.clip_sumsq = self.grad_norm = self.clip_coef = None
             return None
-        total = sum(l.nrows for l in launches)
-        if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
-            self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
-        part = self._clip_part
+        part, total = self._norm_partials(launches, device, stream)
         # the record {f64 sumsq, f32 norm, f32 coef}: a fresh one per step, so a norm somebody holds keeps
         # its value
         rec = torch.empty(2, dtype=torch.float64, device=device)
         tail = rec[1:].view(torch.float32)
+        ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
+        self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
+        return ops._p(tail[1])
+
+    def _norm_partials(self, launches, device, stream):
+        """The norm launches of all buckets, each writing its per-row partials behind the previous bucket's;
+        returns (the partials, how many)."""
+        total = sum(l.nrows for l in launches)
+        if self._clip_part is None or self._clip_part.numel() < total or self._clip_part.device != device:
+            self._clip_part = torch.empty(total, dtype=torch.float64, device=device)
+        part = self._clip_part
         off = 0
         for _, nrows, mode, _, _, norm_table in launches:
             ops.call("ltx_grad_sumsq_multi", ops._p(norm_table), nrows, 1 if mode else 0,
                      ctypes.c_void_p(part.data_ptr() + 8 * off), stream)
             off += nrows
-        ops.call("ltx_grad_clip_coef", ops._p(part), total, float(max_norm), ops._p(rec), stream)
-        self.clip_sumsq, self.grad_norm, self.clip_coef = rec[0], tail[0], tail[1]
-        return ops._p(tail[1])
+        return part, total
 
-    def _launch(self, launches, coef, omd, device, stream):
+    def _guard_pass(self, launches, max_norm, device, stream):
+        """_clip_pass under the guard: the norm launches run with or without max_norm, and
+        ltx_grad_guard_record in the coefficient launch's place writes the 32-byte guard record (the clip's
+        record, then applied and the skipped count carried on from the last step's record). Sets clip_sumsq,
+        grad_norm and step_applied, clip_coef when clipping, and returns (the coefficient's pointer or None,
+        the record)."""
+        part, total = self._norm_partials(launches, device, stream)
+        prev = self._guard_record(device)
+        # a fresh record per step, as the clip's: a norm or a flag somebody holds keeps its value
+        rec = torch.empty(4, dtype=torch.float64, device=device)
+        ops.call("ltx_grad_guard_record", ops._p(part), total, float(max_norm) if max_norm > 0 else 0.0,
+                 ops._p(prev), ops._p(rec), stream)
+        self._guard_rec = rec
+        tail = rec[1:2].view(torch.float32)
+        self.clip_sumsq, self.grad_norm = rec[0], tail[0]
+        self.clip_coef = tail[1] if max_norm > 0 else None
+        self.step_applied = rec[2:3].view(torch.int32)[0]
+        return (ops._p(tail[1]) if max_norm > 0 else None), rec
+
+    def _guard_outcome(self, rec, touched, ema_before):
+        """Behind a guarded step's launches: the outcome (applied, the skipped count) on its way to the pinned
+        slot, an event behind the copy, and what settle() rolls back if the step was skipped. settle() ran at
+        the top of this step, so the slot is free."""
+        if self._guard_slot is None:
+            self._guard_slot = torch.zeros(2, dtype=torch.int64).pin_memory()
+        self._guard_slot.copy_(rec[2:].view(torch.int64), non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        self._guard_pending = (event, touched, ema_before)
+
+    def _launch(self, launches, coef, omd, device, stream, guard=None):
         """One AdamW launch per bucket: ltx_adamw_multi_clip, with the EMA ltx_adamw_multi_ema (given the
         coefficient when clipping), for a mixed bucket ltx_adamw_multi_sr (the coefficient and the shadow
-        as arguments), and for an f32 bucket of the stochastic mode without clip or EMA ltx_adamw_multi."""
+        as arguments), and for an f32 bucket of the stochastic mode without clip or EMA ltx_adamw_multi.
+        `guard` (the guard record's pointer): ltx_adamw_multi_sr_guard for a mixed bucket, ltx_adamw_multi_guard
+        (the coefficient and the EMA as arguments) for every other."""
         ema = self.ema is not None
         for table, nrows, mode, group, step, _ in launches:
             b1, b2 = group["betas"]
             hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
                      int(step))
-            if mode == 2:
+            if guard is not None:
+                tail = (coef, 1 if ema else 0, 0.0 if omd is None else omd)
+                if mode == 2:
+                    ops.call("ltx_adamw_multi_sr_guard", ops._p(table), nrows, *hyper, *tail, self.sr_seed, guard,
+                             stream)
+                else:
+                    ops.call("ltx_adamw_multi_guard", ops._p(table), nrows, mode, *hyper, *tail, guard, stream)
+            elif mode == 2:
                 ops.call("ltx_adamw_multi_sr", ops._p(table), nrows, *hyper, coef, 1 if ema else 0,
                          0.0 if omd is None else omd, self.sr_seed, stream)
             elif ema:
@@ -609,7 +785,7 @@ class FusedAdamW(torch.optim.Optimizer):
     def _step_without_tables(self, max_norm):
         """The unclipped, EMA-less, nearest step: ltx_adamw_multi per dtype group of more than one tensor,
         ltx_adamw_step otherwise, CPU parameters included. False when the step needs the table path."""
-        if max_norm > 0 or self.ema is not None or self.bf16_update == "stochastic":
+        if max_norm > 0 or self.ema is not None or self.bf16_update == "stochastic" or self._skip_nonfinite():
             return False
         for group in self.param_groups:
             b1, b2 = group["betas"]
@@ -713,6 +889,7 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW.ema_swap_in(): this optimizer keeps no EMA (ema=None)")
         if self._ema_swapped is not None:
             raise RuntimeError("FusedAdamW.ema_swap_in(): the EMA weights are swapped in already")
+        self.settle()
         self._check_params("FusedAdamW(ema)", "EMA kernels")
         launches = self._swap_tables()
         stream = ops._s()
@@ -767,6 +944,11 @@ class FusedProdigy(FusedAdamW):
     and float(p0) (ltx_prodigy_moments_multi in its mixed mode, ltx_prodigy_apply_multi_sr), and pass 2
     stores the parameter stochastically rounded (stochastic_round_bf16).
 
+    `skip_nonfinite`, as FusedAdamW's: pass 1 and the d update run behind the guard record
+    (ltx_prodigy_moments_multi_guard, ltx_prodigy_d_update_guard). A skipped step leaves exp_avg, exp_avg_sq,
+    s, p0 and the record's d, d_max, d_numerator, d_denom, d_hat, dlr and k, and sets the record's applied to
+    0, under which pass 2 is the no-op it already is; k lives on the device and needs no rollback.
+
     Two departures from the published code: the factor (d / d0) dlr multiplies the summed numerator once
     instead of every tensor's dot product, and a bf16 tensor's dot product is not rounded to bf16 before it
     is added (products in f32, sums in f64, fixed order: bitwise reproducible, the same on every rank)."""
@@ -778,7 +960,8 @@ class FusedProdigy(FusedAdamW):
 
     def __init__(self, params, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0,
                  decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
-                 growth_rate=float("inf"), max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0):
+                 growth_rate=float("inf"), max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0,
+                 skip_nonfinite=False):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas must be in [0, 1), got {betas}")
@@ -795,7 +978,8 @@ class FusedProdigy(FusedAdamW):
         if not float(growth_rate) > 0.0:
             raise ValueError(f"growth_rate must be > 0, got {growth_rate}")
         super().__init__(params, lr=lr, betas=(b1, b2), eps=float(eps), weight_decay=float(weight_decay),
-                         max_grad_norm=max_grad_norm, ema=ema, bf16_update=bf16_update, sr_seed=sr_seed)
+                         max_grad_norm=max_grad_norm, ema=ema, bf16_update=bf16_update, sr_seed=sr_seed,
+                         skip_nonfinite=skip_nonfinite)
         extra = dict(beta3=None if beta3 is None else float(beta3), decouple=bool(decouple),
                      use_bias_correction=bool(use_bias_correction), safeguard_warmup=bool(safeguard_warmup),
                      d0=float(d0), d_coef=float(d_coef), growth_rate=float(growth_rate))
@@ -858,7 +1042,7 @@ class FusedProdigy(FusedAdamW):
     def _step_without_tables(self, max_norm):
         if float(self.param_groups[0]["lr"]) == 0.0:
             # the published code returns before any state moves; nothing is launched
-            self.clip_sumsq = self.grad_norm = self.clip_coef = None
+            self.clip_sumsq = self.grad_norm = self.clip_coef = self.step_applied = None
             return True
         return False
 
@@ -872,9 +1056,13 @@ class FusedProdigy(FusedAdamW):
         if rec.device != device:
             raise ValueError(f"FusedProdigy: the record is on {rec.device}, the parameters on {device}")
 
-    def _launch(self, launches, coef, omd, device, stream):
+    def _launch(self, launches, coef, omd, device, stream, guard=None):
         """Pass 1 per bucket (each writes its (num, den) partials behind the previous bucket's), the d
-        update, pass 2 per bucket -- ltx_prodigy_apply_multi_sr for a mixed bucket."""
+        update, pass 2 per bucket -- ltx_prodigy_apply_multi_sr for a mixed bucket. `guard` (the guard
+        record's pointer): pass 1 and the d update through their _guard entry points; pass 2 as it is, gated
+        on the record's applied, which a skipped step's d update has set to 0."""
+        gated = () if guard is None else (guard,)
+        suffix = "" if guard is None else "_guard"
         group, rec = launches[0].group, self.record
         ema, omd = 1 if self.ema is not None else 0, 0.0 if omd is None else omd
         total = sum(l.nrows for l in launches)
@@ -888,12 +1076,12 @@ class FusedProdigy(FusedAdamW):
         decouple, use_bc = bool(group["decouple"]), int(bool(group["use_bias_correction"]))
         off = 0
         for table, nrows, mode, _, _, _ in launches:
-            ops.call("ltx_prodigy_moments_multi", ops._p(table), nrows, mode, ops._p(rec), lr, b1, b2, b3, d0,
+            ops.call("ltx_prodigy_moments_multi" + suffix, ops._p(table), nrows, mode, ops._p(rec), lr, b1, b2, b3, d0,
                      0.0 if decouple else wd, use_bc, int(bool(group["safeguard_warmup"])), coef,
-                     ctypes.c_void_p(part.data_ptr() + 16 * off), stream)
+                     ctypes.c_void_p(part.data_ptr() + 16 * off), *gated, stream)
             off += nrows
-        ops.call("ltx_prodigy_d_update", ops._p(part), total, ops._p(rec), lr, b1, b2, b3, d0,
-                 float(group["d_coef"]), float(group["growth_rate"]), use_bc, stream)
+        ops.call("ltx_prodigy_d_update" + suffix, ops._p(part), total, ops._p(rec), lr, b1, b2, b3, d0,
+                 float(group["d_coef"]), float(group["growth_rate"]), use_bc, *gated, stream)
         for table, nrows, mode, _, step, _ in launches:
             if mode == 2:
                 ops.call("ltx_prodigy_apply_multi_sr", ops._p(table), nrows, ops._p(rec), float(group["eps"]),
@@ -918,9 +1106,10 @@ class OptimizerSpec:
     def __init__(self, kind, lr, kwargs):
         self.kind, self.lr, self.kwargs = kind, lr, dict(kwargs)
 
-    def build(self, params, max_grad_norm=None, ema=None):
+    def build(self, params, max_grad_norm=None, ema=None, skip_nonfinite=False):
         cls = FusedProdigy if self.kind == "prodigy" else FusedAdamW  # the module's names at call time
-        return cls(params, lr=self.lr, max_grad_norm=max_grad_norm, ema=ema, **self.kwargs)
+        kwargs = dict(self.kwargs, skip_nonfinite=True) if skip_nonfinite else self.kwargs
+        return cls(params, lr=self.lr, max_grad_norm=max_grad_norm, ema=ema, **kwargs)
 
 
 def optimizer_from_config(config):
@@ -1225,7 +1414,7 @@ class GradAllReduce(OverlapHooks):
 
 def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device, config,
                     prompt_embeds, prompt_attention_mask, epoch, global_step, reducer=None,
-                    log_fn=None, lr_schedule=None):
+                    log_fn=None, lr_schedule=None, max_consecutive_skips=None):
     """training.py:169-231: micro-steps with gradient accumulation, the optimizer step every
     `gradient_accumulation_steps` batches (after the DP gradient all-reduce when `reducer` is
     given), per-step logging of loss / rel_mse / nrmse / lr through `log_fn` (wandb.log in the
@@ -1238,9 +1427,24 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
     gradients -- under data parallelism the averaged ones, the same on every rank -- read at the
     same sync point as the loss. An optimizer that averages (FusedAdamW(ema)) adds "train/ema_decay",
     the decay that step's shadow update used. FusedProdigy adds "train/prodigy_d", its step-size
-    estimate after the step, read from the device record there too."""
+    estimate after the step, read from the device record there too.
+
+    An optimizer that guards (FusedAdamW(skip_nonfinite=True)) adds "train/step_applied" (1, or 0 for a step
+    skipped for non-finite gradients), "train/skipped_steps" (the running count) and "train/grad_norm" also
+    without clipping, all read at that sync point. global_step and the schedule count attempts, skipped
+    ones included. `max_consecutive_skips` (None or 0: no limit): FloatingPointError naming the step once
+    more steps than that were skipped in a row -- the outcome of a step is known to the host at the log
+    point when there is a log_fn, otherwise when the next step (or the end of the epoch) settles it."""
     model.train()
     accum = max(1, int(config.gradient_accumulation_steps))
+    guarded = hasattr(optimizer, "_skip_nonfinite") and optimizer._skip_nonfinite()
+
+    def check_skips():
+        # the newest settled step is global_step, or the one before while this step's outcome is in flight
+        if max_consecutive_skips and optimizer.consecutive_skips > max_consecutive_skips:
+            at = global_step - (1 if optimizer.outcome_pending else 0)
+            raise FloatingPointError(f"optimizer step {at}: {optimizer.consecutive_skips} steps in a row skipped "
+                                     f"for non-finite gradients (max_consecutive_skips = {max_consecutive_skips})")
 
     def zero():
         if reducer is not None:
@@ -1272,6 +1476,9 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
                            "train/lr": optimizer.param_groups[0]["lr"]}
                 if getattr(optimizer, "grad_norm", None) is not None:
                     payload["train/grad_norm"] = float(optimizer.grad_norm)
+                if guarded and optimizer.step_applied is not None:
+                    payload["train/step_applied"] = int(optimizer.step_applied)
+                    payload["train/skipped_steps"] = optimizer.skipped_steps  # settles: the device is past it
                 if isinstance(optimizer, FusedProdigy):
                     payload["train/prodigy_d"] = float(optimizer.d)  # the device record, at the same sync point
                 if getattr(optimizer, "ema", None) is not None:
@@ -1280,7 +1487,12 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
                     if not k.startswith("_"):
                         payload[f"train/{k}"] = float(v)
                 log_fn(payload, global_step)
+            if guarded:
+                check_skips()
     epoch_loss = float(torch.stack(losses).mean()) if losses else 0.0
+    if guarded:
+        optimizer.settle()  # behind the loss's sync: the last step's outcome is there
+        check_skips()
     return global_step, epoch_loss
 
 
@@ -1322,7 +1534,15 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     size on the device (`learning_rate` 1.0, also when null; the schedule multiplies it as it does
     AdamW's rate), logs "train/prodigy_d" per optimizer step, and with save_adapters adds s.<name> /
     p0.<name> to optimizer.safetensors and a "prodigy" block to train_state.json, from which a resumed
-    run continues bitwise. `weight_decay`, `adam_beta1`, `adam_beta2`, `adam_eps` reach either optimizer."""
+    run continues bitwise. `weight_decay`, `adam_beta1`, `adam_beta2`, `adam_eps` reach either optimizer.
+
+    `skip_nonfinite` (guard_from_config; absent or false = today's run, call for call and file for file):
+    either optimizer skips, on the device and without a host sync, every step whose gradients are not all
+    finite -- parameters, moments, shadows, Prodigy's state and the step counts are then exactly those of a
+    run in which that step was never called -- and "train/step_applied" / "train/skipped_steps" (and
+    "train/grad_norm" also without clipping) are logged per step; `max_consecutive_skips` ends the run with
+    FloatingPointError instead of skipping forever. With save_adapters train_state.json gains a "guard" block
+    with the skipped count, from which a resumed run continues bitwise."""
     import os
 
     from . import io
@@ -1338,6 +1558,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     # the optional optimizer-step keys, validated before anything is built
     max_grad_norm, lr_schedule = schedule_from_config(config, dataloader)
     ema = ema_from_config(config)
+    skip_nonfinite, max_consecutive_skips = guard_from_config(config)
     spec = optimizer_from_config(config)
     if spec.kind == "prodigy" and lr_schedule is not None:
         lr_schedule.base_lr = spec.lr  # learning_rate: null means 1.0 there
@@ -1351,7 +1572,8 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                 target_shift_terminal=config.rf_target_shift_terminal,
                                 sampler=config.rf_sampler, shift=config.rf_shift)
     params = [p for p in model.parameters() if p.requires_grad]
-    optimizer = spec.build(params, max_grad_norm=max_grad_norm, ema=ema)
+    guard_kw = dict(skip_nonfinite=True) if skip_nonfinite else {}  # absent: today's call
+    optimizer = spec.build(params, max_grad_norm=max_grad_norm, ema=ema, **guard_kw)
     reducer = None
     if dist.is_available() and dist.is_initialized():
         order = model.grad_ready_order() if hasattr(model, "grad_ready_order") else None
@@ -1371,7 +1593,9 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
         global_step, epoch_loss = train_one_epoch(model, dataloader, optimizer, rf, patchifier,
                                                   device, config, prompt_embeds,
                                                   prompt_attention_mask, epoch, global_step,
-                                                  reducer, log_fn, lr_schedule)
+                                                  reducer, log_fn, lr_schedule,
+                                                  **(dict(max_consecutive_skips=max_consecutive_skips)
+                                                     if skip_nonfinite else {}))
         if val_dataloader is not None:
             from .validation import validate_epoch
             val_loss = validate_epoch(model, val_dataloader, rf, patchifier, config, prompt_embeds,
