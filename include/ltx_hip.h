@@ -468,6 +468,40 @@ int ltx_batch_sum_bf16(const void* x, int64_t ldx, int64_t B, int64_t rows, int6
  * dout = bf16(bf16(bf16(o-v) * 2/n) * gscale). */
 int ltx_mse_fwd_bwd(const void* out, const void* v, void* dout, float* stats, int64_t n,
                     float grad_scale, void* stream);
+
+/* ---- weighted velocity loss (csrc/loss.hip; DESIGN.md "Loss weights") ---------------------------
+ * Per-token loss weights of a [B, F, H, W] latent grid, token n = (f*H + h)*W + w, all f32:
+ *   box  = bbox[b] = (x_min, y_min, x_max, y_max) in [0,1], padded by face_pad times its width and
+ *          height on each side, then clipped to [0,1]; a NaN coordinate or a box that is empty after
+ *          the clip gives cov = 0 for the whole sample, and so does bbox == null;
+ *   ox   = min(1, max(0, min(x1, (w+1)/W) - max(x0, w/W)) * W), oy likewise with h and H;
+ *   cov  = ox * oy, the share of the token's cell that the box covers;
+ *   raw[b,n]   = frame_w[f] * (1 + (face_weight - 1) * cov) * user_w[b,n];
+ *   raw_sum[b] = sum_n raw[b,n]; wt[b,n] = raw[b,n] * (sample_w[b] * N / raw_sum[b]), 0 where
+ *                raw_sum[b] == 0 -- each sample's weights average to sample_w[b].
+ * A null frame_w / sample_w / user_w is all ones. face_weight > 0, face_pad >= 0. One workgroup per
+ * sample; the sum is taken in a fixed order (strided per-thread sums, the wave shuffle tree, four waves
+ * in order) without atomics, bitwise run to run. Any B, F, H, W >= 1. */
+int ltx_loss_token_weights(const float* bbox,      /* [B,4] x_min,y_min,x_max,y_max in [0,1], or null */
+                           const float* frame_w,   /* [F] >= 0, or null (= 1)                          */
+                           const float* sample_w,  /* [B], or null (= 1): the timestep factor          */
+                           const float* user_w,    /* [B,N] >= 0, or null (= 1)                        */
+                           float face_weight, float face_pad,
+                           float* wt,              /* [B,N] out, N = F*H*W, token n = (f*H + h)*W + w  */
+                           float* raw_sum,         /* [B] out                                          */
+                           int64_t B, int64_t F, int64_t H, int64_t W, void* stream);
+/* ltx_mse_fwd_bwd with a weight per token: out / v / dout bf16 [rows, C] dense (16-B aligned), element
+ * i of the n = rows * C belongs to token i / C. Per element d = bf16(o - v), q = bf16(d * d) and
+ * dout = bf16(f32(bf16(bf16(d * 2/n) * grad_scale)) * wt[token]), round to nearest even: ltx_mse_fwd_bwd's
+ * seed, then one multiply and one rounding. stats[0] = sum wt * q, stats[1] = sum v, stats[2] = sum v^2,
+ * stats[3] = sum q (the unweighted sum); stats is f32[4 + 4*256]: the tail holds 256 per-block partials
+ * of each sum, added in ltx_mse_fwd_bwd's fixed order. The traversal is ltx_mse_fwd_bwd's (16-B vectors
+ * over n / 8, then the scalar tail), so for every C: with wt == 1 stats[0..2], stats[3] and dout are
+ * bitwise ltx_mse_fwd_bwd's stats[0..2], stats[0] and dout, and for any wt stats[1..3] are bitwise its
+ * stats[1], stats[2], stats[0]. C % 8 == 0 loads one weight per vector. dout may be null. */
+int ltx_wmse_fwd_bwd(const void* out, const void* v, const float* wt /* [rows] */,
+                     void* dout /* nullable */, float* stats /* f32[4 + 4*256] */,
+                     int64_t rows, int64_t C, float grad_scale, void* stream);
 /* torch.optim.AdamW single-tensor step (training.py:270-271): f32 or bf16 param/state.
  * is_bf16 selects the dtype of param/grad/exp_avg/exp_avg_sq (all the same). */
 int ltx_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n,

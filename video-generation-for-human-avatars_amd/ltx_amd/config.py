@@ -193,4 +193,15 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     for key in ("skip_nonfinite", "max_consecutive_skips"):
         if key in t:
             setattr(config, key, t[key])
+    # and the four keys training.loss_weights_from_config reads (and validates; passed on as written):
+    # `train.loss_face_weight` (a float > 0, absent = 1): the loss weight of the tokens inside the clip's
+    # face box; `train.loss_face_pad` (a float >= 0, absent = 0): the box's margin, as a fraction of its
+    # size; `train.loss_frame0_weight` (a float >= 0, absent = 1): the weight of the first latent frame;
+    # `train.loss_timestep_weighting` ("none", the same as absent, "sigma_sqrt" or "cosmap"). With them
+    # `train.face_bbox_dir`: the directory of the preprocessing's {stem}.json files with the `face_bbox`
+    # key, the face_bbox_dir argument of io.LatentPairDataset
+    for key in ("loss_face_weight", "loss_face_pad", "loss_frame0_weight", "loss_timestep_weighting",
+                "face_bbox_dir"):
+        if key in t:
+            setattr(config, key, t[key])
     return config

@@ -48,22 +48,47 @@ def save_latents_pt(latents, path):
 
 
 def collate_latent_pairs(batch: List[Dict]):
-    """dataset.py:5-44."""
-    return {
+    """dataset.py:5-44; with the items' "face_bbox" (LatentPairDataset(face_bbox_dir)) also its stack,
+    f32 [B, 4]."""
+    out = {
         "latents": torch.stack([b["latents"] for b in batch], dim=0),
         "pose_latents": torch.stack([b["pose_latents"] for b in batch], dim=0),
         "ref_image_latents": torch.stack([b["ref_image_latents"] for b in batch], dim=0),
         "stem": [b["stem"] for b in batch],
     }
+    if batch and "face_bbox" in batch[0]:
+        out["face_bbox"] = torch.stack([b["face_bbox"] for b in batch], dim=0)
+    return out
+
+
+_BBOX_KEYS = ("x_min", "y_min", "x_max", "y_max")
+
+
+def load_face_bbox(path):
+    """f32 [4] (x_min, y_min, x_max, y_max, normalised to the frame) from the `face_bbox` entry of a
+    clip's conditioning JSON, as the reference's preprocessing writes it beside every clip
+    (preprocessing/save_condition_latents.py:168-191: a dict of the four names). All NaN -- which the
+    loss weighting treats as "no box" -- when the file or the key is missing or does not hold the four
+    numbers."""
+    try:
+        with open(path, "r") as f:
+            box = json.load(f)["face_bbox"]
+        return torch.tensor([float(box[k]) for k in _BBOX_KEYS], dtype=torch.float32)
+    except (OSError, ValueError, KeyError, TypeError):
+        return torch.full((4,), float("nan"), dtype=torch.float32)
 
 
 class LatentPairDataset(Dataset):
     """dataset.py:47-97: encoder latents {stem}.pt (not *_ref) paired with the condition dir's
-    {stem}.pt (pose) and {stem}_ref.pt (reference image); stems sorted, unpaired ones skipped."""
+    {stem}.pt (pose) and {stem}_ref.pt (reference image); stems sorted, unpaired ones skipped.
 
-    def __init__(self, condition_latents_dir: str, encoder_latents_dir: str):
+    `face_bbox_dir` (None: the reference's item dict, unchanged): every item also carries "face_bbox",
+    load_face_bbox of {face_bbox_dir}/{stem}.json."""
+
+    def __init__(self, condition_latents_dir: str, encoder_latents_dir: str, face_bbox_dir: Optional[str] = None):
         self.condition_dir = Path(condition_latents_dir)
         self.encoder_dir = Path(encoder_latents_dir)
+        self.face_bbox_dir = Path(face_bbox_dir) if face_bbox_dir else None
         files = [f for f in sorted(self.encoder_dir.glob("*.pt")) if not f.stem.endswith("_ref")]
         self.items = [f.stem for f in files
                       if (self.condition_dir / f"{f.stem}.pt").exists()
@@ -79,7 +104,10 @@ class LatentPairDataset(Dataset):
         ref = load_latents_pt(self.condition_dir / f"{stem}_ref.pt").squeeze()
         if ref.ndim == 3:
             ref = ref.unsqueeze(1)
-        return {"latents": latents, "pose_latents": pose, "ref_image_latents": ref, "stem": stem}
+        item = {"latents": latents, "pose_latents": pose, "ref_image_latents": ref, "stem": stem}
+        if self.face_bbox_dir is not None:
+            item["face_bbox"] = load_face_bbox(self.face_bbox_dir / f"{stem}.json")
+        return item
 
 
 class LatentLoader:
@@ -116,6 +144,8 @@ class LatentLoader:
         for k in ("latents", "pose_latents", "ref_image_latents"):
             t = b[k].to(self.dtype)
             b[k] = t.pin_memory() if self.stream is not None else t
+        if "face_bbox" in b and self.stream is not None:
+            b["face_bbox"] = b["face_bbox"].pin_memory()  # the box stays f32: it is coordinates, not latents
         return b
 
     def _to_device(self, hb):

@@ -1071,6 +1071,57 @@ def mse_fwd_bwd(out, v, grad_scale=1.0, want_grad=True):
     return stats[:4], dout
 
 
+def loss_token_weights(B, F, H, W, device, bbox=None, frame_w=None, sample_w=None, user_w=None, face_weight=1.0,
+                       face_pad=0.0):
+    """(wt f32 [B, N], raw_sum f32 [B]) of ltx_loss_token_weights, N = F*H*W: the face-box coverage of
+    every token's cell (bbox f32 [B, 4], normalised x_min, y_min, x_max, y_max) weighted by face_weight,
+    times frame_w f32 [F], times user_w f32 [B, N], normalised per sample to the mean sample_w f32 [B].
+    A None input is all ones (bbox None: no box)."""
+    B, F, H, W = int(B), int(F), int(H), int(W)
+    N = F * H * W
+    for t, shape, name in ((bbox, (B, 4), "bbox"), (frame_w, (F,), "frame_w"), (sample_w, (B,), "sample_w"),
+                           (user_w, (B, N), "user_w")):
+        if t is None:
+            continue
+        _need(t, F32, "loss_token_weights " + name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"loss_token_weights: {name} must be a contiguous f32 {shape}, got {tuple(t.shape)} "
+                             f"strides {t.stride()}")
+    wt = torch.empty(B, N, dtype=F32, device=device)
+    raw_sum = torch.empty(B, dtype=F32, device=device)
+    label = "ltx::loss_token_weights_kernel"
+    timer, ev0 = _timed(label)
+    call("ltx_loss_token_weights", _p(bbox), _p(frame_w), _p(sample_w), _p(user_w), float(face_weight),
+         float(face_pad), _p(wt), _p(raw_sum), B, F, H, W, _s())
+    if timer is not None:  # wt written, read back and written again by the same lanes; user_w read once
+        timer.stop(label, 0.0, ev0, 4.0 * B * N * (3 if user_w is None else 4))
+    return wt, raw_sum
+
+
+def wmse_fwd_bwd(out, v, wt, grad_scale=1.0, want_grad=True):
+    """mse_fwd_bwd with a weight per token (ltx_wmse_fwd_bwd): out, v bf16 [..., C], wt f32 with one
+    element per row of C. Returns (stats[4] f32 device: sum wt * sq-err, sum v, sum v^2, sum sq-err;
+    dout bf16 = mse_fwd_bwd's seed times wt, or None)."""
+    _need(out, BF16, "wmse out")
+    _need(v, BF16, "wmse v")
+    _need(wt, F32, "wmse wt")
+    C = out.shape[-1]
+    n = out.numel()
+    rows = n // C
+    if v.shape != out.shape or wt.numel() != rows:
+        raise ValueError(f"wmse_fwd_bwd: out {tuple(out.shape)}, v {tuple(v.shape)}, wt {tuple(wt.shape)}: v must "
+                         f"have out's shape and wt one weight per row of {C}")
+    out, v, wt = out.contiguous(), v.contiguous(), wt.contiguous()
+    stats = torch.empty(4 + 4 * 256, dtype=F32, device=out.device)  # + per-block partials
+    dout = torch.empty(out.shape, dtype=BF16, device=out.device) if want_grad else None
+    label = f"ltx::wmse_kernel<{'true' if C % 8 == 0 else 'false'}>"
+    timer, ev0 = _timed(label)
+    call("ltx_wmse_fwd_bwd", _p(out), _p(v), _p(wt), _p(dout), _p(stats), rows, C, float(grad_scale), _s())
+    if timer is not None:
+        timer.stop(label, 0.0, ev0, 2.0 * n * (3 if want_grad else 2) + 4.0 * rows)
+    return stats[:4], dout
+
+
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
     is_bf16 = 1 if param.dtype == BF16 else 0
     call("ltx_adamw_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(),

@@ -67,7 +67,13 @@ def sample_timesteps(batch, config, device):
 def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, prompt_attention_mask,
                device=None, t=None, noise=None, backward=True):
     """Returns (loss, rel_mse, nrmse, loss_dict) like the reference; runs the backward too when
-    `backward` (the reference calls loss.backward() in train_one_epoch, training.py:203)."""
+    `backward` (the reference calls loss.backward() in train_one_epoch, training.py:203).
+
+    With a loss key of loss_weights_from_config off its default, or batch["loss_weights"] (f32 [B, N] or
+    [B, F, H, W], >= 0), the loss is the weighted mean(wt (out - v)^2): the token weights come from
+    ltx_loss_token_weights (batch["face_bbox"], f32 [B, 4], when it is there) and ltx_wmse_fwd_bwd takes
+    ltx_mse_fwd_bwd's place. loss, rel_mse and nrmse are then the weighted loss's, loss_dict gains
+    "transformer_wmse" / "_wmse_f32", and "transformer_mse" / "_mse_f32" stay the unweighted mean."""
     dt = torch.bfloat16
     device = device or model.device
     latents = batch["latents"].to(device=device, dtype=dt)
@@ -75,6 +81,20 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
     pose = batch["pose_latents"].to(device=device, dtype=dt)
     B, C, F, H, W = latents.shape
     N = F * H * W
+    # the loss weights (loss_weights_from_config; None and no batch["loss_weights"]: the reference's plain
+    # mse, today's launches). The refusals come before anything is launched.
+    lw = loss_weights_from_config(config)
+    user_w = batch.get("loss_weights")
+    weighted = lw is not None or user_w is not None
+    if weighted:
+        lw = lw or LossWeights()
+        if lw.frame0_weight == 0.0 and F == 1:
+            raise ValueError("loss_frame0_weight = 0 with a single latent frame: every token's weight would be 0")
+        if user_w is not None:
+            if tuple(user_w.shape) not in ((B, N), (B, F, H, W)):
+                raise ValueError(f"batch['loss_weights']: expected shape {(B, N)} or {(B, F, H, W)}, got "
+                                 f"{tuple(user_w.shape)}")
+            user_w = user_w.to(device=device, dtype=torch.float32).reshape(B, N).contiguous()
     # convert first, then expand: the batch stays a stride-0 view, which the model recognises as
     # one prompt shared by the batch (caption projection and text K/V computed once)
     enc = prompt_embeds.to(device=device, dtype=dt).expand(B, -1, -1)
@@ -92,18 +112,148 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
     out = model._forward_tokens(model_in, coords, enc, t, enc_mask)
     w = float(getattr(config, "transformer_loss_weight", 1.0))
     accum = max(1, int(getattr(config, "gradient_accumulation_steps", 1)))
-    stats, dout = ops.mse_fwd_bwd(out, v_target, grad_scale=w / accum, want_grad=backward)
     n = out.numel()
-    mse = (stats[0] / n).to(dt)
-    loss = w * mse
+    if weighted:
+        # built on the device and consumed inside the loss kernel: no host read, no torch pass over the
+        # tokens. stats[0] is the weighted sum, stats[3] the unweighted one (bitwise mse_fwd_bwd's)
+        bbox = batch.get("face_bbox") if lw.face_weight != 1.0 else None  # a missing box: uniform weights
+        if bbox is not None:
+            bbox = bbox.to(device=device, dtype=torch.float32).reshape(B, 4).contiguous()
+        wt, _ = ops.loss_token_weights(B, F, H, W, device, bbox=bbox,
+                                       frame_w=_frame_weights(F, lw.frame0_weight, device),
+                                       sample_w=timestep_loss_weight(t, lw.timestep_weighting), user_w=user_w,
+                                       face_weight=lw.face_weight, face_pad=lw.face_pad)
+        stats, dout = ops.wmse_fwd_bwd(out, v_target, wt, grad_scale=w / accum, want_grad=backward)
+        wmse_f32, mse_f32 = stats[0] / n, stats[3] / n
+        wmse, mse = wmse_f32.to(dt), mse_f32.to(dt)
+        loss = w * wmse
+        loss_dict = {"transformer_mse": mse, "_mse_f32": mse_f32, "transformer_wmse": wmse, "_wmse_f32": wmse_f32}
+    else:
+        stats, dout = ops.mse_fwd_bwd(out, v_target, grad_scale=w / accum, want_grad=backward)
+        mse = (stats[0] / n).to(dt)
+        loss = w * mse
+        # "_mse_f32": the unrounded f32 mean (parity tests compare losses at 1e-3, below the bf16
+        # rounding of the reference's loss scalar); underscore keys are not logged
+        loss_dict = {"transformer_mse": mse, "_mse_f32": stats[0] / n}
     std = torch.sqrt(torch.clamp((stats[2] - stats[1] * stats[1] / n) / (n - 1), min=0)).to(dt)
     rel_mse = loss / (std ** 2 + 1e-12)
     nrmse = torch.sqrt(loss) / (std + 1e-12)
     if backward:
         out.backward(dout)
-    # "_mse_f32": the unrounded f32 mean (parity tests compare losses at 1e-3, below the bf16
-    # rounding of the reference's loss scalar); underscore keys are not logged
-    return loss, rel_mse, nrmse, {"transformer_mse": mse, "_mse_f32": stats[0] / n}
+    return loss, rel_mse, nrmse, loss_dict
+
+
+TIMESTEP_WEIGHTINGS = ("none", "sigma_sqrt", "cosmap")
+
+# What loss_weights_from_config decided; the defaults are the reference's unweighted loss
+LossWeights = collections.namedtuple("LossWeights", "face_weight face_pad frame0_weight timestep_weighting",
+                                     defaults=(1.0, 0.0, 1.0, "none"))
+
+
+def loss_weights_from_config(config):
+    """LossWeights or None from the optional config keys (setattr, or train.<key> in the YAML; not
+    TrainConfig fields). None -- every key absent or at its default -- is the reference's plain
+    F.mse_loss, launch for launch:
+      `loss_face_weight` (a float > 0, absent = 1): the weight of a token wholly inside the sample's face
+          box (batch["face_bbox"]) relative to one outside; a token the box cuts gets the share it covers;
+      `loss_face_pad` (a float >= 0, absent = 0): the box grows by this fraction of its width and height
+          on each side before it is clipped to the frame -- the allowance for head motion, since the box
+          comes from the reference frame and is applied to every latent frame;
+      `loss_frame0_weight` (a float >= 0, absent = 1): the weight of the first latent frame's tokens,
+          which the model is fed as lerp(x_t, ref, 0.85); train_step refuses 0 when there is one frame;
+      `loss_timestep_weighting` ("none", the same as absent, "sigma_sqrt": t^-2, or "cosmap":
+          2 / (pi (1 - 2 t + 2 t^2)), SD3's weightings of the rectified-flow loss on the step's shifted t).
+    Each sample's token weights are normalised to average to its timestep factor, so the loss scale (and
+    with it the learning rate) carries over from unweighted runs. ValueError for anything else: a bool, a
+    string where a number belongs, a NaN, a value out of range, an unknown weighting."""
+    def number(key, default, ok, what):
+        v = getattr(config, key, None)
+        if v is None:
+            return default
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(float(v)) or math.isinf(float(v)):
+            raise ValueError(f"{key} must be {what}, got {v!r}")
+        return float(v)
+    face = number("loss_face_weight", 1.0, lambda v: v > 0, "a finite float > 0")
+    pad = number("loss_face_pad", 0.0, lambda v: v >= 0, "a finite float >= 0")
+    frame0 = number("loss_frame0_weight", 1.0, lambda v: v >= 0, "a finite float >= 0")
+    scheme = getattr(config, "loss_timestep_weighting", None)
+    if scheme is None:
+        scheme = "none"
+    if not isinstance(scheme, str) or scheme not in TIMESTEP_WEIGHTINGS:
+        raise ValueError(f"loss_timestep_weighting {scheme!r} is not one of {', '.join(TIMESTEP_WEIGHTINGS)}")
+    lw = LossWeights(face, pad, frame0, scheme)
+    return None if lw == LossWeights() else lw
+
+
+def timestep_loss_weight(t, scheme):
+    """The per-sample factor of `loss_timestep_weighting` on the step's (shifted) t, f32 [B], or None for
+    "none": torch ops on t's device, nothing is read back. "sigma_sqrt": t^-2; "cosmap":
+    2 / (pi (1 - 2 t + 2 t^2))."""
+    if scheme == "none":
+        return None
+    if scheme == "sigma_sqrt":
+        return (1.0 / (t * t)).contiguous()
+    if scheme == "cosmap":
+        return (2.0 / (math.pi * (1.0 - 2.0 * t + 2.0 * (t * t)))).contiguous()
+    raise ValueError(f"loss_timestep_weighting {scheme!r} is not one of {', '.join(TIMESTEP_WEIGHTINGS)}")
+
+
+_FRAME_WEIGHTS = {}  # (F, frame0_weight, device) -> the f32 [F] frame weights on the device
+
+
+def _frame_weights(F, frame0_weight, device):
+    """None for a first-frame weight of 1, else ones with frame0_weight in front (built once per key, with
+    device fills: no host-to-device copy in the step)."""
+    if frame0_weight == 1.0:
+        return None
+    key = (int(F), float(frame0_weight), str(torch.device(device)))
+    fw = _FRAME_WEIGHTS.get(key)
+    if fw is None:
+        fw = torch.ones(F, dtype=torch.float32, device=device)
+        fw[:1].fill_(frame0_weight)
+        _FRAME_WEIGHTS[key] = fw
+    return fw
+
+
+def token_loss_weights_ref(B, F, H, W, bbox=None, frame_w=None, sample_w=None, user_w=None, face_weight=1.0,
+                           face_pad=0.0):
+    """The statement, in float64 torch ops on the inputs' device, of ltx_loss_token_weights (the kernel
+    does the same arithmetic in f32): (wt [B, N], raw_sum [B]), N = F H W, token n = (f H + h) W + w.
+      box: bbox[b] = (x_min, y_min, x_max, y_max), padded by face_pad times its width / height on each
+           side, clipped to [0, 1]; a NaN coordinate or an empty clipped box: cov = 0 for the sample;
+      ox = min(1, max(0, min(x1, (w + 1) / W) - max(x0, w / W)) W), oy likewise with h and H, cov = ox oy;
+      raw[b, n] = frame_w[f] (1 + (face_weight - 1) cov) user_w[b, n];
+      raw_sum[b] = sum_n raw[b, n]; wt[b, n] = sample_w[b] raw[b, n] N / raw_sum[b], 0 where raw_sum[b] = 0.
+    A None input is all ones (bbox None: no box). user_w may be [B, N] or [B, F, H, W]."""
+    f64 = torch.float64
+    N = F * H * W
+    dev = next((x.device for x in (bbox, frame_w, sample_w, user_w) if x is not None), torch.device("cpu"))
+    cov = torch.zeros(B, H, W, dtype=f64, device=dev)
+    if bbox is not None:
+        box = bbox.to(f64).reshape(B, 4)
+        valid = ~torch.isnan(box).any(dim=1)
+        x0, y0, x1, y1 = box.unbind(1)
+        px, py = face_pad * (x1 - x0), face_pad * (y1 - y0)
+        x0, x1 = (x0 - px).clamp(0, 1), (x1 + px).clamp(0, 1)
+        y0, y1 = (y0 - py).clamp(0, 1), (y1 + py).clamp(0, 1)
+        valid = valid & (x1 > x0) & (y1 > y0)
+        ws = torch.arange(W, dtype=f64, device=dev)
+        hs = torch.arange(H, dtype=f64, device=dev)
+        ox = ((torch.minimum(x1[:, None], (ws + 1) / W) - torch.maximum(x0[:, None], ws / W)).clamp(min=0) * W)
+        oy = ((torch.minimum(y1[:, None], (hs + 1) / H) - torch.maximum(y0[:, None], hs / H)).clamp(min=0) * H)
+        cov = oy.clamp(max=1)[:, :, None] * ox.clamp(max=1)[:, None, :]
+        cov = torch.where(valid[:, None, None], cov, torch.zeros_like(cov))
+    raw = (1.0 + (float(face_weight) - 1.0) * cov)[:, None].expand(B, F, H, W)
+    if frame_w is not None:
+        raw = raw * frame_w.to(f64).reshape(1, F, 1, 1)
+    raw = raw.reshape(B, N)
+    if user_w is not None:
+        raw = raw * user_w.to(f64).reshape(B, N)
+    raw_sum = raw.sum(dim=1)
+    sw = torch.ones(B, dtype=f64, device=dev) if sample_w is None else sample_w.to(f64).reshape(B)
+    safe = torch.where(raw_sum != 0, raw_sum, torch.ones_like(raw_sum))
+    wt = torch.where((raw_sum != 0)[:, None], sw[:, None] * raw * N / safe[:, None], torch.zeros_like(raw))
+    return wt, raw_sum
 
 
 class LRSchedule:
@@ -1542,7 +1692,14 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     run in which that step was never called -- and "train/step_applied" / "train/skipped_steps" (and
     "train/grad_norm" also without clipping) are logged per step; `max_consecutive_skips` ends the run with
     FloatingPointError instead of skipping forever. With save_adapters train_state.json gains a "guard" block
-    with the skipped count, from which a resumed run continues bitwise."""
+    with the skipped count, from which a resumed run continues bitwise.
+
+    `loss_face_weight`, `loss_face_pad`, `loss_frame0_weight`, `loss_timestep_weighting`
+    (loss_weights_from_config, read by every train_step; absent or at their defaults = today's run, launch
+    for launch): the velocity loss weighted by the clip's face box (the batches' "face_bbox", which a
+    LatentPairDataset built with face_bbox_dir carries), the first latent frame and the timestep.
+    "train/transformer_wmse" is then logged beside "train/transformer_mse", which stays the unweighted mse,
+    as does "val/loss"."""
     import os
 
     from . import io
