@@ -399,6 +399,25 @@ int ltx_lora_dy_dA_grouped(const void* y, int64_t ldy, const float* const* u, in
                            float* workspace, void* stream);
 int ltx_lora_dy_dA_grouped_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups,
                                      int64_t* floats);
+/* The demangled names (as rocprofv3 prints them, without the argument list) of the kernels an
+ * adapter entry would launch for this call on `stream`, joined by " + " in launch order, e.g.
+ * "ltx::lora_dy_kernel<16, 3> + ltx::lora_dy_kernel<16, 6> + ltx::lora_dy_finish_kernel<16>". Host
+ * only, nothing is launched: the same plan the entries launch from (csrc/lora_plan.h), so it depends on
+ * the LTX_LORA_WGRAD_ROWS / LTX_LORA_ROWS_DY / LTX_LORA_ROWS_FULL values the library read and on the
+ * workspace of `stream`. Every pointer is taken as 16-B aligned.
+ *   op DOWN:  ltx_lora_down(_grouped) on x [M, K]
+ *   op ROWS:  ltx_lora_rows on x [M, K] (ld_in), pieces (ld_w), out (ld_out)
+ *   op WGRAD: ltx_lora_wgrad(_grouped) on y [M, N] (ld_in), u [M, r] (ld_w)
+ *   op DY:    ltx_lora_dy on dY [M, N] (ld_in), pieces (ld_w), w (ld_out)
+ *   op DY_DA: ltx_lora_dy_dA, also x [M, K]
+ * A leading dimension of 0 stands for the dense one. groups = 0: the one-adapter entry; groups >= 1:
+ * the _grouped entry (ROWS, DY_DA: up to 4) with out / split columns of group g at g * r / g * K2.
+ * split: the call also writes the K-extension operand (DOWN, ROWS). An argument the entry would
+ * reject, a rank outside 8 / 16 / 32 / 64 / 128 among them, is LTX_ERR_BAD_ARG here too. Writes a
+ * NUL-terminated string of at most len bytes. */
+enum { LTX_LORA_OP_DOWN = 0, LTX_LORA_OP_ROWS = 1, LTX_LORA_OP_WGRAD = 2, LTX_LORA_OP_DY = 3, LTX_LORA_OP_DY_DA = 4 };
+int ltx_lora_describe(int op, int64_t M, int64_t N, int64_t K, int64_t ld_in, int64_t ld_w, int64_t ld_out,
+                      int64_t r, int64_t groups, int split, void* stream, char* buf, int64_t len);
 
 /* ---- LoRA dropout (peft lora_dropout; DESIGN.md "LoRA dropout") -------------------------------
  * The mask is a pure function of (key, sid, row m, column k): Philox4x32-10 with counter

@@ -285,3 +285,196 @@ def test_attn_describe_names_the_dispatched_kernels(attn_switches):
     finally:
         for handle, _ in streams.values():
             lib.ltx_gemm_set_stream_workspace(ctypes.c_void_p(handle), None, 0)
+
+
+# ---- the LoRA adapter dispatch plan (csrc/lora_plan.h) through ltx_lora_describe, host only. The expected
+# kernels are written from the dispatch code of the commit before the plan existed; {R} is the rank.
+# (op, M, N, K, options, kernels): options groups (0: the one-adapter entry), ws ("big" 128 MiB on the call's
+# stream, "small" 64 KiB, "huge" 1 GiB, None none)
+_FULL, _DY1 = "lora_rows_full_kernel<{R}, 2, %d, 5>", "lora_dy_kernel<{R}, 1> + lora_dy_finish_kernel<{R}>"
+_ROWS, _WG = "lora_rows_kernel<{R}, 4, 4>", "lora_wgrad_kernel<{R}>"
+_LORA_ROUTES = [
+    # ltx_lora_rows: the whole contraction per block at token-sized M and K = 512 / 1024 / 2048
+    ("rows", 2048, 0, 512, {}, _FULL % 1),
+    ("rows", 2048, 0, 1024, {}, _FULL % 2),
+    ("rows", 2048, 0, 2048, {}, _FULL % 4),
+    # any other K % 512 == 0: the column-split pass + finish while its partials (3 x 2048 x max(r, 16) f32:
+    # 384 KiB at r = 16) fit the stream's workspace
+    ("rows", 2048, 0, 1536, {}, _DY1),
+    ("rows", 2048, 0, 1536, dict(ws="small"), _ROWS),
+    ("rows", 2048, 0, 1536, dict(ws=None), _ROWS),
+    # M < 2048, K % 512 != 0, M % 32 != 0
+    ("rows", 2016, 0, 512, {}, _ROWS),
+    ("rows", 2048, 0, 256, {}, _ROWS),
+    ("rows", 2050, 0, 512, {}, _ROWS),
+    # ltx_lora_rows_grouped: one launch on the whole-contraction route, else the one-adapter plan per group
+    ("rows", 2048, 0, 512, dict(groups=3), "lora_rows_full_grouped_kernel<{R}, 2, 1, 5>"),
+    ("rows", 2016, 0, 512, dict(groups=3), " + ".join([_ROWS] * 3)),
+    # ltx_lora_wgrad: the dB product of lora_dy_kernel at token-sized M; below it row splits + finish (2016 rows:
+    # 8 splits of 256) while the partials fit the workspace, else one split; 200 rows are one split anyway
+    ("wgrad", 2048, 512, 0, {}, "lora_dy_kernel<{R}, 2> + lora_dy_finish_kernel<{R}>"),
+    ("wgrad", 2016, 512, 0, {}, _WG + " + lora_wgrad_finish_kernel"),
+    ("wgrad", 2016, 512, 0, dict(ws=None), _WG),
+    ("wgrad", 200, 128, 0, {}, _WG),
+    ("wgrad", 2048, 512, 0, dict(ws=None), _WG),
+    ("wgrad", 2048, 512, 0, dict(groups=2), _WG + " + lora_wgrad_finish_kernel"),  # grouped: never the dY route
+    # ltx_lora_down: <R, RG, KW>, RG = 2 from M = 8192 on, KW = 8 where K % 256 == 0
+    ("down", 48, 0, 128, {}, "lora_down_kernel<{R}, 1, 4>"),
+    ("down", 48, 0, 256, {}, "lora_down_kernel<{R}, 1, 8>"),
+    ("down", 8192, 0, 128, {}, "lora_down_kernel<{R}, 2, 4>"),
+    ("down", 8192, 0, 256, {}, "lora_down_kernel<{R}, 2, 8>"),
+    ("down", 8192, 0, 256, dict(groups=3), "lora_down_kernel<{R}, 2, 8>"),
+    # the dY family: the dY pass, the x pass from its partials (MODE 6 up to N = 2048, 14 beyond), one finish
+    ("dy", 32, 512, 0, {}, "lora_dy_kernel<{R}, 3> + lora_dy_finish_kernel<{R}>"),
+    ("dy_dA", 2048, 512, 512, {}, "lora_dy_kernel<{R}, 3> + lora_dy_kernel<{R}, 6> + lora_dy_finish_kernel<{R}>"),
+    ("dy_dA", 2048, 2560, 512, {}, "lora_dy_kernel<{R}, 3> + lora_dy_kernel<{R}, 14> + lora_dy_finish_kernel<{R}>"),
+    ("dy_dA", 2048, 512, 512, dict(groups=3),
+     "lora_dy_grouped_kernel<{R}, 3> + lora_dy_grouped_kernel<{R}, 6> + lora_dy_finish_grouped_kernel<{R}>"),
+]
+_LORA_ALL_RANKS = {"rows": 0, "wgrad": 11, "down": 17, "dy": 22, "dy_dA": 23}  # row of _LORA_ROUTES run at every rank
+_LORA_WS = {"big": (0x10A0, 128 << 20), "small": (0x10B0, 64 << 10), None: (0x10C0, 0), "huge": (0x10D0, 1 << 30)}
+
+
+def _lora_describe(lib, op, M, N, K, r, groups=0, ws="big", split=False):
+    """(return code, the kernels with "ltx::" taken off each)"""
+    import ctypes
+    from ltx_amd import _lib
+    buf = ctypes.create_string_buffer(512)
+    rc = lib.ltx_lora_describe(_lib.LORA_OP[op], M, N, K, 0, 0, 0, r, groups, int(split),
+                               ctypes.c_void_p(_LORA_WS[ws][0]), buf, 512)
+    names = buf.value.decode().split(" + ")
+    assert rc != 0 or all(n.startswith("ltx::") for n in names)
+    return rc, " + ".join(n[5:] for n in names)
+
+
+@pytest.fixture
+def lora_lib():
+    """the library with never dereferenced workspaces registered under made-up stream handles (the default
+    workspace, which GPU tests of the same process rely on, is not touched)"""
+    import ctypes
+    from ltx_amd import _lib
+    lib = _lib.load()
+    try:
+        for handle, nbytes in _LORA_WS.values():
+            assert lib.ltx_gemm_set_stream_workspace(ctypes.c_void_p(handle), ctypes.c_void_p(0x10000 if nbytes else 0),
+                                                     nbytes) == 0
+        yield lib
+    finally:
+        for handle, _ in _LORA_WS.values():
+            lib.ltx_gemm_set_stream_workspace(ctypes.c_void_p(handle), None, 0)
+
+
+def test_lora_describe_names_the_dispatched_kernels(lora_lib):
+    """ltx_lora_describe (host only: the plan every ltx_lora_* launcher launches from) over a table with a row for
+    every branch of every route at the smallest shape that takes it, at r = 16 and r = 64, and every rank on one
+    row per operation. With and without the split operand the kernels are the same."""
+    from ltx_amd import ops
+    for i, (op, M, N, K, opts, want) in enumerate(_LORA_ROUTES):
+        ranks = ops.LORA_RANKS if i == _LORA_ALL_RANKS[op] else (16, 64)
+        for r in ranks:
+            for split in ((False, True) if op in ("rows", "down") else (False,)):
+                assert _lora_describe(lora_lib, op, M, N, K, r, split=split, **opts) == (0, want.replace("{R}", str(r))), \
+                    (op, M, N, K, opts, r, split)
+    # r = 64 at (2048, 1536): the partials are 1.5 MiB, the 64-KiB workspace is too small for r = 8 too
+    assert _lora_describe(lora_lib, "rows", 2048, 0, 1536, 8, ws="small")[1] == "lora_rows_kernel<8, 4, 4>"
+    assert _lora_describe(lora_lib, "dy", 2048, 500, 0, 16)[0] != 0  # N % 512
+    assert _lora_describe(lora_lib, "rows", 2048, 0, 384, 16)[0] != 0                    # ltx_lora_rows wants K % 256
+    assert _lora_describe(lora_lib, "dy_dA", 2048, 2560, 512, 16, groups=3)[0] != 0       # grouped: N <= 2048
+    assert _lora_describe(lora_lib, "rows", 2048, 0, 512, 16, groups=5)[0] != 0
+
+
+def test_lora_ranks_are_the_librarys(lora_lib):
+    """ops.LORA_RANKS is exactly the set of ranks ltx_lora_describe accepts, for every operation; a rank outside
+    it is rejected by every *_workspace entry as well."""
+    import ctypes
+    from ltx_amd import ops
+    shapes = {"down": (48, 0, 128), "rows": (2048, 0, 512), "wgrad": (2048, 512, 0), "dy": (32, 512, 0),
+              "dy_dA": (2048, 512, 512)}
+    n = ctypes.c_int64(0)
+    for op, (M, N, K) in shapes.items():
+        assert tuple(r for r in range(0, 260) if _lora_describe(lora_lib, op, M, N, K, r)[0] == 0) == ops.LORA_RANKS
+    for r in list(range(0, 260)):
+        ok = r in ops.LORA_RANKS
+        assert (lora_lib.ltx_lora_dy_workspace(2048, 512, r, ctypes.byref(n)) == 0) == ok
+        assert (lora_lib.ltx_lora_dy_dA_workspace(2048, 512, 512, r, ctypes.byref(n)) == 0) == ok
+        assert (lora_lib.ltx_lora_dy_dA_grouped_workspace(2048, 512, 512, r, 3, ctypes.byref(n)) == 0) == ok
+
+
+def test_lora_dy_workspace_sizes(lora_lib):
+    """The three *_workspace entries against the formula written out: CS M RP + RS N RP (+ RS K RP) floats per
+    group, RP = max(r, 16), CS = N / 512, RS = ceil(M / (32 G)), G = 7 up to r = 16 and 4 above."""
+    import ctypes
+    from ltx_amd import ops
+    n = ctypes.c_int64(0)
+    cols = (512, 2048, 2560, 8192)
+    for r in ops.LORA_RANKS:
+        RP, G = max(r, 16), 7 if r <= 16 else 4
+        for M in (32, 2016, 2048, 14336):
+            RS = -(-M // (32 * G))
+            for N in cols:
+                dy = (N // 512) * M * RP + RS * N * RP
+                assert lora_lib.ltx_lora_dy_workspace(M, N, r, ctypes.byref(n)) == 0 and n.value == dy, (M, N, r)
+                for K in cols:
+                    assert lora_lib.ltx_lora_dy_dA_workspace(M, N, K, r, ctypes.byref(n)) == 0
+                    assert n.value == dy + RS * K * RP, (M, N, K, r)
+                    for groups in (1, 3, 4):
+                        assert lora_lib.ltx_lora_dy_dA_grouped_workspace(M, N, K, r, groups, ctypes.byref(n)) == 0
+                        assert n.value == groups * (dy + RS * K * RP), (M, N, K, r, groups)
+    assert lora_lib.ltx_lora_dy_dA_grouped_workspace(2048, 512, 512, 16, 5, ctypes.byref(n)) != 0
+
+
+def test_lora_python_gates_follow_the_plan(lora_lib, monkeypatch):
+    """The gates ops decides per call without asking the library, against the plan: lora_dy_da_fits(y, x, r) holds
+    exactly where ltx_lora_wgrad(x, w), given its workspace, takes the lora_dy_kernel<R, 2> route (so the merged
+    call is bitwise the separate ones), and lora_rows_gate only where ltx_lora_rows accepts the call."""
+    import torch
+    from ltx_amd import ops
+    monkeypatch.delenv("LTX_LORA_DY_DA", raising=False)
+    cols = (512, 2048, 2560, 8192)
+    for r in ops.LORA_RANKS:
+        for M in (2016, 2048, 8160, 8192):
+            for K in cols:
+                x = torch.empty(M, K, dtype=torch.bfloat16, device="meta")
+                # a workspace that holds the partials of every row (256 MiB at M = 8192, K = 8192, r = 128)
+                rc, names = _lora_describe(lora_lib, "wgrad", M, K, 0, r, ws="huge")
+                dy_route = rc == 0 and names == f"lora_dy_kernel<{r}, 2> + lora_dy_finish_kernel<{r}>"
+                for N in cols:
+                    y = torch.empty(M, N, dtype=torch.bfloat16, device="meta")
+                    assert ops.lora_dy_da_fits(y, x, r) == dy_route, (M, N, K, r)
+            for K in cols + (128, 384, 640):
+                assert ops.lora_rows_gate(M, K) == (M >= 8192 and K % 256 == 0)
+                if ops.lora_rows_gate(M, K):
+                    assert _lora_describe(lora_lib, "rows", M, 0, K, r)[0] == 0, (M, K, r)
+    assert not ops.lora_dy_da_fits(torch.empty(2048, 512, device="meta"), torch.empty(2048, 512, device="meta"), 24)
+    assert (ops.LORA_ROWS_MIN_M, ops.LORA_TOKEN_ROWS, ops.LORA_DY_COLS) == (8192, 2048, 512)
+
+
+_LORA_SWITCH_CHILD = """
+import ctypes, sys
+from ltx_amd import _lib
+lib = _lib.load()
+assert lib.ltx_gemm_set_workspace(ctypes.c_void_p(0x10000), 128 << 20) == 0
+buf = ctypes.create_string_buffer(512)
+op, M, N, K = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+assert lib.ltx_lora_describe(_lib.LORA_OP[op], M, N, K, 0, 0, 0, 16, 0, 0, None, buf, 512) == 0
+print(buf.value.decode())
+"""
+
+
+@pytest.mark.parametrize("env,call,want", [
+    ({}, ("wgrad", 2048, 512, 0), "ltx::lora_dy_kernel<16, 2> + ltx::lora_dy_finish_kernel<16>"),
+    ({"LTX_LORA_WGRAD_ROWS": "0"}, ("wgrad", 2048, 512, 0), "ltx::lora_wgrad_kernel<16> + ltx::lora_wgrad_finish_kernel"),
+    ({"LTX_LORA_ROWS_DY": "0"}, ("rows", 2048, 0, 512), "ltx::lora_rows_kernel<16, 4, 4>"),
+    ({"LTX_LORA_ROWS_FULL": "0"}, ("rows", 2048, 0, 512), "ltx::lora_dy_kernel<16, 1> + ltx::lora_dy_finish_kernel<16>"),
+])
+def test_lora_library_switches(env, call, want):
+    """LTX_LORA_WGRAD_ROWS / LTX_LORA_ROWS_DY / LTX_LORA_ROWS_FULL are read once per process, so each is asked in a
+    fresh one (host only)."""
+    import subprocess
+    import sys
+    names = ("LTX_LORA_WGRAD_ROWS", "LTX_LORA_ROWS_DY", "LTX_LORA_ROWS_FULL")
+    child_env = {k: v for k, v in os.environ.items() if k not in names}
+    child_env.update(env, PYTHONPATH=os.pathsep.join(p for p in sys.path if p))
+    out = subprocess.run([sys.executable, "-c", _LORA_SWITCH_CHILD, *map(str, call)], env=child_env, check=True,
+                         capture_output=True, text=True, timeout=120)
+    assert out.stdout.strip().splitlines()[-1] == want

@@ -1,6 +1,6 @@
 """Fingerprint of one step per model configuration (and, group `optim`, of three optimizer steps per
-optimizer condition; group `attn`, of direct attention calls per shape and LTX_ATTN_* switch), to hold a
-refactor to equality.
+optimizer condition; group `attn`, of direct attention calls per shape and LTX_ATTN_* switch; group `lora`, of
+direct adapter calls per route of csrc/lora_plan.h), to hold a refactor to equality.
 
     python tools/step_fingerprint.py run --pkg <dir that holds ltx_amd/> --group <name> --out fp.json
     python tools/step_fingerprint.py compare old.json new.json [--md table.md]
@@ -58,6 +58,20 @@ ATTN_SWITCHES = ["default", "XCD=0", "BWD1=0", "W8=0", "SKIP=0", "FWD1=0", "FWD1
                  "QSPLIT=0", "DKDV_W1=1", "DKDV_W1=0", "DQ_W1=1", "DQ_W1=0", "DQ_PIPE=0", "DQ_NBUF=3", "FWD_W1=1",
                  "FWD_PIPE=0", "FWD_F32SUM=0", "DKDV_PIPE=0", "DKDV_NBUF=3"]
 GROUPS["attn"] = ({}, [f"{'x'.join(str(int(v)) for v in shape)}/{sw}" for shape in ATTN_SHAPES for sw in ATTN_SWITCHES])
+
+
+def _lora_configs():
+    """group `lora`: one configuration per row of the adapter route table of tests/test_abi.py and rank it runs at"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_abi import _LORA_ALL_RANKS, _LORA_ROUTES
+    names = []
+    for i, (op, M, N, K, opts, _) in enumerate(_LORA_ROUTES):
+        for r in ((8, 16, 32, 64, 128) if i == _LORA_ALL_RANKS[op] else (16, 64)):
+            names.append(f"{i:02d}_{op}_{M}x{N}x{K}_g{opts.get('groups', 0)}_ws{opts.get('ws', 'big')}_r{r}")
+    return names
+
+
+GROUPS["lora"] = ({}, _lora_configs())
 
 
 def _sha(t):
@@ -267,6 +281,84 @@ def _attn_one(name, torch):
             "output": _sha(o), "loss": _sha(lse), "grads": {"dq": _sha(dq), "dk": _sha(dk), "dv": _sha(dv)}}
 
 
+def _lora_one(name, torch):
+    """The ops.lora_* calls of one route row on seeded inputs: "grads" holds the hash of every output (u, split, w,
+    dB, dA; overwriting and accumulating; the grouped rows into column views of wider buffers), "labels" what
+    ops.lora_kernel_label says each call launches, in call order (commits that have it; not compared)."""
+    from ltx_amd import ops
+    op, shape, g, ws, r = name.split("_", 1)[1].rsplit("_", 4)
+    (M, N, K), G, r = (int(v) for v in shape.split("x")), int(g[1:]), int(r[1:])
+    gen = torch.Generator(device="cpu").manual_seed(M * 7 + N + K + r)
+    bf = lambda *sh: torch.randn(*sh, generator=gen).bfloat16().cuda()  # noqa: E731
+    f32 = lambda *sh, scale=1.0: (torch.randn(*sh, generator=gen) * scale).cuda()  # noqa: E731
+    K2, n = ops.lora_k2(r), max(G, 1)
+    out, labels = {}, []
+    buf = ops._gemm_workspace("cuda:0")  # then the row's workspace on the stream: whole, 64 KiB of it, or none
+    nbytes = {"wsbig": ops.GEMM_WS_BYTES, "wssmall": 64 << 10, "wsNone": 0}[ws]
+    ops.call("ltx_gemm_set_stream_workspace", ops._s(), ops._p(buf) if nbytes else None, nbytes)
+
+    def label(*a, **k):
+        if hasattr(ops, "lora_kernel_label"):
+            labels.append(ops.lora_kernel_label(*a, **k))
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    try:
+        if op == "rows":
+            x, As = bf(M, K), [f32(r, K, scale=K ** -0.5) for _ in range(n)]
+            pieces = [ops.lora_pieces(A) for A in As]
+            if G:
+                ub, sb = torch.full((M, 2 * G * r), 3.0, device="cuda"), torch.full((M, 2 * G * K2), 7.0).bfloat16().cuda()
+                ops.lora_rows_grouped(x, pieces, r, alpha=0.5, out=ub[:, r:2 * r], split=True, split_out=sb[:, K2:2 * K2],
+                                      group_strides=(2 * r, 2 * K2))
+                label("rows", M, K=K, r=r, groups=G, split=True, ld_out=2 * G * r)
+                out.update(u=ub, split=sb, u_nosplit=ops.lora_rows_grouped(x, pieces, r, alpha=0.5))
+                label("rows", M, K=K, r=r, groups=G)
+            else:
+                out["u"], out["split"] = ops.lora_rows(x, pieces[0], r, alpha=0.5, split=True)
+                label("rows", M, K=K, r=r, split=True)
+                out["u_nosplit"] = ops.lora_rows(x, pieces[0], r, alpha=0.5)
+                label("rows", M, K=K, r=r)
+        elif op == "down":
+            x, A, Bm = bf(M, K), f32(n, r, K, scale=K ** -0.5), f32(K, r, scale=K ** -0.5)
+            out["u"], out["split"] = torch.zeros(n, M, r, device="cuda"), torch.zeros(n, M, K2).bfloat16().cuda()
+            ops.lora_down(x, A[0], alpha=0.5, out=out["u"][0], split=True, split_out=out["split"][0], groups=n,
+                          group_strides=(0, r * K, M * r, M * K2))
+            label("down", M, K=K, r=r, groups=G, split=True)
+            out["w_t"] = ops.lora_down(x, Bm, alpha=0.5, transposed=True)
+            label("down", M, K=K, r=r)
+        elif op == "wgrad":
+            y, u = bf(M, n * N), f32(M, n * r)
+            for key, tr in (("dw", False), ("dw_t", True)):
+                out[key] = ops.lora_wgrad(y[:, :N], u[:, :r], alpha=0.5, transpose_out=tr, groups=n, group_strides=(N, r))
+                acc = f32(*out[key].shape)
+                out[key + "_acc"] = ops.lora_wgrad(y[:, :N], u[:, :r], alpha=0.5, transpose_out=tr, out=acc,
+                                                   accumulate=True, groups=n, group_strides=(N, r))
+                for _ in range(2):
+                    label("wgrad", M, N=N, r=r, groups=G, ld_in=n * N, ld_w=n * r)
+        else:
+            y, x = bf(M, n * N), bf(M, K) if K else None
+            us, Bs = [f32(M, r) for _ in range(n)], [f32(N, r, scale=0.05) for _ in range(n)]
+            pieces = [ops.lora_pieces(Bm, transposed=True) for Bm in Bs]
+            for acc in (False, True):
+                dB, dA = [f32(N, r) for _ in range(n)], [f32(r, K) for _ in range(n)] if K else None
+                if G:
+                    w, sp = ops.lora_dy_grouped(y, us, pieces, r, 0.5, dB, x, dA, accumulate=acc, dA_accumulate=acc)
+                elif K:
+                    w, sp = ops.lora_dy(y, us[0], pieces[0], r, 0.5, dB[0], accumulate=acc, x=x, dA_out=dA[0],
+                                        dA_accumulate=acc)
+                else:
+                    w, sp = ops.lora_dy(y, us[0], pieces[0], r, 0.5, dB[0], accumulate=acc)
+                label(op, M, N=N, K=K, r=r, groups=G)
+                out.update({f"w{int(acc)}": w, f"split{int(acc)}": sp})
+                out.update({f"dB{int(acc)}.{i}": t for i, t in enumerate(dB)})
+                out.update({f"dA{int(acc)}.{i}": t for i, t in enumerate(dA or [])})
+        torch.cuda.synchronize()
+    finally:
+        ops.call("ltx_gemm_set_stream_workspace", ops._s(), ops._p(buf), ops.GEMM_WS_BYTES)
+    return {"kernels": [], "labels": labels, "peak_bytes": torch.cuda.max_memory_allocated(), "output": None,
+            "loss": None, "grads": {k: _sha(v) for k, v in sorted(out.items())}}
+
+
 def run(args):
     env, names = GROUPS[args.group]
     os.environ.update(env)
@@ -277,10 +369,11 @@ def run(args):
     from ltx_amd import _lib
     _lib.ensure_device("cuda:0")
     torch.cuda.set_device(0)
-    case = None if args.group in ("optim", "attn") else _2b_case() if args.group == "2b" else _tiny_case()
+    case = None if args.group in ("optim", "attn", "lora") else _2b_case() if args.group == "2b" else _tiny_case()
     out = {"pkg": os.path.dirname(os.path.abspath(ltx_amd.__file__)), "env": env, "configs": {}}
     for name in names:
-        rec = (_attn_one(name, torch) if args.group == "attn" else _optim_one(name, torch) if case is None
+        rec = (_attn_one(name, torch) if args.group == "attn" else _lora_one(name, torch) if args.group == "lora"
+               else _optim_one(name, torch) if case is None
                else _one(name, case, torch))
         out["configs"][f"{args.group}/{name}"] = rec
         gc.collect()

@@ -11,6 +11,7 @@
 //     kernels' result.
 // f32 throughout, fixed summation orders, no atomics.
 #include "common.h"
+#include "lora_plan.h"
 #include "ltx_hip.h"
 
 namespace ltx {
@@ -226,7 +227,7 @@ int ltx_dora_fold(const void* W, int64_t ldw, const float* A, int64_t lda, const
                   const float* m, float s, int64_t N, int64_t K, int64_t r, float* norm, float* c, void* w_eff,
                   int64_t ldo, float* sb_eff, void* stream) {
   LTX_CHECK_ARG(W && A && B && m && norm && c && w_eff && sb_eff && N > 0 && K > 0, "dora_fold: bad args");
-  LTX_CHECK_ARG(r == 8 || r == 16 || r == 32 || r == 64 || r == 128, "dora_fold: rank must be 8, 16, 32, 64 or 128");
+  LTX_CHECK_ARG(lora_rank_ok(r), "dora_fold: rank must be " LTX_LORA_RANK_TEXT);
   LTX_CHECK_ARG(K % 8 == 0 && ldw % 8 == 0 && ldo % 8 == 0 && lda % 4 == 0 && ldw >= K && ldo >= K && lda >= K,
                 "dora_fold: K and the bf16 strides must be %8, lda %4, every stride >= K");
   LTX_CHECK_ARG(((uintptr_t)W | (uintptr_t)w_eff | (uintptr_t)A) % 16 == 0, "dora_fold: operands must be 16-B aligned");

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lora_plan.h"
 #include "ltx_hip.h"
 
 namespace ltx {
@@ -341,11 +342,12 @@ __global__ __launch_bounds__(64 * NW) void lora_rows_kernel(const bf16_t* __rest
 // per row), and MFMA t (t = 0..7) takes element t, so its output column c stands for
 // n0 + 8c + t (a fixed permutation undone at the store). Block = 8 waves on the same 128
 // columns, interleaved row quads; the wave partials are reduced through LDS in wave order.
-// the token-sized paths of ltx_lora_rows and ltx_lora_wgrad (lora_dy.hip)
-bool lora_rows_dy(const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, float* out, int64_t ldo, int64_t M,
-                  int64_t K, int64_t r, float alpha, bf16_t* split, int64_t ld_split, int64_t K2, hipStream_t s);
-bool lora_wgrad_rows(const bf16_t* y, int64_t ldy, const float* u, int64_t ldu, float* dw, int64_t on, int64_t oj,
-                     int64_t M, int64_t N, int64_t r, float alpha, int accumulate, hipStream_t s);
+// the launches of ltx_lora_rows' and ltx_lora_wgrad's dY-family routes (lora_dy.hip)
+void lora_rows_dy(const LoraPlan& pl, const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, float* out,
+                  int64_t ldo, int64_t M, int64_t K, int64_t r, float alpha, bf16_t* split, int64_t ld_split, int64_t K2,
+                  hipStream_t s);
+void lora_wgrad_rows(const LoraPlan& pl, const bf16_t* y, int64_t ldy, const float* u, int64_t ldu, float* dw,
+                     int64_t on, int64_t oj, int64_t M, int64_t N, int64_t r, float alpha, int accumulate, hipStream_t s);
 
 template <int R>
 __global__ __launch_bounds__(512) void lora_wgrad_kernel(const bf16_t* __restrict__ y, int64_t ldy,
@@ -504,35 +506,19 @@ extern "C" int ltx_lora_down_grouped(const void* x, int64_t ldx, const float* Wr
   LTX_CHECK_ARG(!split || (K2 >= 3 * r && K2 % 64 == 0 && ld_split >= K2), "lora_down: split needs K2 >= 3r, %64");
   LTX_CHECK_ARG(K % 128 == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0, "lora_down: K %128, 16-B rows");
   LTX_CHECK_ARG(wk != 1 || (wj % 4 == 0 && ((uintptr_t)Wr % 16) == 0), "lora_down: W rows must be 16-B aligned");
-  // 32-row blocks for token-sized M (16-row blocks measured 26 vs 21 us at M = 14336); K split 8
-  // ways (512 threads) there: 19.7 vs 20.7 us (forward A), 18.6 vs 19.6 us (split B^T dgrad)
-  const bool big = M >= 8192;
-  // ranks above 32: one 32-wide rank slice per grid z
-  const dim3 grid((unsigned)(big ? (M + 31) / 32 : (M + 15) / 16), (unsigned)groups, (unsigned)(r > 32 ? r / 32 : 1));
+  LTX_CHECK_ARG(lora_rank_ok(r), "lora_down: rank must be " LTX_LORA_RANK_TEXT);
+  const LoraLaunch l = plan_lora_down(M, K, r, groups).l[0];
   hipStream_t s = (hipStream_t)stream;
-  bf16_t* sp = (bf16_t*)split;
-#define LTX_LORA_DOWN(RR)                                                                                      \
-  if (big && K % 256 == 0)                                                                                     \
-    hipLaunchKernelGGL((lora_down_kernel<RR, 2, 8>), grid, dim3(512), 0, s, (const bf16_t*)x, ldx, Wr, wj, wk,  \
-                       out, ldo, (int)M, (int)K, alpha, sp, ld_split, (int)K2, gx, gw, go, gs);                \
-  else if (big)                                                                                                \
-    hipLaunchKernelGGL((lora_down_kernel<RR, 2, 4>), grid, dim3(256), 0, s, (const bf16_t*)x, ldx, Wr, wj, wk,  \
-                       out, ldo, (int)M, (int)K, alpha, sp, ld_split, (int)K2, gx, gw, go, gs);                \
-  else if (K % 256 == 0)                                                                                       \
-    hipLaunchKernelGGL((lora_down_kernel<RR, 1, 8>), grid, dim3(512), 0, s, (const bf16_t*)x, ldx, Wr, wj, wk,  \
-                       out, ldo, (int)M, (int)K, alpha, sp, ld_split, (int)K2, gx, gw, go, gs);                \
-  else                                                                                                         \
-    hipLaunchKernelGGL((lora_down_kernel<RR, 1, 4>), grid, dim3(256), 0, s, (const bf16_t*)x, ldx, Wr, wj, wk,  \
-                       out, ldo, (int)M, (int)K, alpha, sp, ld_split, (int)K2, gx, gw, go, gs);
-  switch (r) {
-    case 8: LTX_LORA_DOWN(8) break;
-    case 16: LTX_LORA_DOWN(16) break;
-    case 32: LTX_LORA_DOWN(32) break;
-    case 64: LTX_LORA_DOWN(64) break;
-    case 128: LTX_LORA_DOWN(128) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_down: rank must be 8, 16, 32, 64 or 128");
-  }
-#undef LTX_LORA_DOWN
+  with_rank(r, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    with_value<1, 2>(l.a[0], [&](auto rg) {
+      with_value<4, 8>(l.a[1], [&](auto kw) {
+        hipLaunchKernelGGL((lora_down_kernel<R, decltype(rg)::value, decltype(kw)::value>), grid_of(l), dim3(l.threads), 0,
+                           s, (const bf16_t*)x, ldx, Wr, wj, wk, out, ldo, (int)M, (int)K, alpha, (bf16_t*)split, ld_split,
+                           (int)K2, gx, gw, go, gs);
+      });
+    });
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
@@ -546,8 +532,7 @@ extern "C" int ltx_lora_down(const void* x, int64_t ldx, const float* Wr, int64_
 
 extern "C" int ltx_lora_pieces(const float* src, int64_t rs, int64_t cs, int64_t r, int64_t K, void* out,
                                int64_t ldo, void* stream) {
-  LTX_CHECK_ARG(src && out && K > 0 && ldo >= K && (r == 8 || r == 16 || r == 32 || r == 64 || r == 128),
-                "lora_pieces: bad args (rank 8, 16, 32, 64 or 128)");
+  LTX_CHECK_ARG(src && out && K > 0 && ldo >= K && lora_rank_ok(r), "lora_pieces: bad args (rank " LTX_LORA_RANK_TEXT ")");
   const int RP = r >= 16 ? (int)r : 16;
   const int64_t total = (int64_t)RP * K;
   int64_t g = (total + 255) / 256;
@@ -561,34 +546,21 @@ extern "C" int ltx_lora_pieces(const float* src, int64_t rs, int64_t cs, int64_t
 extern "C" int ltx_lora_rows(const void* x, int64_t ldx, const void* w3, int64_t ldw, float* out, int64_t ldo,
                              int64_t M, int64_t K, int64_t r, float alpha, void* split, int64_t ld_split, int64_t K2,
                              void* stream) {
-  LTX_CHECK_ARG(x && w3 && out && M > 0 && K > 0 && ldo >= r, "lora_rows: bad args");
-  LTX_CHECK_ARG(K % 256 == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldw % 8 == 0 &&
-                    ((uintptr_t)w3 % 16) == 0 && ldw >= K,
-                "lora_rows: K % 256, 16-B aligned rows of x and of the pieces");
-  LTX_CHECK_ARG((int64_t)ldx * 2 * (M - 1) + 2 * K < ((int64_t)1 << 32) && (int64_t)ldw * 2 * 3 * (r > 32 ? r : 32) < ((int64_t)1 << 32),
-                "lora_rows: 32-bit DMA offsets");
-  LTX_CHECK_ARG(!split || (K2 >= 3 * r && K2 % 64 == 0 && ld_split >= K2), "lora_rows: split needs K2 >= 3r, %64");
+  const RowsCall c{M, K, r, ldx, ldw, ldo, (uintptr_t)x, (uintptr_t)w3, (uintptr_t)out, split != nullptr,
+                   (uintptr_t)split, ld_split, K2};
+  if (const char* err = lora_rows_check(c)) return fail(LTX_ERR_BAD_ARG, err);
   hipStream_t s = (hipStream_t)stream;
-  bf16_t* sp = (bf16_t*)split;
-  if (lora_rows_dy((const bf16_t*)x, ldx, (const bf16_t*)w3, ldw, out, ldo, M, K, r, alpha, sp, ld_split, K2, s)) {
-    LTX_LAUNCH_CHECK();
-    return LTX_OK;
+  const LoraPlan pl = plan_lora_rows(c, lora_site(s));
+  if (pl.l[0].k == LK_ROWS) {
+    with_rank(r, [&](auto rank) {
+      hipLaunchKernelGGL((lora_rows_kernel<decltype(rank)::value, 4, 4>), grid_of(pl.l[0]), dim3(pl.l[0].threads), 0, s,
+                         (const bf16_t*)x, ldx, (const bf16_t*)w3, ldw, out, ldo, (int)M, (int)K, alpha, (bf16_t*)split,
+                         ld_split, (int)K2);
+    });
+  } else {
+    lora_rows_dy(pl, (const bf16_t*)x, ldx, (const bf16_t*)w3, ldw, out, ldo, M, K, r, alpha, (bf16_t*)split, ld_split,
+                 K2, s);
   }
-  const dim3 grid((unsigned)((M + 31) / 32), (unsigned)(r > 32 ? r / 32 : 1));  // y: 32-wide rank slices
-  // 4 waves x K/4 per 32-row block, 4-slot ring: 16.3 us at M = 14336, K = 2048, r = 16 against
-  // 19.9 us for lora_down_kernel (8 waves x K/8 with a 3-slot ring: 17.8 us)
-#define LTX_LORA_ROWS(RR)                                                                             \
-  hipLaunchKernelGGL((lora_rows_kernel<RR, 4, 4>), grid, dim3(256), 0, s, (const bf16_t*)x, ldx,     \
-                     (const bf16_t*)w3, ldw, out, ldo, (int)M, (int)K, alpha, sp, ld_split, (int)K2);
-  switch (r) {
-    case 8: LTX_LORA_ROWS(8) break;
-    case 16: LTX_LORA_ROWS(16) break;
-    case 32: LTX_LORA_ROWS(32) break;
-    case 64: LTX_LORA_ROWS(64) break;
-    case 128: LTX_LORA_ROWS(128) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_rows: rank must be 8, 16, 32, 64 or 128");
-  }
-#undef LTX_LORA_ROWS
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
@@ -602,54 +574,25 @@ extern "C" int ltx_lora_wgrad_grouped(const void* y, int64_t ldy, const float* u
   LTX_CHECK_ARG(N % 8 == 0 && ldy % 8 == 0 && ((uintptr_t)y % 16) == 0, "lora_wgrad: y rows must be 16-B aligned");
   LTX_CHECK_ARG(groups >= 1 && groups <= 65535 && gy % 8 == 0 && (groups == 1 || gd >= N * r),
                 "lora_wgrad: groups in [1, 65535], 16-B aligned y groups, disjoint outputs");
+  LTX_CHECK_ARG(lora_rank_ok(r), "lora_wgrad: rank must be " LTX_LORA_RANK_TEXT);
   hipStream_t s = (hipStream_t)stream;
-  if (groups == 1 && lora_wgrad_rows((const bf16_t*)y, ldy, u, ldu, dw, on, oj, M, N, r, alpha, accumulate, s)) {
+  const LoraPlan pl =
+      plan_lora_wgrad(WgradCall{M, N, r, ldy, ldu, groups, gd, (uintptr_t)dw}, lora_site(s));
+  if (pl.l[0].k != LK_WGRAD) {
+    lora_wgrad_rows(pl, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, M, N, r, alpha, accumulate, s);
     LTX_LAUNCH_CHECK();
     return LTX_OK;
   }
-  // ~512 blocks of 128 columns x >= 512 rows (8 waves x 4-quad steps): enough waves to stream y.
-  // ~512 blocks (two per CU): 17.9 us vs 20.0 us with 256 at M = 14336, N = 2048, r = 16. Splits
-  // of >= 256 rows in multiples of 32 (a wave's row quads stay aligned; the last 128-row step of a
-  // split may be partial): M = 14336 -> 32 splits of 448 rows = exactly 512 blocks
-  const int nb = (int)((N + 127) / 128);
-  const int target = 512;
-  int splits = (int)((target + nb * groups - 1) / (nb * groups));
-  const int max_splits = (int)((M + 255) / 256);
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int rps = (int)((M + splits - 1) / splits);
-  rps = (rps + 31) / 32 * 32;
-  splits = (int)((M + rps - 1) / rps);
-  // S > 1: per-split partials in the stream's workspace (caller-owned, stream-ordered), summed in
-  // order by the finish kernel; with no room for them, one split (each block owns its outputs)
-  float* part = nullptr;
-  if (splits > 1) {
-    size_t ws = 0;
-    float* w = stream_workspace(s, &ws);
-    const bool aligned = ((uintptr_t)dw % 16) == 0 && (N * r) % 4 == 0 && (groups == 1 || gd % 4 == 0);
-    if (w != nullptr && aligned && (size_t)groups * splits * N * r * sizeof(float) <= ws) {
-      part = w;
-    } else {
-      splits = 1;
-      rps = (int)M;
-    }
-  }
-  // ranks above 32: r / 32 rank slices per 128 columns (consecutive blockIdx.x)
-  const dim3 grid((unsigned)(nb * (r > 32 ? r / 32 : 1)), (unsigned)splits, (unsigned)groups);
+  float* part = pl.ws;  // per-split partials, summed in split order by the finish kernel (pl.l[1])
   const int acc = accumulate ? 1 : 0;
-  switch (r) {
-    case 8: hipLaunchKernelGGL(lora_wgrad_kernel<8>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
-    case 16: hipLaunchKernelGGL(lora_wgrad_kernel<16>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
-    case 32: hipLaunchKernelGGL(lora_wgrad_kernel<32>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
-    case 64: hipLaunchKernelGGL(lora_wgrad_kernel<64>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
-    case 128: hipLaunchKernelGGL(lora_wgrad_kernel<128>, grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu, dw, on, oj, (int)M, (int)N, rps, alpha, gy, gu, gd, part, acc); break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_wgrad: rank must be 8, 16, 32, 64 or 128");
-  }
+  with_rank(r, [&](auto rank) {
+    hipLaunchKernelGGL(lora_wgrad_kernel<decltype(rank)::value>, grid_of(pl.l[0]), dim3(pl.l[0].threads), 0, s, (const bf16_t*)y,
+                       ldy, u, ldu, dw, on, oj, (int)M, (int)N, pl.rps, alpha, gy, gu, gd, part, acc);
+  });
   LTX_LAUNCH_CHECK();
-  if (part != nullptr) {
-    const int64_t npg = N * r;
-    const dim3 gf((unsigned)((npg / 4 + 255) / 256), (unsigned)groups);
-    hipLaunchKernelGGL(lora_wgrad_finish_kernel, gf, dim3(256), 0, s, part, dw, npg, splits, gd, acc);
+  if (pl.n > 1) {
+    hipLaunchKernelGGL(lora_wgrad_finish_kernel, grid_of(pl.l[1]), dim3(pl.l[1].threads), 0, s, part, dw, N * r,
+                       pl.splits, gd, acc);
     LTX_LAUNCH_CHECK();
   }
   return LTX_OK;
@@ -659,4 +602,48 @@ extern "C" int ltx_lora_wgrad(const void* y, int64_t ldy, const float* u, int64_
                               int64_t oj, int64_t M, int64_t N, int64_t r, float alpha, int accumulate,
                               void* stream) {
   return ltx_lora_wgrad_grouped(y, ldy, u, ldu, dw, on, oj, M, N, r, alpha, accumulate, 1, 0, 0, 0, stream);
+}
+
+// The kernels an adapter entry would launch for this call on `stream` (include/ltx_hip.h): the plan
+// the launchers launch from, with every pointer taken as 16-B aligned. Nothing is launched.
+extern "C" int ltx_lora_describe(int op, int64_t M, int64_t N, int64_t K, int64_t ld_in, int64_t ld_w, int64_t ld_out,
+                                 int64_t r, int64_t groups, int split, void* stream, char* buf, int64_t len) {
+  LTX_CHECK_ARG(buf && len > 0 && M > 0 && N >= 0 && K >= 0 && groups >= 0, "lora_describe: bad args");
+  LTX_CHECK_ARG(lora_rank_ok(r), "lora_describe: rank must be " LTX_LORA_RANK_TEXT);
+  const int64_t G = groups ? groups : 1, K2 = (3 * r + 63) / 64 * 64;
+  const uintptr_t p = 16;  // any aligned, non-null address
+  const LoraSite e = lora_site((hipStream_t)stream);
+  LoraPlan pl;
+  switch (op) {
+    case LTX_LORA_OP_DOWN:
+      LTX_CHECK_ARG(K > 0 && K % 128 == 0 && G <= 65535, "lora_describe: down needs K % 128 == 0");
+      pl = plan_lora_down(M, K, r, G);
+      break;
+    case LTX_LORA_OP_ROWS: {
+      LTX_CHECK_ARG(groups <= LORA_MAX_GROUPS, "lora_describe: rows takes up to 4 groups");
+      const RowsCall c{M, K, r, ld_in ? ld_in : K, ld_w ? ld_w : K, ld_out ? ld_out : G * r, p, p, p, split != 0,
+                       p, G * K2, K2};
+      if (const char* err = lora_rows_check(c)) return fail(LTX_ERR_BAD_ARG, err);
+      pl = plan_lora_rows(c, e, groups, r, K2);
+      break;
+    }
+    case LTX_LORA_OP_WGRAD:
+      LTX_CHECK_ARG(N > 0 && N % 8 == 0 && ld_in % 8 == 0 && G <= 65535, "lora_describe: wgrad needs N, ldy % 8 == 0");
+      pl = plan_lora_wgrad(WgradCall{M, N, r, ld_in ? ld_in : N, ld_w ? ld_w : r, G, N * r, p}, e);
+      break;
+    case LTX_LORA_OP_DY:
+    case LTX_LORA_OP_DY_DA: {
+      const int64_t Kx = op == LTX_LORA_OP_DY_DA ? K : 0;
+      LTX_CHECK_ARG(groups <= LORA_MAX_GROUPS && (groups == 0 || Kx > 0) && (op == LTX_LORA_OP_DY || K > 0),
+                    "lora_describe: dy takes no groups, dy_dA up to 4 and K > 0");
+      const DyCall c{M, N, Kx, r, groups, ld_in ? ld_in : G * N, r, ld_w ? ld_w : N, Kx, ld_out ? ld_out : G * r, r,
+                     G * K2, K2, K2, r, 1, 1, Kx, p, p, p, p, p};
+      if (const char* err = lora_dy_check(c)) return fail(LTX_ERR_BAD_ARG, std::string("lora_describe: ") + err);
+      pl = plan_lora_dy(M, N, Kx, r, groups);
+      break;
+    }
+    default: return fail(LTX_ERR_BAD_ARG, "lora_describe: unknown operation");
+  }
+  describe_lora_plan(pl, r, buf, (size_t)len);
+  return LTX_OK;
 }

@@ -7,6 +7,7 @@
 //   ltx_lora_up_masked_add   dx += g * c * sum_g keep_g * (w_g . A_g), the adapter's input-gradient
 //                            term that cannot ride the dgrad GEMM's K extension under a mask
 #include "common.h"
+#include "lora_plan.h"
 #include "ltx_hip.h"
 #include "philox.h"
 
@@ -177,18 +178,11 @@ extern "C" int ltx_lora_up_masked_add(void* dx, int64_t lddx, const float* w, in
   LTX_CHECK_ARG(grid.y <= 65535, "lora_up_masked_add: M <= 64 * 65535");
   hipStream_t s = (hipStream_t)stream;
   const uint32_t k0 = (uint32_t)(key & 0xffffffffu), k1 = (uint32_t)(key >> 32);
-#define LTX_MASKED_ADD(RR)                                                                                         \
-  hipLaunchKernelGGL(lora_up_masked_add_kernel<RR>, grid, dim3(256), 0, s, (bf16_t*)dx, lddx, w, ldw, gr, lda,   \
-                     (int)groups, (int)M, (int)K, k0, k1, (uint32_t)T, c, (const int16_t*)gq, ldg);
-  switch (r) {
-    case 8: LTX_MASKED_ADD(8) break;
-    case 16: LTX_MASKED_ADD(16) break;
-    case 32: LTX_MASKED_ADD(32) break;
-    case 64: LTX_MASKED_ADD(64) break;
-    case 128: LTX_MASKED_ADD(128) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_up_masked_add: rank must be 8, 16, 32, 64 or 128");
-  }
-#undef LTX_MASKED_ADD
+  LTX_CHECK_ARG(lora_rank_ok(r), "lora_up_masked_add: rank must be " LTX_LORA_RANK_TEXT);
+  with_rank(r, [&](auto rank) {
+    hipLaunchKernelGGL(lora_up_masked_add_kernel<decltype(rank)::value>, grid, dim3(256), 0, s, (bf16_t*)dx, lddx, w, ldw,
+                       gr, lda, (int)groups, (int)M, (int)K, k0, k1, (uint32_t)T, c, (const int16_t*)gq, ldg);
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

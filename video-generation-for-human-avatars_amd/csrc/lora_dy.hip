@@ -31,17 +31,14 @@
 #include <cstdlib>
 
 #include "attention_common.h"
+#include "lora_plan.h"
 #include "ltx_hip.h"
 
 namespace ltx {
 
-#ifndef LTX_RF_NR
-#define LTX_RF_NR 5
-#endif
 namespace {
-constexpr int DY_NR = 4;     // ring slots per wave
-constexpr int DY_COLS = 512; // columns per block
-constexpr int DY_MAXCS = 4;  // column splits a MODE-6 pass sums its u from (N <= 2048; MODE 14: per loop trip)
+constexpr int DY_NR = 4;  // ring slots per wave
+// DY_COLS columns per block, DY_MAXCS column splits a MODE-6 pass sums its u from, dy_g / dy_nsl: lora_plan.h.
 // A block works on one rank slice of DY_SW(r) <= 32 columns of the adapter: the whole rank up to
 // r = 32, so dY is streamed from HBM once; ranks 64 / 128 run 2 / 4 slices per dY tile as
 // consecutive blockIdx.x of the same launch, each streaming the tile again (at 6r FLOP/B those
@@ -51,9 +48,6 @@ constexpr int DY_MAXCS = 4;  // column splits a MODE-6 pass sums its u from (N <
 // 8 . 32 . (32 G + 4) . 4 B, must fit the ring plus the u^T area they overlay (147,968 B at G = 4;
 // G = 7 would need 236,544 B), and 4 divides config A's 448 row groups where 3 would not.
 constexpr int dy_sw(int r) { return r <= 16 ? 16 : 32; }
-constexpr int dy_g(int r) { return r <= 16 ? 7 : 4; }
-constexpr int dy_nsl(int r) { return r <= 32 ? 1 : r / 32; }
-constexpr bool dy_rank_ok(int64_t r) { return r == 8 || r == 16 || r == 32 || r == 64 || r == 128; }
 }  // namespace
 
 // MODE: bit 0 the w product, bit 1 the dB product. MODE 2 is ltx_lora_wgrad's token-sized path
@@ -81,7 +75,6 @@ __global__ __launch_bounds__(512) void lora_dy_kernel(const bf16_t* __restrict__
 }
 
 // Per-group operands of the grouped launches (kernel arguments by value; G <= LORA_MAX_GROUPS)
-constexpr int LORA_MAX_GROUPS = 4;
 struct DyGroupPtrs {
   const float* u[LORA_MAX_GROUPS];
   const bf16_t* w3[LORA_MAX_GROUPS];
@@ -253,244 +246,128 @@ __global__ __launch_bounds__(512) void lora_rows_full_grouped_kernel(const bf16_
 #undef DY_BY
 }
 
-// ltx_lora_wgrad's token-sized path (called from lora.hip): dw (+)= alpha . Y^T . u through the
-// dB product of lora_dy_kernel (bf16 matrix core, u split into exact hi / mid / lo pieces) and the
-// dB half of the finish kernel. lora_wgrad_kernel spends ~9 us of f32 MFMA issue on the same
-// product at M = 14336, N = 2048, r = 16. Returns false (nothing launched) where it does not apply;
-// LTX_LORA_WGRAD_ROWS=0 at load keeps lora_wgrad_kernel everywhere.
-bool lora_wgrad_rows(const bf16_t* y, int64_t ldy, const float* u, int64_t ldu, float* dw, int64_t on, int64_t oj,
-                     int64_t M, int64_t N, int64_t r, float alpha, int accumulate, hipStream_t s) {
-  static const int enabled = [] {
-    const char* e = getenv("LTX_LORA_WGRAD_ROWS");
-    return e ? atoi(e) : 1;
-  }();
-  if (!enabled || M < 2048 || M % 32 != 0 || N % DY_COLS != 0 || !dy_rank_ok(r)) return false;
-  if (ldy % 8 != 0 || ((uintptr_t)y % 16) != 0 || ldy * 2 * 32 >= ((int64_t)1 << 32) || ldu < r) return false;
-  const int64_t RP = r >= 16 ? r : 16;
-  const int DY_G = dy_g((int)r);
-  const int RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
-  size_t ws = 0;
-  float* pb = stream_workspace(s, &ws);
-  if (pb == nullptr || (size_t)RS * N * RP * sizeof(float) > ws) return false;
-  const dim3 grid((unsigned)(N / DY_COLS * dy_nsl((int)r)), (unsigned)RS);
-  const dim3 g2((unsigned)((N * r + 63) / 64));
-#define LTX_LORA_WG(RR)                                                                                       \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 2>), grid, dim3(512), 0, s, y, ldy, u, ldu, nullptr, (int64_t)0, \
-                     nullptr, pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f);                           \
-  hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), g2, dim3(256), 0, s, nullptr, 0, pb, RS, (int)M, (int)N,    \
-                     alpha, nullptr, (int64_t)0, nullptr, (int64_t)0, 0, dw, on, oj, accumulate, 0, 1 << 30,   \
-                     (const float*)nullptr, 0, 1.f, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
-  switch (r) {
-    case 8: LTX_LORA_WG(8) break;
-    case 16: LTX_LORA_WG(16) break;
-    case 32: LTX_LORA_WG(32) break;
-    case 64: LTX_LORA_WG(64) break;
-    default: LTX_LORA_WG(128) break;
-  }
-#undef LTX_LORA_WG
-  return true;
+// ---- launchers: every route, grid and offset below comes from the call's LoraPlan (lora_plan.h)
+
+// lora_dy_finish_kernel over the partials of pl.dy in pl.ws (N, K: the columns of its dB / dA blocks): w and
+// its split operand, dB, dA, each null where the route has none
+template <int R>
+static void launch_dy_finish(const LoraPlan& pl, hipStream_t s, int64_t M, int64_t N, int64_t K, float alpha, float* w,
+                             int64_t ldw, bf16_t* split, int64_t lds, int64_t K2, float* dw = nullptr, int64_t on = 0,
+                             int64_t oj = 0, int acc = 0, float alpha_a = 1.f, float* dwa = nullptr, int64_t ona = 0,
+                             int64_t oja = 0, int acc_a = 0) {
+  const DyLayout& d = pl.dy;
+  const LoraLaunch& l = pl.l[pl.n - 1];
+  hipLaunchKernelGGL((lora_dy_finish_kernel<R>), grid_of(l), dim3(l.threads), 0, s, d.gpw ? pl.ws + d.pw : nullptr,
+                     d.gpw ? d.CS : 0, d.gpb ? pl.ws + d.pb : nullptr, d.gpb ? d.RS : 0, (int)M, (int)N, alpha, w, ldw,
+                     split, lds, (int)K2, dw, on, oj, acc, d.nwb, d.finish_nbb(),
+                     (const float*)(d.gpa ? pl.ws + d.pa : nullptr), (int)K, alpha_a, dwa, ona, oja, acc_a);
 }
 
-// ltx_lora_rows' token-sized path (called from lora.hip): out = alpha . x . A^T (and its split
-// operand) through the w product of lora_dy_kernel (MODE 1: eight waves x 64 columns per block,
-// column-split partials in the stream's workspace) and the w half of the finish kernel. Returns
-// false (nothing launched) where it does not apply; LTX_LORA_ROWS_DY=0 at load keeps
-// lora_rows_kernel.
-bool lora_rows_dy(const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, float* out, int64_t ldo, int64_t M,
-                  int64_t K, int64_t r, float alpha, bf16_t* split, int64_t ld_split, int64_t K2, hipStream_t s) {
-  static const int enabled = [] {
-    const char* e = getenv("LTX_LORA_ROWS_DY");
-    return e ? atoi(e) : 1;
-  }();
-  if (!enabled || M < 2048 || M % 32 != 0 || K % DY_COLS != 0 || !dy_rank_ok(r)) return false;
-  if (ldx % 8 != 0 || ((uintptr_t)x % 16) != 0 || ldx * 2 * 32 >= ((int64_t)1 << 32)) return false;
-  if (ldw % 8 != 0 || ((uintptr_t)w3 % 16) != 0 || ldw < K) return false;
-  if (ldo % 4 != 0 || ((uintptr_t)out % 16) != 0) return false;
-  if (split && (ld_split % 4 != 0 || ((uintptr_t)split % 8) != 0 || K2 < 3 * r || (K2 - 3 * r) % 4 != 0)) return false;
-  // K = 512 / 1024 / 2048: the whole contraction per block (lora_rows_full_kernel, no finish);
-  // LTX_LORA_ROWS_FULL=0 at load keeps the column-split pass + finish
-  static const int full = [] {
-    const char* e = getenv("LTX_LORA_ROWS_FULL");
-    return e ? atoi(e) : 1;
-  }();
-  if (full && (K == 512 || K == 1024 || K == 2048)) {
-    constexpr int RG = 2, NRF = LTX_RF_NR;
-    const dim3 gf((unsigned)((M + RG * 32 - 1) / (RG * 32)), (unsigned)(r > 16 ? r / 16 : 1));  // y: rank slices
-#define LTX_LORA_RF(RR, CHH)                                                                                  \
-  hipLaunchKernelGGL((lora_rows_full_kernel<RR, RG, CHH, NRF>), gf, dim3(512), 0, s, x, ldx, w3, ldw, out, ldo, (int)M, \
-                     alpha, split, ld_split, (int)K2)
-    const int ch = (int)(K / 512);
-#define LTX_LORA_RFC(RR) \
-  if (ch == 1) LTX_LORA_RF(RR, 1); else if (ch == 2) LTX_LORA_RF(RR, 2); else LTX_LORA_RF(RR, 4)
-    switch (r) {
-      case 8: LTX_LORA_RFC(8); break;
-      case 16: LTX_LORA_RFC(16); break;
-      case 32: LTX_LORA_RFC(32); break;
-      case 64: LTX_LORA_RFC(64); break;
-      default: LTX_LORA_RFC(128); break;
+// ltx_lora_wgrad's token-sized route (called from lora.hip): dw (+)= alpha . Y^T . u through the dB
+// product of lora_dy_kernel (bf16 matrix core, u split into exact hi / mid / lo pieces) and the dB
+// half of the finish kernel, the row-split partials in the stream's workspace.
+void lora_wgrad_rows(const LoraPlan& pl, const bf16_t* y, int64_t ldy, const float* u, int64_t ldu, float* dw,
+                     int64_t on, int64_t oj, int64_t M, int64_t N, int64_t r, float alpha, int accumulate, hipStream_t s) {
+  with_rank(r, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    hipLaunchKernelGGL((lora_dy_kernel<R, 2>), grid_of(pl.l[0]), dim3(pl.l[0].threads), 0, s, y, ldy, u, ldu, nullptr,
+                       (int64_t)0, nullptr, pl.ws + pl.dy.pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f);
+    launch_dy_finish<R>(pl, s, M, N, 0, alpha, nullptr, 0, nullptr, 0, 0, dw, on, oj, accumulate);
+  });
+}
+
+// ltx_lora_rows' token-sized routes (called from lora.hip): out = alpha . x . A^T and its split
+// operand, either with the whole contraction inside one block (lora_rows_full_kernel) or through the
+// w product of lora_dy_kernel (MODE 1: eight waves x 64 columns per block, column-split partials in
+// the stream's workspace) and the w half of the finish kernel.
+void lora_rows_dy(const LoraPlan& pl, const bf16_t* x, int64_t ldx, const bf16_t* w3, int64_t ldw, float* out,
+                  int64_t ldo, int64_t M, int64_t K, int64_t r, float alpha, bf16_t* split, int64_t ld_split, int64_t K2,
+                  hipStream_t s) {
+  const LoraLaunch& l = pl.l[0];
+  with_rank(r, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    if (l.k == LK_ROWS_FULL) {
+      with_value<1, 2, 4>(l.a[1], [&](auto ch) {
+        hipLaunchKernelGGL((lora_rows_full_kernel<R, RF_RG, decltype(ch)::value, LTX_RF_NR>), grid_of(l), dim3(l.threads),
+                           0, s, x, ldx, w3, ldw, out, ldo, (int)M, alpha, split, ld_split, (int)K2);
+      });
+      return;
     }
-#undef LTX_LORA_RFC
-#undef LTX_LORA_RF
-    return true;
-  }
-  const int64_t RP = r >= 16 ? r : 16;
-  const int DY_G = dy_g((int)r);
-  const int CS = (int)(K / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
-  size_t ws = 0;
-  float* pw = stream_workspace(s, &ws);
-  if (pw == nullptr || (size_t)CS * M * RP * sizeof(float) > ws) return false;
-  const dim3 grid((unsigned)(CS * dy_nsl((int)r)), (unsigned)RS);
-  const dim3 g2((unsigned)((M * (r / 4) + 255) / 256));
-  const int nwb = (int)g2.x;
-#define LTX_LORA_RW(RR)                                                                                      \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 1>), grid, dim3(512), 0, s, x, ldx, nullptr, (int64_t)0, w3, ldw, pw, \
-                     nullptr, (int)M, (int)K, (const float*)nullptr, 0, 1.f);                             \
-  hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), g2, dim3(256), 0, s, pw, CS, nullptr, 0, (int)M, (int)K,    \
-                     alpha, out, ldo, split, ld_split, (int)K2, nullptr, (int64_t)0, (int64_t)0, 0, nwb, 1 << 30, \
-                     (const float*)nullptr, 0, 1.f, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
-  switch (r) {
-    case 8: LTX_LORA_RW(8) break;
-    case 16: LTX_LORA_RW(16) break;
-    case 32: LTX_LORA_RW(32) break;
-    case 64: LTX_LORA_RW(64) break;
-    default: LTX_LORA_RW(128) break;
-  }
-#undef LTX_LORA_RW
-  return true;
+    hipLaunchKernelGGL((lora_dy_kernel<R, 1>), grid_of(l), dim3(l.threads), 0, s, x, ldx, nullptr, (int64_t)0, w3, ldw,
+                       pl.ws + pl.dy.pw, nullptr, (int)M, (int)K, (const float*)nullptr, 0, 1.f);
+    launch_dy_finish<R>(pl, s, M, K, 0, alpha, out, ldo, split, ld_split, K2);
+  });
 }
 
-extern "C" int ltx_lora_dy_workspace(int64_t M, int64_t N, int64_t r, int64_t* floats) {
-  LTX_CHECK_ARG(floats && M > 0 && N > 0 && dy_rank_ok(r), "lora_dy_workspace: bad args (rank 8, 16, 32, 64 or 128)");
-  const int64_t RP = r >= 16 ? r : 16;
-  const int64_t DY_G = dy_g((int)r);
-  const int64_t CS = N / DY_COLS, RS = (M + DY_G * 32 - 1) / (DY_G * 32);
-  *floats = CS * M * RP + RS * N * RP;
+static int dy_workspace(const char* who, int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups, bool ok,
+                        int64_t* floats) {
+  if (!(ok && floats && M > 0 && N > 0 && lora_rank_ok(r)))
+    return fail(LTX_ERR_BAD_ARG, std::string(who) + ": bad args (rank " LTX_LORA_RANK_TEXT ")");
+  *floats = dy_layout(M, N, K, r, groups).total;
   return LTX_OK;
 }
+extern "C" int ltx_lora_dy_workspace(int64_t M, int64_t N, int64_t r, int64_t* floats) {
+  return dy_workspace("lora_dy_workspace", M, N, 0, r, 1, true, floats);
+}
+extern "C" int ltx_lora_dy_dA_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t* floats) {
+  return dy_workspace("lora_dy_dA_workspace", M, N, K, r, 1, K > 0, floats);
+}
+extern "C" int ltx_lora_dy_dA_grouped_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups,
+                                                int64_t* floats) {
+  LTX_CHECK_ARG(groups >= 1 && groups <= LORA_MAX_GROUPS, "lora_dy_dA_grouped_workspace: 1 to 4 groups");
+  return dy_workspace("lora_dy_dA_workspace", M, N, K, r, groups, K > 0, floats);
+}
 
+// ltx_lora_dy_dA: the dY pass (w and dB partials), the x pass reading w from those partials, and one finish
+// for w / split, dB and dA. Every output is bitwise what ltx_lora_dy followed by ltx_lora_wgrad(x, w, alpha_a)
+// produces (dA: where that takes its token-sized route, M >= LORA_TOKEN_ROWS). ltx_lora_dy is the same
+// without x (K = 0): the dY pass and the finish.
+static int lora_dy_entry(const char* who, bool dA, const void* y, int64_t ldy, const float* u, int64_t ldu,
+                         const void* w3, int64_t ldw3, const void* x, int64_t ldx, int64_t M, int64_t N, int64_t K,
+                         int64_t r, float alpha, float* w, int64_t ldw_out, void* split, int64_t ld_split, int64_t K2,
+                         float* dw, int64_t on, int64_t oj, int accumulate, float alpha_a, float* dwa, int64_t ona,
+                         int64_t oja, int acc_a, float* workspace, void* stream) {
+  if (!(y && u && w3 && w && split && dw && workspace && (!dA || (x && dwa && K > 0))))
+    return fail(LTX_ERR_BAD_ARG, std::string(who) + ": null operand");
+  const DyCall c{M, N, K, r, 0, ldy, ldu, ldw3, ldx, ldw_out, r, ld_split, K2, K2, on, oj, ona, oja,
+                 (uintptr_t)y, (uintptr_t)w3, (uintptr_t)x, (uintptr_t)w, (uintptr_t)split};
+  if (const char* err = lora_dy_check(c)) return fail(LTX_ERR_BAD_ARG, std::string(who) + ": " + err);
+  LoraPlan pl = plan_lora_dy(M, N, K, r, 0);
+  pl.ws = workspace;
+  const DyLayout& d = pl.dy;
+  hipStream_t s = (hipStream_t)stream;
+  with_rank(r, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    hipLaunchKernelGGL((lora_dy_kernel<R, 3>), grid_of(pl.l[0]), dim3(pl.l[0].threads), 0, s, (const bf16_t*)y, ldy, u,
+                       ldu, (const bf16_t*)w3, ldw3, pl.ws + d.pw, pl.ws + d.pb, (int)M, (int)N, (const float*)nullptr, 0,
+                       1.f);
+    if (dA) {
+      with_value<6, 14>(pl.l[1].a[0], [&](auto mode) {
+        hipLaunchKernelGGL((lora_dy_kernel<R, decltype(mode)::value>), grid_of(pl.l[1]), dim3(pl.l[1].threads), 0, s,
+                           (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr, (int64_t)0,
+                           (float*)nullptr, pl.ws + d.pa, (int)M, (int)K, (const float*)(pl.ws + d.pw), d.CS, alpha);
+      });
+    }
+    launch_dy_finish<R>(pl, s, M, N, K, alpha, w, ldw_out, (bf16_t*)split, ld_split, K2, dw, on, oj, accumulate, alpha_a,
+                        dwa, ona, oja, acc_a);
+  });
+  LTX_LAUNCH_CHECK();
+  return LTX_OK;
+}
 extern "C" int ltx_lora_dy(const void* y, int64_t ldy, const float* u, int64_t ldu, const void* w3, int64_t ldw3,
                            int64_t M, int64_t N, int64_t r, float alpha, float* w, int64_t ldw_out, void* split,
                            int64_t ld_split, int64_t K2, float* dw, int64_t on, int64_t oj, int accumulate,
                            float* workspace, void* stream) {
-  LTX_CHECK_ARG(y && u && w3 && w && split && dw && workspace, "lora_dy: null operand");
-  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && dy_rank_ok(r),
-                "lora_dy: M % 32 == 0, N % 512 == 0, rank 8, 16, 32, 64 or 128");
-  LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldw3 % 8 == 0 && ((uintptr_t)w3 % 16) == 0 && ldw3 >= N,
-                "lora_dy: 16-B aligned rows of dY and of the pieces");
-  LTX_CHECK_ARG(ldy * 2 * 32 < ((int64_t)1 << 32), "lora_dy: 32-bit DMA offsets");
-  LTX_CHECK_ARG(ldw_out >= r && ldu >= r && K2 >= 3 * r && K2 % 64 == 0 && ld_split >= K2, "lora_dy: output strides");
-  LTX_CHECK_ARG(ldw_out % 4 == 0 && ((uintptr_t)w % 16) == 0 && ld_split % 4 == 0 && ((uintptr_t)split % 8) == 0,
-                "lora_dy: 16-B aligned w rows, 8-B aligned split rows");
-  LTX_CHECK_ARG((on == r && oj == 1) || (on == 1 && oj == N), "lora_dy: dB must be a dense [N,r] or [r,N]");
-  const int64_t RP = r >= 16 ? r : 16;
-  const int DY_G = dy_g((int)r);
-  const int CS = (int)(N / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
-  float* pw = workspace;
-  float* pb = workspace + (int64_t)CS * M * RP;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)(CS * dy_nsl((int)r)), (unsigned)RS);
-  const int nwb = (int)((M * (r / 4) + 255) / 256);
-  const dim3 g2((unsigned)(nwb + (N * r + 63) / 64));
-#define LTX_LORA_DY(RR)                                                                                          \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 3>), grid, dim3(512), 0, s, (const bf16_t*)y, ldy, u, ldu,                \
-                     (const bf16_t*)w3, ldw3, pw, pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f);          \
-  LTX_LAUNCH_CHECK();                                                                                            \
-  hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), g2, dim3(256), 0, s, pw, CS, pb, RS, (int)M, (int)N, alpha, w, \
-                     ldw_out, (bf16_t*)split, ld_split, (int)K2, dw, on, oj, accumulate, nwb, 1 << 30,           \
-                     (const float*)nullptr, 0, 1.f, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
-  switch (r) {
-    case 8: LTX_LORA_DY(8) break;
-    case 16: LTX_LORA_DY(16) break;
-    case 32: LTX_LORA_DY(32) break;
-    case 64: LTX_LORA_DY(64) break;
-    case 128: LTX_LORA_DY(128) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_dy: rank must be 8, 16, 32, 64 or 128");
-  }
-#undef LTX_LORA_DY
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
+  return lora_dy_entry("lora_dy", false, y, ldy, u, ldu, w3, ldw3, nullptr, 0, M, N, 0, r, alpha, w, ldw_out, split,
+                       ld_split, K2, dw, on, oj, accumulate, 1.f, nullptr, 0, 0, 0, workspace, stream);
 }
-
-extern "C" int ltx_lora_dy_dA_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t* floats) {
-  LTX_CHECK_ARG(floats && M > 0 && N > 0 && K > 0 && dy_rank_ok(r),
-                "lora_dy_dA_workspace: bad args (rank 8, 16, 32, 64 or 128)");
-  const int64_t RP = r >= 16 ? r : 16;
-  const int64_t DY_G = dy_g((int)r);
-  const int64_t CS = N / DY_COLS, RS = (M + DY_G * 32 - 1) / (DY_G * 32);
-  *floats = CS * M * RP + RS * N * RP + RS * K * RP;
-  return LTX_OK;
-}
-
-// ltx_lora_dy + the adapter's dA = alpha_a . x^T . w ([K, r] or [r, K]) in three launches instead of
-// four: the dY pass (w and dB partials), the x pass reading w from those partials (lora_dy_kernel
-// MODE 6), and one finish for w / split, dB and dA. Every output is bitwise what ltx_lora_dy followed
-// by ltx_lora_wgrad(x, w, alpha_a) produces (dA: where that takes lora_wgrad_rows, M >= 2048). Any N
-// that is a multiple of 512: up to 2048 the x pass is MODE 6, beyond it MODE 14.
 extern "C" int ltx_lora_dy_dA(const void* y, int64_t ldy, const float* u, int64_t ldu, const void* w3, int64_t ldw3,
                               const void* x, int64_t ldx, int64_t M, int64_t N, int64_t K, int64_t r, float alpha,
                               float* w, int64_t ldw_out, void* split, int64_t ld_split, int64_t K2, float* dw,
                               int64_t on, int64_t oj, int accumulate, float alpha_a, float* dwa, int64_t ona,
                               int64_t oja, int acc_a, float* workspace, void* stream) {
-  LTX_CHECK_ARG(y && u && w3 && x && w && split && dw && dwa && workspace, "lora_dy_dA: null operand");
-  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && K % DY_COLS == 0 && dy_rank_ok(r),
-                "lora_dy_dA: M % 32 == 0, N % 512 == 0, K % 512 == 0, rank 8, 16, 32, 64 or 128");
-  LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldw3 % 8 == 0 && ((uintptr_t)w3 % 16) == 0 && ldw3 >= N,
-                "lora_dy_dA: 16-B aligned rows of dY and of the pieces");
-  LTX_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldx >= K, "lora_dy_dA: 16-B aligned rows of x");
-  LTX_CHECK_ARG(ldy * 2 * 32 < ((int64_t)1 << 32) && ldx * 2 * 32 < ((int64_t)1 << 32),
-                "lora_dy_dA: 32-bit DMA offsets");
-  LTX_CHECK_ARG(ldw_out >= r && ldu >= r && K2 >= 3 * r && K2 % 64 == 0 && ld_split >= K2,
-                "lora_dy_dA: output strides");
-  LTX_CHECK_ARG(ldw_out % 4 == 0 && ((uintptr_t)w % 16) == 0 && ld_split % 4 == 0 && ((uintptr_t)split % 8) == 0,
-                "lora_dy_dA: 16-B aligned w rows, 8-B aligned split rows");
-  LTX_CHECK_ARG((on == r && oj == 1) || (on == 1 && oj == N), "lora_dy_dA: dB must be a dense [N,r] or [r,N]");
-  LTX_CHECK_ARG((ona == r && oja == 1) || (ona == 1 && oja == K), "lora_dy_dA: dA must be a dense [K,r] or [r,K]");
-  const int64_t RP = r >= 16 ? r : 16;
-  const int DY_G = dy_g((int)r), NSL = dy_nsl((int)r);
-  const int CS = (int)(N / DY_COLS), CSx = (int)(K / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
-  float* pw = workspace;
-  float* pb = pw + (int64_t)CS * M * RP;
-  float* pa = pb + (int64_t)RS * N * RP;
-  hipStream_t s = (hipStream_t)stream;
-  const int nwb = (int)((M * (r / 4) + 255) / 256);
-  const int nbb = (int)((N * r + 63) / 64), nba = (int)((K * r + 63) / 64);
-#define LTX_LORA_DYA(RR)                                                                                           \
-  hipLaunchKernelGGL((lora_dy_kernel<RR, 3>), dim3((unsigned)(CS * NSL), (unsigned)RS), dim3(512), 0, s, (const bf16_t*)y, \
-                     ldy, u, ldu, (const bf16_t*)w3, ldw3, pw, pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f);  \
-  LTX_LAUNCH_CHECK();                                                                                              \
-  if (CS <= DY_MAXCS)                                                                                              \
-    hipLaunchKernelGGL((lora_dy_kernel<RR, 6>), dim3((unsigned)(CSx * NSL), (unsigned)RS), dim3(512), 0, s,       \
-                       (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr,           \
-                       (int64_t)0, (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, CS, alpha);              \
-  else                                                                                                             \
-    hipLaunchKernelGGL((lora_dy_kernel<RR, 14>), dim3((unsigned)(CSx * NSL), (unsigned)RS), dim3(512), 0, s,      \
-                       (const bf16_t*)x, ldx, (const float*)nullptr, (int64_t)0, (const bf16_t*)nullptr,           \
-                       (int64_t)0, (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, CS, alpha);              \
-  LTX_LAUNCH_CHECK();                                                                                              \
-  hipLaunchKernelGGL((lora_dy_finish_kernel<RR>), dim3((unsigned)(nwb + nbb + nba)), dim3(256), 0, s, pw, CS, pb,  \
-                     RS, (int)M, (int)N, alpha, w, ldw_out, (bf16_t*)split, ld_split, (int)K2, dw, on, oj,         \
-                     accumulate, nwb, nbb, (const float*)pa, (int)K, alpha_a, dwa, ona, oja, acc_a);
-  switch (r) {
-    case 8: LTX_LORA_DYA(8) break;
-    case 16: LTX_LORA_DYA(16) break;
-    case 32: LTX_LORA_DYA(32) break;
-    case 64: LTX_LORA_DYA(64) break;
-    case 128: LTX_LORA_DYA(128) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_dy_dA: rank must be 8, 16, 32, 64 or 128");
-  }
-#undef LTX_LORA_DYA
-  LTX_LAUNCH_CHECK();
-  return LTX_OK;
-}
-
-extern "C" int ltx_lora_dy_dA_grouped_workspace(int64_t M, int64_t N, int64_t K, int64_t r, int64_t groups,
-                                                int64_t* floats) {
-  LTX_CHECK_ARG(groups >= 1 && groups <= LORA_MAX_GROUPS, "lora_dy_dA_grouped_workspace: 1 to 4 groups");
-  int64_t one = 0;
-  const int rc = ltx_lora_dy_dA_workspace(M, N, K, r, &one);
-  if (rc != LTX_OK) return rc;
-  *floats = groups * one;
-  return LTX_OK;
+  return lora_dy_entry("lora_dy_dA", true, y, ldy, u, ldu, w3, ldw3, x, ldx, M, N, K, r, alpha, w, ldw_out, split,
+                       ld_split, K2, dw, on, oj, accumulate, alpha_a, dwa, ona, oja, acc_a, workspace, stream);
 }
 
 // ltx_lora_dy_dA for `groups` adapters on the column blocks of one packed dY [M, groups * N] that
@@ -504,25 +381,8 @@ extern "C" int ltx_lora_dy_dA_grouped(const void* y, int64_t ldy, const float* c
                                       int64_t gs, float* const* dw, int64_t on, int64_t oj, int accumulate,
                                       float alpha_a, float* const* dwa, int64_t ona, int64_t oja, int acc_a,
                                       float* workspace, void* stream) {
-  LTX_CHECK_ARG(y && u && w3 && x && w && split && dw && dwa && workspace, "lora_dy_dA_grouped: null operand");
+  LTX_CHECK_ARG(y && u && w3 && x && w && split && dw && dwa && workspace && K > 0, "lora_dy_dA_grouped: null operand");
   LTX_CHECK_ARG(groups >= 1 && groups <= LORA_MAX_GROUPS, "lora_dy_dA_grouped: 1 to 4 groups");
-  LTX_CHECK_ARG(M >= 32 && M % 32 == 0 && N % DY_COLS == 0 && K % DY_COLS == 0 && dy_rank_ok(r),
-                "lora_dy_dA_grouped: M % 32 == 0, N % 512 == 0, K % 512 == 0, rank 8, 16, 32, 64 or 128");
-  LTX_CHECK_ARG(N <= DY_MAXCS * DY_COLS, "lora_dy_dA_grouped: N <= 2048 per group");
-  LTX_CHECK_ARG(ldy % 8 == 0 && ((uintptr_t)y % 16) == 0 && ldy >= groups * N && ldw3 % 8 == 0 && ldw3 >= N,
-                "lora_dy_dA_grouped: 16-B aligned rows of dY (groups * N columns) and of the pieces");
-  LTX_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldx >= K, "lora_dy_dA_grouped: 16-B aligned rows of x");
-  LTX_CHECK_ARG(ldy * 2 * 32 < ((int64_t)1 << 32) && ldx * 2 * 32 < ((int64_t)1 << 32),
-                "lora_dy_dA_grouped: 32-bit DMA offsets");
-  LTX_CHECK_ARG(gw >= r && gs >= K2 && ldw_out >= (groups - 1) * gw + r && ldu >= r && K2 >= 3 * r && K2 % 64 == 0 &&
-                    ld_split >= (groups - 1) * gs + K2,
-                "lora_dy_dA_grouped: every group's w / split columns inside the row, disjoint");
-  LTX_CHECK_ARG(ldw_out % 4 == 0 && gw % 4 == 0 && ((uintptr_t)w % 16) == 0 && ld_split % 4 == 0 && gs % 4 == 0 &&
-                    ((uintptr_t)split % 8) == 0,
-                "lora_dy_dA_grouped: 16-B aligned w rows, 8-B aligned split rows");
-  LTX_CHECK_ARG((on == r && oj == 1) || (on == 1 && oj == N), "lora_dy_dA_grouped: dB must be a dense [N,r] or [r,N]");
-  LTX_CHECK_ARG((ona == r && oja == 1) || (ona == 1 && oja == K),
-                "lora_dy_dA_grouped: dA must be a dense [K,r] or [r,K]");
   DyGroupPtrs gp{};
   for (int g = 0; g < (int)groups; ++g) {
     LTX_CHECK_ARG(u[g] && w3[g] && dw[g] && dwa[g] && ((uintptr_t)w3[g] % 16) == 0,
@@ -532,46 +392,34 @@ extern "C" int ltx_lora_dy_dA_grouped(const void* y, int64_t ldy, const float* c
     gp.dw[g] = dw[g];
     gp.dwa[g] = dwa[g];
   }
-  const int64_t RP = r >= 16 ? r : 16;
-  const int DY_G = dy_g((int)r), NSL = dy_nsl((int)r), G = (int)groups;
-  const int CS = (int)(N / DY_COLS), CSx = (int)(K / DY_COLS), RS = (int)((M + DY_G * 32 - 1) / (DY_G * 32));
-  const int64_t gpw = (int64_t)CS * M * RP, gpb = (int64_t)RS * N * RP, gpa = (int64_t)RS * K * RP;
-  float* pw = workspace;
-  float* pb = pw + G * gpw;
-  float* pa = pb + G * gpb;
+  const DyCall c{M, N, K, r, groups, ldy, ldu, ldw3, ldx, ldw_out, gw, ld_split, K2, gs, on, oj, ona, oja,
+                 (uintptr_t)y, (uintptr_t)w3[0], (uintptr_t)x, (uintptr_t)w, (uintptr_t)split};
+  if (const char* err = lora_dy_check(c)) return fail(LTX_ERR_BAD_ARG, std::string("lora_dy_dA_grouped: ") + err);
+  const LoraPlan pl = plan_lora_dy(M, N, K, r, groups);
+  const DyLayout& d = pl.dy;
+  const int G = (int)groups;
+  float *pw = workspace + d.pw, *pb = workspace + d.pb, *pa = workspace + d.pa;
   hipStream_t s = (hipStream_t)stream;
-  const int nwb = (int)((M * (r / 4) + 255) / 256);
-  const int nbb = (int)((N * r + 63) / 64), nba = (int)((K * r + 63) / 64);
-#define LTX_LORA_DYG(RR)                                                                                            \
-  hipLaunchKernelGGL((lora_dy_grouped_kernel<RR, 3>), dim3((unsigned)(CS * NSL), (unsigned)RS, (unsigned)G),        \
-                     dim3(512), 0, s, (const bf16_t*)y, ldy, gp, ldu, ldw3, pw, pb, (int)M, (int)N,                 \
-                     (const float*)nullptr, 0, 1.f, G, N, gpw, gpb, (int64_t)0);                                    \
-  LTX_LAUNCH_CHECK();                                                                                               \
-  hipLaunchKernelGGL((lora_dy_grouped_kernel<RR, 6>), dim3((unsigned)(CSx * NSL * G), (unsigned)RS), dim3(512), 0, \
-                     s, (const bf16_t*)x, ldx, gp, (int64_t)0, (int64_t)0, (float*)nullptr, pa, (int)M, (int)K,     \
-                     (const float*)pw, CS, alpha, G, (int64_t)0, (int64_t)0, gpa, gpw);                             \
-  LTX_LAUNCH_CHECK();                                                                                               \
-  hipLaunchKernelGGL((lora_dy_finish_grouped_kernel<RR>), dim3((unsigned)(nwb + nbb + nba), (unsigned)G),           \
-                     dim3(256), 0, s, pw, CS, pb, RS, (int)M, (int)N, alpha, w, ldw_out, (bf16_t*)split, ld_split,  \
-                     (int)K2, gp, on, oj, accumulate, nwb, nbb, (const float*)pa, (int)K, alpha_a, ona, oja, acc_a, \
-                     gpw, gpb, gpa, gw, gs);
-  switch (r) {
-    case 8: LTX_LORA_DYG(8) break;
-    case 16: LTX_LORA_DYG(16) break;
-    case 32: LTX_LORA_DYG(32) break;
-    case 64: LTX_LORA_DYG(64) break;
-    case 128: LTX_LORA_DYG(128) break;
-    default: return fail(LTX_ERR_BAD_ARG, "lora_dy_dA_grouped: rank must be 8, 16, 32, 64 or 128");
-  }
-#undef LTX_LORA_DYG
+  with_rank(r, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    hipLaunchKernelGGL((lora_dy_grouped_kernel<R, 3>), grid_of(pl.l[0]), dim3(pl.l[0].threads), 0, s, (const bf16_t*)y,
+                       ldy, gp, ldu, ldw3, pw, pb, (int)M, (int)N, (const float*)nullptr, 0, 1.f, G, N, d.gpw, d.gpb,
+                       (int64_t)0);
+    hipLaunchKernelGGL((lora_dy_grouped_kernel<R, 6>), grid_of(pl.l[1]), dim3(pl.l[1].threads), 0, s, (const bf16_t*)x,
+                       ldx, gp, (int64_t)0, (int64_t)0, (float*)nullptr, pa, (int)M, (int)K, (const float*)pw, d.CS,
+                       alpha, G, (int64_t)0, (int64_t)0, d.gpa, d.gpw);
+    hipLaunchKernelGGL((lora_dy_finish_grouped_kernel<R>), grid_of(pl.l[2]), dim3(pl.l[2].threads), 0, s, pw, d.CS, pb,
+                       d.RS, (int)M, (int)N, alpha, w, ldw_out, (bf16_t*)split, ld_split, (int)K2, gp, on, oj, accumulate,
+                       d.nwb, d.nbb, (const float*)pa, (int)K, alpha_a, ona, oja, acc_a, d.gpw, d.gpb, d.gpa, gw, gs);
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }
 
-// ltx_lora_rows for `groups` adapters that share x. Where ltx_lora_rows runs its whole-contraction
-// kernel (token-sized M, K = 512 / 1024 / 2048) this is ONE launch with (group, rank slice) as grid y;
-// everywhere else it issues the one-adapter calls. Either way every output is bitwise
-// ltx_lora_rows' on the same operands.
+// ltx_lora_rows for `groups` adapters that share x. Where ltx_lora_rows' whole-contraction route
+// holds for every group's operands (rows_full_route, the same function ltx_lora_rows plans from) this
+// is ONE launch with (group, rank slice) as grid y; everywhere else it issues the one-adapter calls.
+// Either way every output is bitwise ltx_lora_rows' on the same operands.
 extern "C" int ltx_lora_rows_grouped(const void* x, int64_t ldx, const void* const* w3, int64_t ldw, float* out,
                                      int64_t ldo, int64_t go, int64_t M, int64_t K, int64_t r, float alpha,
                                      void* split, int64_t ld_split, int64_t K2, int64_t gs, int64_t groups,
@@ -581,35 +429,19 @@ extern "C" int ltx_lora_rows_grouped(const void* x, int64_t ldx, const void* con
   LTX_CHECK_ARG(go >= r && ldo >= (groups - 1) * go + r, "lora_rows_grouped: every group's out columns inside the row");
   LTX_CHECK_ARG(!split || (K2 >= 3 * r && K2 % 64 == 0 && gs >= K2 && ld_split >= (groups - 1) * gs + K2),
                 "lora_rows_grouped: split needs K2 >= 3r, %64, every group's columns inside the row");
-  LTX_CHECK_ARG(K % 256 == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldw % 8 == 0 && ldw >= K,
-                "lora_rows_grouped: K % 256, 16-B aligned rows of x and of the pieces");
-  LTX_CHECK_ARG((int64_t)ldx * 2 * (M - 1) + 2 * K < ((int64_t)1 << 32) &&
-                    (int64_t)ldw * 2 * 3 * (r > 32 ? r : 32) < ((int64_t)1 << 32),
-                "lora_rows_grouped: 32-bit DMA offsets");
-  for (int g = 0; g < (int)groups; ++g)
-    LTX_CHECK_ARG(w3[g] && ((uintptr_t)w3[g] % 16) == 0, "lora_rows_grouped: null or misaligned pieces");
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t* xb = (const bf16_t*)x;
-  bf16_t* sp = (bf16_t*)split;
-  static const int rows_dy = [] {
-    const char* e = getenv("LTX_LORA_ROWS_DY");
-    return e ? atoi(e) : 1;
-  }();
-  static const int full = [] {
-    const char* e = getenv("LTX_LORA_ROWS_FULL");
-    return e ? atoi(e) : 1;
-  }();
-  // the gates of lora_rows_dy's whole-contraction route, for every group's operands
-  bool one = rows_dy && full && M >= 2048 && M % 32 == 0 && (K == 512 || K == 1024 || K == 2048) && dy_rank_ok(r);
-  one = one && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ldx * 2 * 32 < ((int64_t)1 << 32) && ldx >= K;
-  one = one && ldw % 8 == 0 && ldw >= K && ldo % 4 == 0 && go % 4 == 0 && ((uintptr_t)out % 16) == 0;
-  one = one && (!split || (ld_split % 4 == 0 && gs % 4 == 0 && ((uintptr_t)split % 8) == 0 && (K2 - 3 * r) % 4 == 0));
   RowsGroupPtrs gp{};
   for (int g = 0; g < (int)groups; ++g) {
+    LTX_CHECK_ARG(w3[g] && ((uintptr_t)w3[g] % 16) == 0, "lora_rows_grouped: null or misaligned pieces");
     gp.w3[g] = (const bf16_t*)w3[g];
-    one = one && ((uintptr_t)w3[g] % 16) == 0;
   }
-  if (!one) {
+  const RowsCall c{M, K, r, ldx, ldw, ldo, (uintptr_t)x, (uintptr_t)w3[0], (uintptr_t)out, split != nullptr,
+                   (uintptr_t)split, ld_split, K2};
+  if (const char* err = lora_rows_check(c)) return fail(LTX_ERR_BAD_ARG, err);
+  hipStream_t s = (hipStream_t)stream;
+  bf16_t* sp = (bf16_t*)split;
+  const LoraPlan pl = plan_lora_rows(c, lora_site(s), groups, go, gs);
+  const LoraLaunch* l = &pl.l[0];
+  if (l->k != LK_ROWS_FULL_GROUPED) {
     for (int g = 0; g < (int)groups; ++g) {
       const int rc = ltx_lora_rows(x, ldx, w3[g], ldw, out + g * go, ldo, M, K, r, alpha, sp ? sp + g * gs : nullptr,
                                    ld_split, K2, stream);
@@ -617,24 +449,13 @@ extern "C" int ltx_lora_rows_grouped(const void* x, int64_t ldx, const void* con
     }
     return LTX_OK;
   }
-  constexpr int RG = 2, NRF = LTX_RF_NR;
-  const int nsl = (int)(r > 16 ? r / 16 : 1);
-  const dim3 gf((unsigned)((M + RG * 32 - 1) / (RG * 32)), (unsigned)(nsl * groups));
-#define LTX_LORA_RFG(RR, CHH)                                                                                     \
-  hipLaunchKernelGGL((lora_rows_full_grouped_kernel<RR, RG, CHH, NRF>), gf, dim3(512), 0, s, xb, ldx, gp, ldw, out, \
-                     ldo, (int)M, alpha, sp, ld_split, (int)K2, nsl, go, gs)
-  const int ch = (int)(K / 512);
-#define LTX_LORA_RFGC(RR) \
-  if (ch == 1) LTX_LORA_RFG(RR, 1); else if (ch == 2) LTX_LORA_RFG(RR, 2); else LTX_LORA_RFG(RR, 4)
-  switch (r) {
-    case 8: LTX_LORA_RFGC(8); break;
-    case 16: LTX_LORA_RFGC(16); break;
-    case 32: LTX_LORA_RFGC(32); break;
-    case 64: LTX_LORA_RFGC(64); break;
-    default: LTX_LORA_RFGC(128); break;
-  }
-#undef LTX_LORA_RFGC
-#undef LTX_LORA_RFG
+  with_rank(r, [&](auto rank) {
+    with_value<1, 2, 4>(l->a[1], [&](auto ch) {
+      hipLaunchKernelGGL((lora_rows_full_grouped_kernel<decltype(rank)::value, RF_RG, decltype(ch)::value, LTX_RF_NR>),
+                         grid_of(*l), dim3(l->threads), 0, s, (const bf16_t*)x, ldx, gp, ldw, out, ldo, (int)M, alpha, sp,
+                         ld_split, (int)K2, (int)(l->gy / groups), go, gs);
+    });
+  });
   LTX_LAUNCH_CHECK();
   return LTX_OK;
 }

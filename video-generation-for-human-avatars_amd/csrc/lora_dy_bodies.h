@@ -18,7 +18,7 @@
   constexpr int NF = 3 * JT;
   constexpr int RING = 8 * DY_NR * 4096;
   constexpr int UT = SW * DY_UPAD * 4;
-  static_assert(dy_rank_ok(R), "rank 8, 16, 32, 64 or 128");
+  static_assert(lora_rank_ok(R), "rank 8, 16, 32, 64 or 128");
   // ONE shared array (the DMA target): the ring, then u^T of the block's rows
   __shared__ __attribute__((aligned(16))) char smem[RING + UT];
   float* ut = (float*)(smem + RING);
@@ -340,7 +340,7 @@
   constexpr int NS = RG * CH;  // slots per wave
   constexpr int RING = 8 * NR * 4096;
   constexpr int PROW = RG * 32 + 4;  // floats per (wave, j) partial row; +4 spreads the banks
-  static_assert(dy_rank_ok(R), "rank 8, 16, 32, 64 or 128");
+  static_assert(lora_rank_ok(R), "rank 8, 16, 32, 64 or 128");
   static_assert(8 * SW * PROW * 4 <= RING, "wave partials fit the ring");
   const int j0 = DY_BY * SW;
   __shared__ __attribute__((aligned(16))) char smem[RING];

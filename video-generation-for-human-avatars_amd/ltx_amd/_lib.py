@@ -90,6 +90,7 @@ _SIGNATURES = {
                                ctypes.POINTER(_p), _i64, _i64, _i32, _f32, ctypes.POINTER(_p), _i64, _i64,
                                _i32, _p, _p],
     "ltx_lora_dy_dA_grouped_workspace": [_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64)],
+    "ltx_lora_describe": [_i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i64],
     "ltx_lora_dropout_apply": [_p, _i64, _p, _i64, _i64, _i64, ctypes.c_uint64, _i64, _i64, _p],
     "ltx_lora_up_masked_add": [_p, _i64, _p, _i64, ctypes.POINTER(_p), _i64, ctypes.POINTER(_i64), _i64, _i64,
                                _i64, _i64, ctypes.c_uint64, _i64, _f32, _p, _i64, _p],
@@ -145,6 +146,7 @@ _SIGNATURES = {
     "ltx_guidance_bf16": [_p, _i64, _i64, _i32, _i32, _f32, _f32, _f32, _i32, _p, _i64, _p, _p],
 }
 
+LORA_OP = {"down": 0, "rows": 1, "wgrad": 2, "dy": 3, "dy_dA": 4}  # LTX_LORA_OP_*
 EPI = {"store": 0, "gelu": 1, "gated_residual": 2, "lora": 3, "lora_residual": 4,
        "gelu_bwd": 5, "accum": 6, "lora_dgrad_accum": 7, "store_rowdot": 8}
 

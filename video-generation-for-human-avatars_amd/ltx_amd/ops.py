@@ -618,6 +618,18 @@ def gemm_algorithmic_bytes(M, N, K, K2, epilogue, has_aux0, has_aux2):
 
 
 _LORA_ROWS = os.environ.get("LTX_LORA_ROWS", "1") != "0"  # A/B switch: 0 = the f32 kernel only
+# The adapter gates Python decides per call, named once (csrc/lora_plan.h holds the library's own).
+# lora_dy_fits / lora_dy_da_fits mirror the library's numbers and do not ask it: they run on every hot-path
+# call. tests/test_abi.py ties them to ltx_lora_describe.
+LORA_ROWS_MIN_M = 8192   # lora_down hands calls with pieces to ltx_lora_rows from here on (LORA_DOWN_BIG_ROWS)
+LORA_TOKEN_ROWS = 2048   # ltx_lora_wgrad takes its lora_dy_kernel<R, 2> route from here on (LORA_TOKEN_ROWS)
+LORA_DY_COLS = 512       # the dY family works on whole 512-column blocks (DY_COLS)
+
+
+def lora_rows_gate(M, K):
+    """lora_down (and the grouped q / k / v down-projection) goes to ltx_lora_rows: token-sized M, K in whole
+    256-column wave quarters (ltx_lora_rows' own argument check), and LTX_LORA_ROWS not 0."""
+    return _LORA_ROWS and M >= LORA_ROWS_MIN_M and K % 256 == 0
 
 
 def lora_down(x, wr, alpha=1.0, transposed=False, out=None, split=False, split_out=None,
@@ -631,7 +643,7 @@ def lora_down(x, wr, alpha=1.0, transposed=False, out=None, split=False, split_o
     caller's cache) routes token-sized calls to the bf16-matrix-core kernel (ltx_lora_rows); a
     callable is invoked only when that route is taken (the pieces are built lazily)."""
     M, K = x.shape
-    if pieces is not None and _LORA_ROWS and groups == 1 and M >= 8192 and K % 256 == 0:
+    if pieces is not None and groups == 1 and lora_rows_gate(M, K):
         pieces = pieces() if callable(pieces) else pieces
         return lora_rows(x, pieces, wr.shape[1] if transposed else wr.shape[0], alpha=alpha,
                          out=out, split=split, split_out=split_out)
@@ -699,7 +711,7 @@ def bump_weight_generation():
     _WEIGHT_GENERATION[0] += 1
 
 
-LORA_RANKS = (8, 16, 32, 64, 128)  # the ranks every adapter kernel is built for
+LORA_RANKS = (8, 16, 32, 64, 128)  # the ranks every adapter kernel is built for (lora_rank_ok in csrc/lora_plan.h)
 
 
 def check_lora_rank(r):
@@ -765,17 +777,18 @@ def lora_dy_da_enabled():
 
 
 def lora_dy_da_fits(y, x, r):
-    """lora_dy(y, ..., x=x) applies (and LTX_LORA_DY_DA is not 0). Only at M >= 2048, where
-    ltx_lora_wgrad takes the same token-sized path, so the merged call is bitwise the separate ones
+    """lora_dy(y, ..., x=x) applies (and LTX_LORA_DY_DA is not 0). Only at M >= LORA_TOKEN_ROWS, where
+    ltx_lora_wgrad takes the same lora_dy_kernel route, so the merged call is bitwise the separate ones
     (below it ltx_lora_wgrad runs the f32-MFMA kernel: another rounding of dA). Any dY width that is
-    a multiple of 512 (the feed-forward's 8192 included)."""
-    return (lora_dy_da_enabled() and lora_dy_fits(x, r) and y.shape[1] % 512 == 0 and x.shape[0] == y.shape[0]
-            and y.shape[0] >= 2048)
+    a multiple of LORA_DY_COLS (the feed-forward's 8192 included)."""
+    return (lora_dy_da_enabled() and lora_dy_fits(x, r) and y.shape[1] % LORA_DY_COLS == 0
+            and x.shape[0] == y.shape[0] and y.shape[0] >= LORA_TOKEN_ROWS)
 
 
 def lora_dy_fits(y, r):
+    """y can be the dY (or x) operand of ltx_lora_dy / ltx_lora_dy_dA: lora_dy_check's shape and stride part"""
     M, N = y.shape
-    return r in LORA_RANKS and M % 32 == 0 and N % 512 == 0 and y.stride(1) == 1 and y.stride(0) % 8 == 0
+    return r in LORA_RANKS and M % 32 == 0 and N % LORA_DY_COLS == 0 and y.stride(1) == 1 and y.stride(0) % 8 == 0
 
 
 def _ptr_array(tensors):
@@ -867,7 +880,7 @@ def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=
     n = ctypes.c_int64(0)
     if x is not None:
         K = x.shape[1]
-        assert x.shape[0] == M and x.dtype == BF16 and lora_dy_fits(x, r) and N % 512 == 0
+        assert x.shape[0] == M and x.dtype == BF16 and lora_dy_fits(x, r) and N % LORA_DY_COLS == 0
         assert tuple(dA_out.shape) == (r, K) and dA_out.dtype == F32 and dA_out.is_contiguous()
         call("ltx_lora_dy_dA_workspace", M, N, K, r, ctypes.byref(n))
         ws = torch.empty(n.value, dtype=F32, device=y.device)
@@ -882,6 +895,16 @@ def lora_dy(y, u, w3, r, alpha, dB_out, accumulate=True, transpose_out=False, x=
          float(alpha), _p(w), _rows(w, "w"), _p(sp), _rows(sp, "split"), K2, _p(dB_out), on, oj,
          1 if accumulate else 0, _p(ws), _s())
     return w, sp
+
+
+def lora_kernel_label(op, M, N=0, K=0, r=16, groups=0, split=False, ld_in=0, ld_w=0, ld_out=0):
+    """The kernels an adapter entry launches for this call on the current stream, as rocprofv3 names them,
+    joined by " + " (ltx_lora_describe: the plan the launchers launch from; nothing runs). op: "down", "rows"
+    (x [M, K]), "wgrad" (y [M, N]), "dy" (dY [M, N]), "dy_dA" (also x [M, K]); groups >= 1: the _grouped entry;
+    a leading dimension of 0 is the dense one. Raises LtxHipError where the entry would reject the call."""
+    buf = ctypes.create_string_buffer(512)
+    call("ltx_lora_describe", _lib.LORA_OP[op], M, N, K, ld_in, ld_w, ld_out, r, groups, int(split), _s(), buf, 512)
+    return buf.value.decode()
 
 
 @functools.lru_cache(maxsize=64)

@@ -479,7 +479,7 @@ def _qkv_lora_down(x1, lora1, ab1, r, dp=None):
     one-adapter calls."""
     M, K = x1.shape
     K2 = ops.lora_k2(r)
-    if dp is None and _qkv_grouped() and ops._LORA_ROWS and M >= 8192 and K % 256 == 0:  # lora_down's token-sized gate
+    if dp is None and _qkv_grouped() and ops.lora_rows_gate(M, K):  # where lora_down takes ltx_lora_rows
         return ops.lora_rows_grouped(x1, [m.weight_pieces("A") for m in lora1[:3]], r, split=True)
     u = torch.empty(M, 3 * r, dtype=torch.float32, device=x1.device)
     su = torch.empty(M, 3 * K2, dtype=torch.bfloat16, device=x1.device)
