@@ -521,6 +521,29 @@ int ltx_loss_token_weights(const float* bbox,      /* [B,4] x_min,y_min,x_max,y_
 int ltx_wmse_fwd_bwd(const void* out, const void* v, const float* wt /* [rows] */,
                      void* dout /* nullable */, float* stats /* f32[4 + 4*256] */,
                      int64_t rows, int64_t C, float grad_scale, void* stream);
+/* The robust (pseudo-Huber) velocity loss (DESIGN.md "Robust loss"): out / v / dout bf16
+ * [B, rows_per_sample, C] dense (16-B aligned), n = B * rows_per_sample * C elements; element i belongs to
+ * token i / C and to sample i / (rows_per_sample * C). Per element, in f32 from the bf16 values:
+ *   e = o - v, r = sqrt(e*e + c*c), l = k * (e*e) / (r + c) (== k * (r - c)), g = dl/do = k * e / r,
+ *   c = c[sample] > 0, k = 2*c (LTX_ROBUST_HUBER: e^2 as c grows, 2*c*|e| for |e| >> c) or
+ *   2 (LTX_ROBUST_SMOOTH_L1: 2*|e| as c shrinks);
+ *   dout = bf16(wt[token] * g * grad_scale / n), computed in f32 and rounded once, to nearest even.
+ * The square root and the two divisions are the hardware's 1-ulp v_sqrt_f32 / v_rcp_f32.
+ * e == 0 gives l == 0 and dout == 0 exactly; non-finite inputs give non-finite sums and seeds.
+ * stats[0] = sum wt * l, stats[4] = sum l, and stats[1] = sum v, stats[2] = sum v^2,
+ * stats[3] = sum bf16(d*d) with d = bf16(o - v), the last three bitwise ltx_mse_fwd_bwd's stats[1],
+ * stats[2], stats[0] for every shape and any wt: the traversal is ltx_mse_fwd_bwd's (16-B vectors over
+ * n / 8, then the scalar tail, on its fixed grid) and the 256 per-block partials of each sum, kept in the
+ * tail of stats (f32[8 + 5*256]), are added in its fixed order: no atomics, bitwise run to run.
+ * C % 8 == 0 loads one weight and one threshold per vector; otherwise a vector may straddle tokens and
+ * samples, and both are indexed per element. wt == null: every weight 1 (stats[0] == stats[4], bitwise
+ * what a wt of ones gives). dout may be null (forward only). Refused before any launch: a null out, v, c
+ * or stats, a kind other than the two below, a non-positive B, rows_per_sample or C. */
+enum { LTX_ROBUST_HUBER = 1, LTX_ROBUST_SMOOTH_L1 = 2 };
+int ltx_robust_loss_fwd_bwd(const void* out, const void* v, const float* wt /* [B*rows_per_sample] or null */,
+                            const float* c /* [B] */, int kind, void* dout /* nullable */,
+                            float* stats /* f32[8 + 5*256] */, int64_t B, int64_t rows_per_sample, int64_t C,
+                            float grad_scale, void* stream);
 /* torch.optim.AdamW single-tensor step (training.py:270-271): f32 or bf16 param/state.
  * is_bf16 selects the dtype of param/grad/exp_avg/exp_avg_sq (all the same). */
 int ltx_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n,

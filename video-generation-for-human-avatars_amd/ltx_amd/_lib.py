@@ -110,6 +110,7 @@ _SIGNATURES = {
     "ltx_mse_fwd_bwd": [_p, _p, _p, _p, _i64, _f32, _p],
     "ltx_loss_token_weights": [_p, _p, _p, _p, _f32, _f32, _p, _p, _i64, _i64, _i64, _i64, _p],
     "ltx_wmse_fwd_bwd": [_p, _p, _p, _p, _p, _i64, _i64, _f32, _p],
+    "ltx_robust_loss_fwd_bwd": [_p, _p, _p, _p, _i32, _p, _p, _i64, _i64, _i64, _f32, _p],
     "ltx_adamw_multi": [_p, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _p],
     "ltx_adamw_step": [_p, _p, _p, _p, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _p],
     "ltx_grad_sumsq_multi": [_p, _i64, _i32, _p, _p],

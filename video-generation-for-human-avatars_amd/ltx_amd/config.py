@@ -204,4 +204,12 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
                 "face_bbox_dir"):
         if key in t:
             setattr(config, key, t[key])
+    # and the three keys training.robust_loss_from_config reads (and validates; passed on as written):
+    # `train.loss_type` ("l2", the same as absent, "huber" or "smooth_l1": the pseudo-Huber velocity loss),
+    # `train.huber_c` (a float > 0, absent = 0.1: the threshold at t = 1) and `train.huber_schedule`
+    # ("constant", "exponential" or "snr", absent = "snr": how the threshold follows the timestep); the
+    # last two are refused without a loss_type that reads them
+    for key in ("loss_type", "huber_c", "huber_schedule"):
+        if key in t:
+            setattr(config, key, t[key])
     return config

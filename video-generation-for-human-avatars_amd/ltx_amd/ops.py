@@ -1145,6 +1145,46 @@ def wmse_fwd_bwd(out, v, wt, grad_scale=1.0, want_grad=True):
     return stats[:4], dout
 
 
+ROBUST_KINDS = {"huber": 1, "smooth_l1": 2}  # LTX_ROBUST_*
+
+
+def robust_loss_fwd_bwd(out, v, c, kind, wt=None, grad_scale=1.0, want_grad=True):
+    """The robust velocity loss and its seed (ltx_robust_loss_fwd_bwd): out, v bf16 [B, ..., C], c f32 [B]
+    (the threshold of each sample, > 0), kind 1 (huber) or 2 (smooth_l1), wt f32 with one element per row
+    of C, or None for ones. Per element e = o - v, r = sqrt(e^2 + c^2), l = k e^2 / (r + c), k = 2 c | 2.
+    Returns (stats[5] f32 device: sum wt * l, sum v, sum v^2, sum bf16(d * d) -- the three of mse_fwd_bwd,
+    bitwise -- and sum l; dout bf16 = wt * k * e / r * grad_scale / n rounded once, or None)."""
+    _need(out, BF16, "robust_loss out")
+    _need(v, BF16, "robust_loss v")
+    _need(c, F32, "robust_loss c")
+    if kind not in (1, 2):
+        raise ValueError(f"robust_loss_fwd_bwd: kind must be 1 (huber) or 2 (smooth_l1), got {kind!r}")
+    if out.dim() < 2 or out.numel() == 0:
+        raise ValueError(f"robust_loss_fwd_bwd: out must be a non-empty [B, ..., C], got {tuple(out.shape)}")
+    B, C = out.shape[0], out.shape[-1]
+    n = out.numel()
+    rows = n // C
+    if v.shape != out.shape or tuple(c.shape) != (B,) or not c.is_contiguous():
+        raise ValueError(f"robust_loss_fwd_bwd: out {tuple(out.shape)}, v {tuple(v.shape)}, c {tuple(c.shape)}: v "
+                         f"must have out's shape and c be a contiguous [{B}]")
+    if wt is not None:
+        _need(wt, F32, "robust_loss wt")
+        if wt.numel() != rows or not wt.is_contiguous():
+            raise ValueError(f"robust_loss_fwd_bwd: wt {tuple(wt.shape)} strides {wt.stride()} must be contiguous "
+                             f"with one weight per row of {C} ({rows} rows)")
+    out, v = out.contiguous(), v.contiguous()
+    stats = torch.empty(8 + 5 * 256, dtype=F32, device=out.device)  # + per-block partials
+    dout = torch.empty(out.shape, dtype=BF16, device=out.device) if want_grad else None
+    label = f"ltx::robust_loss_kernel<{'true' if C % 8 == 0 else 'false'}>"
+    timer, ev0 = _timed(label)
+    call("ltx_robust_loss_fwd_bwd", _p(out), _p(v), _p(wt), _p(c), int(kind), _p(dout), _p(stats), B, rows // B, C,
+         float(grad_scale), _s())
+    if timer is not None:
+        timer.stop(label, 0.0, ev0,
+                   2.0 * n * (3 if want_grad else 2) + 4.0 * (rows if wt is not None else 0) + 4.0 * B)
+    return stats[:5], dout
+
+
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
     is_bf16 = 1 if param.dtype == BF16 else 0
     call("ltx_adamw_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(),

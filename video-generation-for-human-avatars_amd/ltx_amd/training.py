@@ -73,7 +73,14 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
     [B, F, H, W], >= 0), the loss is the weighted mean(wt (out - v)^2): the token weights come from
     ltx_loss_token_weights (batch["face_bbox"], f32 [B, 4], when it is there) and ltx_wmse_fwd_bwd takes
     ltx_mse_fwd_bwd's place. loss, rel_mse and nrmse are then the weighted loss's, loss_dict gains
-    "transformer_wmse" / "_wmse_f32", and "transformer_mse" / "_mse_f32" stay the unweighted mean."""
+    "transformer_wmse" / "_wmse_f32", and "transformer_mse" / "_mse_f32" stay the unweighted mean.
+
+    With `loss_type` huber or smooth_l1 (robust_loss_from_config) ltx_robust_loss_fwd_bwd takes the place of
+    either: the loss is mean(wt l), l the pseudo-Huber term against the sample's threshold
+    (huber_threshold on the step's shifted t; wt as above, or ones). loss, rel_mse and nrmse are that
+    loss's, loss_dict gains "transformer_robust" / "_robust_f32" (and no "transformer_wmse": the weighted
+    squared error would be a sum the kernel does not otherwise need), and "transformer_mse" / "_mse_f32"
+    stay the unweighted squared error, bitwise the plain step's."""
     dt = torch.bfloat16
     device = device or model.device
     latents = batch["latents"].to(device=device, dtype=dt)
@@ -84,6 +91,7 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
     # the loss weights (loss_weights_from_config; None and no batch["loss_weights"]: the reference's plain
     # mse, today's launches). The refusals come before anything is launched.
     lw = loss_weights_from_config(config)
+    robust = robust_loss_from_config(config)
     user_w = batch.get("loss_weights")
     weighted = lw is not None or user_w is not None
     if weighted:
@@ -113,9 +121,10 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
     w = float(getattr(config, "transformer_loss_weight", 1.0))
     accum = max(1, int(getattr(config, "gradient_accumulation_steps", 1)))
     n = out.numel()
+    wt = None
     if weighted:
         # built on the device and consumed inside the loss kernel: no host read, no torch pass over the
-        # tokens. stats[0] is the weighted sum, stats[3] the unweighted one (bitwise mse_fwd_bwd's)
+        # tokens
         bbox = batch.get("face_bbox") if lw.face_weight != 1.0 else None  # a missing box: uniform weights
         if bbox is not None:
             bbox = bbox.to(device=device, dtype=torch.float32).reshape(B, 4).contiguous()
@@ -123,6 +132,19 @@ def train_step(model, batch, scheduler, patchifier, config, prompt_embeds, promp
                                        frame_w=_frame_weights(F, lw.frame0_weight, device),
                                        sample_w=timestep_loss_weight(t, lw.timestep_weighting), user_w=user_w,
                                        face_weight=lw.face_weight, face_pad=lw.face_pad)
+    if robust is not None:
+        # the thresholds from the t the model saw, a few torch ops on [B]; stats[0] is the (weighted) robust
+        # sum, stats[1..3] mse_fwd_bwd's sum v, sum v^2 and squared-error sum, bit for bit
+        c = huber_threshold(t, robust.schedule, robust.huber_c)
+        stats, dout = ops.robust_loss_fwd_bwd(out, v_target, c, ops.ROBUST_KINDS[robust.loss_type], wt=wt,
+                                              grad_scale=w / accum, want_grad=backward)
+        robust_f32, mse_f32 = stats[0] / n, stats[3] / n
+        rob = robust_f32.to(dt)
+        loss = w * rob
+        loss_dict = {"transformer_mse": mse_f32.to(dt), "_mse_f32": mse_f32, "transformer_robust": rob,
+                     "_robust_f32": robust_f32}
+    elif weighted:
+        # stats[0] is the weighted sum, stats[3] the unweighted one (bitwise mse_fwd_bwd's)
         stats, dout = ops.wmse_fwd_bwd(out, v_target, wt, grad_scale=w / accum, want_grad=backward)
         wmse_f32, mse_f32 = stats[0] / n, stats[3] / n
         wmse, mse = wmse_f32.to(dt), mse_f32.to(dt)
@@ -254,6 +276,101 @@ def token_loss_weights_ref(B, F, H, W, bbox=None, frame_w=None, sample_w=None, u
     safe = torch.where(raw_sum != 0, raw_sum, torch.ones_like(raw_sum))
     wt = torch.where((raw_sum != 0)[:, None], sw[:, None] * raw * N / safe[:, None], torch.zeros_like(raw))
     return wt, raw_sum
+
+
+LOSS_TYPES = ("l2", "huber", "smooth_l1")
+HUBER_SCHEDULES = ("constant", "exponential", "snr")
+
+# What robust_loss_from_config decided, when loss_type is off "l2"
+RobustLoss = collections.namedtuple("RobustLoss", "loss_type huber_c schedule")
+
+
+def robust_loss_from_config(config):
+    """RobustLoss or None from the optional config keys (setattr, or train.<key> in the YAML; not
+    TrainConfig fields). None -- `loss_type` absent or "l2" -- is the reference's squared error, launch for
+    launch:
+      `loss_type` ("l2", the same as absent, "huber" or "smooth_l1"): the pseudo-Huber forms of the velocity
+          loss (ltx_robust_loss_fwd_bwd), quadratic for residuals well below the threshold c and linear well
+          above it; "huber" is 2 c (sqrt(e^2 + c^2) - c), which tends to e^2 as c grows; "smooth_l1" is
+          2 (sqrt(e^2 + c^2) - c), which tends to 2 |e| as c shrinks;
+      `huber_c` (a finite float > 0, absent = 0.1): the threshold at t = 1;
+      `huber_schedule` ("constant", "exponential" or "snr", absent = "snr"): how the threshold follows the
+          step's shifted t (huber_threshold): loose at low noise, tight at high noise.
+    ValueError for an unknown name, a value of the wrong type, huber_c <= 0 or not finite, and for huber_c or
+    huber_schedule set without a loss_type that reads them."""
+    loss_type = getattr(config, "loss_type", None)
+    c = getattr(config, "huber_c", None)
+    schedule = getattr(config, "huber_schedule", None)
+    if loss_type is None:
+        loss_type = "l2"
+    if not isinstance(loss_type, str) or loss_type not in LOSS_TYPES:
+        raise ValueError(f"loss_type {loss_type!r} is not one of {', '.join(LOSS_TYPES)}")
+    if c is not None and (isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0):
+        raise ValueError(f"huber_c must be a finite float > 0, got {c!r}")
+    if schedule is not None and (not isinstance(schedule, str) or schedule not in HUBER_SCHEDULES):
+        raise ValueError(f"huber_schedule {schedule!r} is not one of {', '.join(HUBER_SCHEDULES)}")
+    if loss_type == "l2":
+        for key, val in (("huber_c", c), ("huber_schedule", schedule)):
+            if val is not None:
+                raise ValueError(f"{key} is set but loss_type is 'l2' (or absent): it is read only with "
+                                 f"loss_type huber or smooth_l1")
+        return None
+    return RobustLoss(loss_type, 0.1 if c is None else float(c), "snr" if schedule is None else schedule)
+
+
+_HUBER_CONSTS = {}  # (schedule, huber_c, B, device) -> the schedule's constant device tensor
+
+
+def huber_threshold(t, schedule, huber_c):
+    """The robust loss's threshold per sample, f32 [B], from the step's (shifted) t in [0, 1]: torch ops on
+    t's device, nothing is read back and nothing copied from the host (the constant tensors are filled on
+    the device, once per key). "constant": huber_c; "exponential": huber_c ** t; "snr":
+    (1 - huber_c) (1 - t)^2 + huber_c, i.e. (1 - c) / (1 + sigma)^2 + c at the rectified flow's
+    sigma = t / (1 - t). Both scheduled forms run from 1 at t = 0 to huber_c at t = 1."""
+    huber_c = float(huber_c)
+    if schedule == "snr":
+        u = 1.0 - t
+        return ((1.0 - huber_c) * (u * u) + huber_c).contiguous()
+    if schedule not in ("constant", "exponential"):
+        raise ValueError(f"huber_schedule {schedule!r} is not one of {', '.join(HUBER_SCHEDULES)}")
+    B = t.numel() if schedule == "constant" else 0
+    key = (schedule, huber_c, B, str(t.device))
+    const = _HUBER_CONSTS.get(key)
+    if const is None:
+        # constant: the [B] thresholds themselves; exponential: the 0-dim base of the power
+        const = torch.full((B,) if schedule == "constant" else (), huber_c, dtype=torch.float32, device=t.device)
+        _HUBER_CONSTS[key] = const
+    if schedule == "constant":
+        return const
+    return torch.pow(const, t).contiguous()
+
+
+def robust_loss_ref(out, v, c, kind, wt=None, grad_scale=1.0):
+    """The statement, in float64 on the CPU, of ltx_robust_loss_fwd_bwd (the kernel does the loss term in
+    f32): out, v [B, ..., C] (their values as given: bf16 tensors are widened exactly), c [B], kind 1
+    (huber) or 2 (smooth_l1), wt one weight per row of C, or None for ones. Returns (sums f64 [5], dout f64
+    of out's shape, before the kernel's one bf16 rounding):
+      e = o - v, r = sqrt(e^2 + c_b^2), l = k_b e^2 / (r + c_b), g = k_b e / r, k_b = 2 c_b | 2;
+      sums = (sum wt l, sum v, sum v^2, sum bf16(d d) with d = bf16(o - v), sum l), dout = wt g grad_scale / n."""
+    if kind not in (1, 2):
+        raise ValueError(f"robust_loss_ref: kind must be 1 (huber) or 2 (smooth_l1), got {kind!r}")
+    f64 = torch.float64
+    o64, v64 = out.detach().cpu().to(f64), v.detach().cpu().to(f64)
+    B, C = out.shape[0], out.shape[-1]
+    n = o64.numel()
+    tail = (1,) * (out.dim() - 1)
+    cb = c.detach().cpu().to(f64).reshape(B, *tail)
+    w = torch.ones((), dtype=f64) if wt is None else wt.detach().cpu().to(f64).reshape(*out.shape[:-1], 1)
+    k = 2.0 * cb if kind == 1 else torch.full_like(cb, 2.0)
+    e = o64 - v64
+    r = torch.sqrt(e * e + cb * cb)
+    l = k * (e * e) / (r + cb)
+    g = k * e / r
+    # the shipped loss's squared error: each of the two bf16 ops rounded, as ATen's mse does
+    d = (out.detach().cpu() - v.detach().cpu()).bfloat16()
+    q = (d * d).bfloat16()
+    sums = torch.stack([(w * l).sum(), v64.sum(), (v64 * v64).sum(), q.to(f64).sum(), l.sum()])
+    return sums, w * g * (float(grad_scale) / n)
 
 
 class LRSchedule:
@@ -1699,7 +1816,13 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     for launch): the velocity loss weighted by the clip's face box (the batches' "face_bbox", which a
     LatentPairDataset built with face_bbox_dir carries), the first latent frame and the timestep.
     "train/transformer_wmse" is then logged beside "train/transformer_mse", which stays the unweighted mse,
-    as does "val/loss"."""
+    as does "val/loss".
+
+    `loss_type`, `huber_c`, `huber_schedule` (robust_loss_from_config, read by every train_step; absent or
+    "l2" = today's run, launch for launch): the pseudo-Huber velocity loss with a threshold per sample from
+    its timestep, with or without the weights above. "train/transformer_robust" is then logged beside
+    "train/transformer_mse", which stays the unweighted squared error, as does "val/loss". Nothing about
+    the loss enters a checkpoint: it is a function of the config alone."""
     import os
 
     from . import io
