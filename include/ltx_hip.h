@@ -709,6 +709,33 @@ int ltx_prodigy_d_update_guard(const double* part, int64_t nrows, double* record
                                double beta2, double beta3, double d0, double d_coef, double growth_rate,
                                int use_bias_correction, const void* guard, void* stream);
 
+/* ---- max-norm regularisation of the LoRA adapters (DESIGN.md "Max-norm (scale_weight_norms)";
+ * csrc/max_norm.hip) ------------------------------------------------------------------------------ */
+/* After the optimizer's update, every adapter pair (A f32 [r, K], B f32 [N, r], s) with
+ * norm = |s| ||B A||_F above the cap has A and B multiplied by f = f32(sqrt(cap / norm)). No entry point
+ * reads anything back, none uses atomics, every sum has a fixed order.
+ *
+ * The pair table: 12 int64 per pair { A, B, N, K, r, the bits of the f64 s, the first f64 of the pair's A
+ * partials in ws, of its B partials, the pair's first workgroup, slab, slabs of K, slabs of N }; r one of
+ * 8, 16, 32, 64, 128, A and B dense. ltx_max_norm_plan (host only) gives for one pair out[0 .. 6) = { slab,
+ * slabs of K, slabs of N, workgroups, f64 of the A partials, f64 of the B partials }. */
+int ltx_max_norm_plan(int64_t N, int64_t K, int64_t r, int64_t* out);
+/* sumsq[p] = ||B A||_F^2 = sum_ij (B^T B)_ij (A A^T)_ij of every pair, in f64 and without forming B A: one
+ * launch of nwg workgroups (the sum of the plans') writes the Gram tiles' per-slab partials to ws, a second
+ * of one workgroup per pair adds the slabs in order and contracts the two matrices. */
+int ltx_max_norm_sumsq(const int64_t* table, int64_t npairs, int64_t nwg, double* ws, double* sumsq, void* stream);
+/* Per pair, in f64: norm = |s| sqrt(sumsq), ratio = norm <= cap ? 1 : cap / norm, factor[p] = f32(sqrt(ratio)),
+ * scaled = norm ratio; record (16 bytes) = { i32 pairs with ratio != 1; f32 mean of scaled; f32 max of scaled;
+ * i32 0 }. With a guard record whose applied is 0 every ratio is 1. */
+int ltx_max_norm_finish(const int64_t* table, const double* sumsq, int64_t npairs, double cap,
+                        const void* guard_or_null, float* factor, void* record, void* stream);
+/* The chunk table of the paired tensors, 5 int64 per row { param f32, its f32 EMA shadow or 0, first element,
+ * count <= 2048, pair }, one workgroup per row: a row whose factor[pair] is 1 stores nothing; otherwise
+ * p <- fl32(p f) and, with a shadow, shadow <- fl32(shadow - fl32(one_minus_decay fl32(p_before - p_after))).
+ * With a guard record whose applied is 0 it returns before the first store. */
+int ltx_max_norm_scale_multi(const int64_t* rows, int64_t nrows, const float* factor, float one_minus_decay,
+                             const void* guard_or_null, void* stream);
+
 /* ---- train_mode='full' parameter gradients (csrc/paramgrad.hip) --------- */
 /* Weight gradient of the q/k RMSNorm weights: partials[(which * splits + s) * D + d] (f32) =
  * sum over row split s of bf16(dn * bf16(x_raw * rstd)), dn = RoPE^T of the incoming gradient (the

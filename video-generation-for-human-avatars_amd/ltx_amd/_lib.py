@@ -131,6 +131,10 @@ _SIGNATURES = {
     "ltx_prodigy_moments_multi_guard": [_p, _i64, _i32, _p, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _i32, _p, _p,
                                         _p, _p],
     "ltx_prodigy_d_update_guard": [_p, _i64, _p, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p, _p],
+    "ltx_max_norm_plan": [_i64, _i64, _i64, ctypes.POINTER(_i64)],
+    "ltx_max_norm_sumsq": [_p, _i64, _i64, _p, _p, _p],
+    "ltx_max_norm_finish": [_p, _p, _i64, _f64, _p, _p, _p, _p],
+    "ltx_max_norm_scale_multi": [_p, _i64, _p, _f32, _p, _p],
     "ltx_qk_norm_wgrad": [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _p, _p, _p, _i64,
                           _i64, _i64, _i64, _i32, _i64, _p, _p],
     "ltx_group_colsum": [_p, _i64, _p, _i64, _p, _p, _i32, _i64, _i64, _i64, _i64, _p, _p],

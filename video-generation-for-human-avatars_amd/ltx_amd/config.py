@@ -212,4 +212,9 @@ def load_train_config_from_yaml(yaml_path: str) -> TrainConfig:
     for key in ("loss_type", "huber_c", "huber_schedule"):
         if key in t:
             setattr(config, key, t[key])
+    # and the key training.max_norm_from_config reads (and validates; passed on as written):
+    # `train.scale_weight_norms` (a float > 0; absent, null or 0 = off): kohya's max-norm regularisation, the
+    # cap on every adapter's |s| ||B A||_F, enforced inside the optimizer step
+    if "scale_weight_norms" in t:
+        setattr(config, "scale_weight_norms", t["scale_weight_norms"])
     return config

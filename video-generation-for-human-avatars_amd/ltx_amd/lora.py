@@ -233,6 +233,15 @@ def trainable_parameters(model):
     return [(n, p) for n, p in model.named_parameters() if p.requires_grad]
 
 
+def adapter_pairs(model):
+    """[(module name, lora_A weight [r, K], lora_B weight [N, r], scaling)] of every LoraLinear, DoRA ones
+    included, in module order: the pairs whose update s B A the max-norm pass of the optimizer step bounds
+    (FusedAdamW(scale_weight_norms=..., norm_pairs=...)). The magnitudes of DoRA and the caption projection
+    are not adapters and do not appear."""
+    return [(name, mod.lora_A["default"].weight, mod.lora_B["default"].weight, float(mod.scaling))
+            for name, mod in model.named_modules() if isinstance(mod, LoraLinear)]
+
+
 @torch.no_grad()
 def merged_state_dict(model):
     """peft merge_and_unload(): W + s*B@A (under DoRA (m / norm)[:, None] times it) folded into each

@@ -1048,6 +1048,62 @@ def dora_rowscale_add(out, src, c, alpha=1.0, transpose_out=False):
     return out
 
 
+# the max-norm pass of the optimizer step (csrc/max_norm.hip; DESIGN.md "Max-norm (scale_weight_norms)")
+MAX_NORM_PAIR_FIELDS = 12  # int64 per row of the pair table
+MAX_NORM_ROW_FIELDS = 5    # int64 per row of the scale table
+
+
+def max_norm_plan(N, K, r):
+    """ltx_max_norm_plan (host only) for one pair A [r, K], B [N, r]: (slab, slabs of K, slabs of N, workgroups
+    of the Gram launch, f64 of the A partials, f64 of the B partials)."""
+    out = (ctypes.c_int64 * 6)()
+    call("ltx_max_norm_plan", int(N), int(K), check_lora_rank(r), out)
+    return tuple(out)
+
+
+def max_norm_sumsq(table, npairs, nwg, ws, sumsq):
+    """sumsq[p] = ||B A||_F^2 of every pair of the device pair table (ltx_max_norm_sumsq: the Gram partials
+    into `ws`, then one workgroup per pair), f64, B A never formed."""
+    _need(ws, torch.float64, "max_norm_sumsq ws")
+    _need(sumsq, torch.float64, "max_norm_sumsq sumsq")
+    if table.dtype != torch.int64 or table.numel() != npairs * MAX_NORM_PAIR_FIELDS or sumsq.numel() < npairs:
+        raise ValueError(f"max_norm_sumsq: a table of {npairs} x {MAX_NORM_PAIR_FIELDS} int64 and {npairs} sums "
+                         f"expected, got {tuple(table.shape)} {table.dtype}, {sumsq.numel()}")
+    label = "ltx::gram_partials_kernel + ltx::gram_contract_kernel"
+    timer, ev0 = _timed(label)
+    call("ltx_max_norm_sumsq", _p(table), npairs, nwg, _p(ws), _p(sumsq), _s())
+    if timer is not None:
+        timer.stop(label, 0.0, ev0)
+    return sumsq
+
+
+def max_norm_finish(table, sumsq, npairs, cap, factor, record, guard=None):
+    """factor[p] = f32(sqrt(ratio)) per pair and the 16-byte record {keys_scaled, avg, max, 0}
+    (ltx_max_norm_finish); `guard`: the guard record's pointer or None."""
+    _need(factor, F32, "max_norm_finish factor")
+    if factor.numel() < npairs or record.numel() * record.element_size() < 16:
+        raise ValueError("max_norm_finish: factor holds fewer than npairs values or the record fewer than 16 bytes")
+    label = "ltx::max_norm_finish_kernel"
+    timer, ev0 = _timed(label)
+    call("ltx_max_norm_finish", _p(table), _p(sumsq), npairs, float(cap), guard, _p(factor), _p(record), _s())
+    if timer is not None:
+        timer.stop(label, 0.0, ev0)
+    return factor, record
+
+
+def max_norm_scale_multi(rows, nrows, factor, omd=0.0, guard=None):
+    """p <- p factor[pair] over the device scale table (and the EMA shadow's correction where a row has one);
+    ltx_max_norm_scale_multi."""
+    if rows.dtype != torch.int64 or rows.numel() != nrows * MAX_NORM_ROW_FIELDS:
+        raise ValueError(f"max_norm_scale_multi: a table of {nrows} x {MAX_NORM_ROW_FIELDS} int64 expected, got "
+                         f"{tuple(rows.shape)} {rows.dtype}")
+    label = "ltx::max_norm_scale_multi_kernel"
+    timer, ev0 = _timed(label)
+    call("ltx_max_norm_scale_multi", _p(rows), nrows, _p(factor), float(omd), guard, _s())
+    if timer is not None:
+        timer.stop(label, 0.0, ev0)
+
+
 # ---------------------------------------------------------------------------------------------
 # small ops
 # ---------------------------------------------------------------------------------------------

@@ -543,6 +543,39 @@ def guard_from_config(config):
     return True, (limit or None)
 
 
+def _check_cap(value, what="scale_weight_norms"):
+    """None for None or 0 (off), else the cap as a float; ValueError for a bool, a string or anything else that
+    is not a real number, for a negative and for a non-finite value."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError(f"{what} must be a number > 0 (or absent / 0 for off), got {value!r}")
+    cap = float(value)
+    if not math.isfinite(cap) or cap < 0.0:
+        raise ValueError(f"{what} must be a finite number > 0 (or absent / 0 for off), got {value!r}")
+    return cap or None
+
+
+def max_norm_from_config(config):
+    """The cap of the max-norm pass, or None, from the optional config key `scale_weight_norms` (setattr, or
+    train.scale_weight_norms in the YAML; not a TrainConfig field): kohya's --scale_weight_norms. Absent, None
+    or 0: off, and the run is today's. With a cap c > 0 FusedAdamW / FusedProdigy scale, after every optimizer
+    step and on the device, the A and B of every adapter whose |s| ||B A||_F exceeds c so that it sits on c
+    (DESIGN.md "Max-norm (scale_weight_norms)"). ValueError for a bool, a string, a negative or a non-finite
+    value; NotImplementedError outside train_mode 'lora_audio' or with use_deepspeed (the sharded Zero2AdamW
+    step is its own path)."""
+    cap = _check_cap(getattr(config, "scale_weight_norms", None))
+    if cap is None:
+        return None
+    train_mode = getattr(config, "train_mode", "full")
+    if train_mode != "lora_audio" or getattr(config, "use_deepspeed", False):
+        raise NotImplementedError(f"scale_weight_norms with train_mode={train_mode!r}, use_deepspeed="
+                                  f"{bool(getattr(config, 'use_deepspeed', False))}: the max-norm pass rides the "
+                                  f"step of FusedAdamW and FusedProdigy, which step the lora_audio trainable set; "
+                                  f"the sharded Zero2AdamW path has none")
+    return cap
+
+
 BF16_UPDATES = ("nearest", "stochastic")
 
 
@@ -656,6 +689,63 @@ def table_rows(fields, chunk):
     return chunk_rows([(t[0], t[1:5], t[5:]) for t in fields], chunk)
 
 
+# ---- the two tables of the max-norm pass (csrc/max_norm.hip); not optimizer-step layouts, so not in LAYOUTS
+# The pair table, one row per adapter pair: what the Gram, contraction and finish launches read.
+MAX_NORM_PAIR = ("A", "B", "N", "K", "r", "scaling (f64 bits)", "A partials", "B partials", "first workgroup",
+                 "slab", "slabs of K", "slabs of N")
+# The scale table, chunk_rows over the paired tensors: one row per at most CHUNK elements of A or B.
+MAX_NORM_ROW = ("param", "shadow or 0", "start", "count", "pair")
+
+
+def max_norm_pair_rows(pairs):
+    """(rows of MAX_NORM_PAIR, workgroups of the Gram launch, f64 of the partials' workspace) for `pairs`, a
+    list of (A pointer, B pointer, N, K, r, scaling): every pair's plan from ops.max_norm_plan, its partials
+    behind the previous pair's. Pure host code."""
+    import struct
+    rows, nwg, ws = [], 0, 0
+    for a, b, N, K, r, s in pairs:
+        slab, sa, sb, wgs, fa, fb = ops.max_norm_plan(N, K, r)
+        bits = struct.unpack("<q", struct.pack("<d", float(s)))[0]
+        rows.append((a, b, N, K, r, bits, ws, ws + fa, nwg, slab, sa, sb))
+        nwg += wgs
+        ws += fa + fb
+    return rows, nwg, ws
+
+
+def max_norm_scale_rows(tensors, chunk):
+    """Rows of MAX_NORM_ROW for `tensors`, a list of (numel, parameter pointer, shadow pointer or 0, pair)."""
+    return chunk_rows([(n, (p, shadow), (pair,)) for n, p, shadow, pair in tensors], chunk)
+
+
+def _check_norm_pairs(norm_pairs, params):
+    """[(name, A, B, scaling)] validated against the optimizer's parameters `params`: ValueError when a pair's
+    tensors are not f32 contiguous parameters among them, when the shapes are not A [r, K] / B [N, r] with r one
+    of ops.LORA_RANKS, or when a tensor appears in two pairs."""
+    known, seen, out = {id(p) for p in params}, set(), []
+    for item in norm_pairs:
+        if not isinstance(item, (tuple, list)) or len(item) != 4:
+            raise ValueError("norm_pairs: (module name, A, B, scaling) tuples expected, as lora.adapter_pairs returns")
+        name, A, B, s = item
+        for what, t in (("A", A), ("B", B)):
+            if not isinstance(t, torch.nn.Parameter) or id(t) not in known:
+                raise ValueError(f"norm_pairs: {what} of {name!r} is not a parameter of this optimizer")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"norm_pairs: {what} of {name!r} must be a contiguous f32 tensor, got {t.dtype}, "
+                                 f"strides {t.stride()}")
+            if id(t) in seen:
+                raise ValueError(f"norm_pairs: {what} of {name!r} appears in two pairs")
+            seen.add(id(t))
+        if A.dim() != 2 or B.dim() != 2 or A.shape[0] != B.shape[1] or A.shape[0] not in ops.LORA_RANKS \
+                or A.numel() == 0 or B.numel() == 0:
+            raise ValueError(f"norm_pairs: {name!r}: expected A [r, K] and B [N, r] with r one of "
+                             f"{', '.join(map(str, ops.LORA_RANKS))}, got {tuple(A.shape)} and {tuple(B.shape)}")
+        s = float(s)
+        if not math.isfinite(s):
+            raise ValueError(f"norm_pairs: {name!r}: the scaling must be finite, got {s}")
+        out.append((str(name), A, B, s))
+    return out
+
+
 # One launch of the table step: the bucket's device table and its rows, 0 f32 / 1 bf16 / 2 bf16 with f32
 # state and the stochastic store, the param group, the bucket's step count (None where the kernels take
 # none) and the 6-field table of the norm pass (None when nothing is clipped)
@@ -713,24 +803,52 @@ class FusedAdamW(torch.optim.Optimizer):
     increments. After a guarded step `step_applied` is a 0-dim int32 device tensor (1 or 0), `grad_norm` the
     pre-clip norm also without max_grad_norm, `clip_coef` as above when clipping; `skipped_steps` (a Python
     int, settles first) counts the skipped steps and `consecutive_skips` those since the last applied one.
+    The value enters param_groups only when on.
+
+    `scale_weight_norms` (None or 0: today's step, call for call; a cap c > 0 with `norm_pairs`, the
+    [(module name, A, B, scaling)] of lora.adapter_pairs): kohya's max-norm regularisation. After the update
+    launches of every step -- always the table kernels -- every pair whose norm = |s| ||B A||_F exceeds c has
+    A and B multiplied by f = float32(sqrt(c / norm)), so the update s B A sits on the cap
+    (tests/max_norm_utils.py is the statement). Three entry points over device tables, whatever the number of
+    pairs, and nothing syncs: ltx_max_norm_sumsq (the f64 Gram form of ||B A||_F^2, B A never formed),
+    ltx_max_norm_finish (norm, ratio, f per pair and the record), ltx_max_norm_scale_multi (the stores; pairs
+    at or under the cap store nothing). Moments, Prodigy's s / p0 and DoRA magnitudes are not touched, nor is
+    any tensor outside the pairs. With `ema` a scaled element's shadow takes s <- s - omd (p_before - p_after),
+    three separately rounded f32 operations, so the shadow stays the average of the weights as stored. Under
+    `skip_nonfinite` a skipped step scales nothing. After a step `keys_scaled` (int32: the pairs scaled),
+    `avg_key_norm` and `max_key_norm` (f32: mean and maximum of the norms after scaling) are 0-dim device
+    tensors, views of a fresh record per step. Every decision is a function of the weights alone, in fixed
+    summation orders: data-parallel ranks decide alike without a collective, and nothing enters a checkpoint.
     The value enters param_groups only when on."""
 
     CHUNK = 2048  # elements per block of the multi-tensor kernel
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  multi_tensor=True, max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, scale_weight_norms=None, norm_pairs=None):
         if max_grad_norm is not None and not float(max_grad_norm) >= 0:
             raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
         if ema is not None and not isinstance(ema, EMASchedule):
             raise TypeError(f"ema must be an EMASchedule or None, got {type(ema).__name__}")
         self.bf16_update, self.sr_seed = _check_bf16_update(bf16_update, sr_seed)
+        cap = _check_cap(scale_weight_norms)
+        if cap is not None and not norm_pairs:
+            raise ValueError("scale_weight_norms without norm_pairs: pass lora.adapter_pairs(model)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         if self.bf16_update == "stochastic":
             defaults.update(bf16_update=self.bf16_update, sr_seed=self.sr_seed)
         if skip_nonfinite:
             defaults.update(skip_nonfinite=True)
+        if cap is not None:
+            defaults.update(scale_weight_norms=cap)
         super().__init__(params, defaults)
+        # the max-norm pass: the validated pairs, the last step's record (0-dim device views) and the cached
+        # device tables with their workspace
+        self.norm_pairs = None
+        if cap is not None:
+            self.norm_pairs = _check_norm_pairs(norm_pairs, [p for g in self.param_groups for p in g["params"]])
+        self.keys_scaled = self.avg_key_norm = self.max_key_norm = self.key_factors = None
+        self._max_norm_cache = None
         self.multi_tensor = multi_tensor
         self._tables = []  # pinned host tables of the last two builds (alive until their H2D lands)
         self._table_cache = {}  # (layout, slot) -> (tensor_fields, device table, rows, pinned host table)
@@ -758,6 +876,17 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("skip_nonfinite differs between parameter groups: the decision is global, over every "
                              "gradient of the step")
         return vals.pop() if vals else False
+
+    def _scale_weight_norms(self):
+        """The max-norm cap (0.0: off), one value over the parameter groups: the pairs belong to the optimizer."""
+        vals = {float(g.get("scale_weight_norms") or 0.0) for g in self.param_groups}
+        if len(vals) > 1:
+            raise ValueError(f"scale_weight_norms differs between parameter groups ({sorted(vals)})")
+        cap = vals.pop() if vals else 0.0
+        if cap > 0 and not self.norm_pairs:
+            raise ValueError("scale_weight_norms is set in param_groups, but the optimizer was built without "
+                             "norm_pairs")
+        return cap
 
     def settle(self):
         """Wait for the last guarded step's outcome (an event recorded behind a 16-byte copy into pinned host
@@ -890,15 +1019,21 @@ class FusedAdamW(torch.optim.Optimizer):
         omd = self._ema_tick() if (launches or self._EMPTY_STEP_TICKS) else None
         if not launches:
             self.clip_sumsq = self.grad_norm = self.clip_coef = self.step_applied = None
+            self.keys_scaled = self.avg_key_norm = self.max_key_norm = None
             return
         stream = ops._s()
+        cap = self._scale_weight_norms()
         if not guard:
             self.step_applied = None
             coef = self._clip_pass(launches, max_norm, device, stream)
             self._launch(launches, coef, omd, device, stream)
+            if cap > 0:
+                self._max_norm_pass(cap, omd, device)
         else:
             coef, rec = self._guard_pass(launches, max_norm, device, stream)
             self._launch(launches, coef, omd, device, stream, ops._p(rec))
+            if cap > 0:
+                self._max_norm_pass(cap, omd, device, ops._p(rec))
             self._guard_outcome(rec, touched, ema_before)
         ops.bump_weight_generation()  # in-place kernel updates: invalidate weight-derived caches
 
@@ -910,6 +1045,8 @@ class FusedAdamW(torch.optim.Optimizer):
             return "FusedAdamW(skip_nonfinite)", "guard kernels", "the global norm"
         if self.ema is not None:
             return "FusedAdamW(ema)", "EMA kernels", "the global norm"
+        if self._scale_weight_norms() > 0:
+            return "FusedAdamW(scale_weight_norms)", "max-norm kernels", "the pairs' norms"
         return "FusedAdamW(bf16_update)", "stochastic-rounding kernels", "the global norm"
 
     def _check_params(self, what, kernels, sums=None):
@@ -1049,10 +1186,55 @@ class FusedAdamW(torch.optim.Optimizer):
             else:
                 ops.call("ltx_adamw_multi", ops._p(table), nrows, mode, *hyper, stream)
 
+    def _max_norm_tables(self, device):
+        """(pair table, pairs, Gram workgroups, workspace, factors, scale table, rows) on the device, built once
+        per set of buffers and reused while every pair's A, B and their EMA shadows keep their storage. The
+        workspace holds the Gram partials and, behind them, one f64 sum per pair. The pinned host copies stay
+        alive in the cache entry until the next build, past their non-blocking uploads."""
+        key, pairs, tensors = [], [], []
+        for i, (_, A, B, s) in enumerate(self.norm_pairs):
+            if A.device != device or B.device != device:
+                raise ValueError(f"{type(self).__name__}(scale_weight_norms): pair {i} is on {A.device} / {B.device}, "
+                                 f"the step on {device}")
+            shadows = [(self.state.get(t) or {}).get("ema") for t in (A, B)]
+            ptrs = [0 if sh is None else sh.data_ptr() for sh in shadows]
+            key.append((A.data_ptr(), B.data_ptr(), ptrs[0], ptrs[1]))
+            pairs.append((A.data_ptr(), B.data_ptr(), B.shape[0], A.shape[1], A.shape[0], s))
+            tensors += [(A.numel(), A.data_ptr(), ptrs[0], i), (B.numel(), B.data_ptr(), ptrs[1], i)]
+        hit = self._max_norm_cache
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        pair_rows, nwg, ws_f64 = max_norm_pair_rows(pairs)
+        rows = max_norm_scale_rows(tensors, self.CHUNK)
+        hosts = [torch.tensor(pair_rows, dtype=torch.int64).pin_memory(),
+                 torch.tensor(rows, dtype=torch.int64).pin_memory()]
+        table, scale = (h.to(device, non_blocking=True) for h in hosts)
+        ws = torch.empty(ws_f64 + len(pairs), dtype=torch.float64, device=device)
+        factor = torch.empty(len(pairs), dtype=torch.float32, device=device)
+        out = (table, len(pairs), nwg, ws, factor, scale, len(rows))
+        self._max_norm_cache = (key, out, hosts)
+        return out
+
+    def _max_norm_pass(self, cap, omd, device, guard=None):
+        """The three max-norm entry points behind the update launches: the sums of squares of every pair, the
+        factors and the record (a fresh one per step, so a value somebody holds keeps it), the stores. `omd`:
+        this step's 1 - decay for the shadows' correction (None without an EMA); `guard`: the guard record's
+        pointer, under which a skipped step scales nothing."""
+        table, npairs, nwg, ws, factor, scale, nrows = self._max_norm_tables(device)
+        sumsq = ws[ws.numel() - npairs:]
+        ops.max_norm_sumsq(table, npairs, nwg, ws, sumsq)
+        rec = torch.empty(4, dtype=torch.int32, device=device)
+        ops.max_norm_finish(table, sumsq, npairs, cap, factor, rec, guard)
+        ops.max_norm_scale_multi(scale, nrows, factor, 0.0 if omd is None else omd, guard)
+        self.keys_scaled = rec[0]
+        self.avg_key_norm, self.max_key_norm = rec[1:3].view(torch.float32)
+        self.key_factors = factor  # f per pair, in norm_pairs' order: the pass's own buffer, rewritten every step
+
     def _step_without_tables(self, max_norm):
         """The unclipped, EMA-less, nearest step: ltx_adamw_multi per dtype group of more than one tensor,
         ltx_adamw_step otherwise, CPU parameters included. False when the step needs the table path."""
-        if max_norm > 0 or self.ema is not None or self.bf16_update == "stochastic" or self._skip_nonfinite():
+        if max_norm > 0 or self.ema is not None or self.bf16_update == "stochastic" or self._skip_nonfinite() \
+                or self._scale_weight_norms() > 0:
             return False
         for group in self.param_groups:
             b1, b2 = group["betas"]
@@ -1211,6 +1393,10 @@ class FusedProdigy(FusedAdamW):
     and float(p0) (ltx_prodigy_moments_multi in its mixed mode, ltx_prodigy_apply_multi_sr), and pass 2
     stores the parameter stochastically rounded (stochastic_round_bf16).
 
+    `scale_weight_norms` / `norm_pairs`, as FusedAdamW's: the max-norm pass runs behind pass 2. The scaled
+    weights move without p0 following, so d's numerator sees the scaling as distance travelled (as it would
+    under kohya's loop around prodigyopt); s, p0 and the record are not touched.
+
     `skip_nonfinite`, as FusedAdamW's: pass 1 and the d update run behind the guard record
     (ltx_prodigy_moments_multi_guard, ltx_prodigy_d_update_guard). A skipped step leaves exp_avg, exp_avg_sq,
     s, p0 and the record's d, d_max, d_numerator, d_denom, d_hat, dlr and k, and sets the record's applied to
@@ -1228,7 +1414,7 @@ class FusedProdigy(FusedAdamW):
     def __init__(self, params, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0,
                  decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                  growth_rate=float("inf"), max_grad_norm=None, ema=None, bf16_update="nearest", sr_seed=0,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, scale_weight_norms=None, norm_pairs=None):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas must be in [0, 1), got {betas}")
@@ -1246,7 +1432,8 @@ class FusedProdigy(FusedAdamW):
             raise ValueError(f"growth_rate must be > 0, got {growth_rate}")
         super().__init__(params, lr=lr, betas=(b1, b2), eps=float(eps), weight_decay=float(weight_decay),
                          max_grad_norm=max_grad_norm, ema=ema, bf16_update=bf16_update, sr_seed=sr_seed,
-                         skip_nonfinite=skip_nonfinite)
+                         skip_nonfinite=skip_nonfinite, scale_weight_norms=scale_weight_norms,
+                         norm_pairs=norm_pairs)
         extra = dict(beta3=None if beta3 is None else float(beta3), decouple=bool(decouple),
                      use_bias_correction=bool(use_bias_correction), safeguard_warmup=bool(safeguard_warmup),
                      d0=float(d0), d_coef=float(d_coef), growth_rate=float(growth_rate))
@@ -1373,9 +1560,12 @@ class OptimizerSpec:
     def __init__(self, kind, lr, kwargs):
         self.kind, self.lr, self.kwargs = kind, lr, dict(kwargs)
 
-    def build(self, params, max_grad_norm=None, ema=None, skip_nonfinite=False):
+    def build(self, params, max_grad_norm=None, ema=None, skip_nonfinite=False, scale_weight_norms=None,
+              norm_pairs=None):
         cls = FusedProdigy if self.kind == "prodigy" else FusedAdamW  # the module's names at call time
         kwargs = dict(self.kwargs, skip_nonfinite=True) if skip_nonfinite else self.kwargs
+        if scale_weight_norms:  # absent: today's call
+            kwargs = dict(kwargs, scale_weight_norms=scale_weight_norms, norm_pairs=norm_pairs)
         return cls(params, lr=self.lr, max_grad_norm=max_grad_norm, ema=ema, **kwargs)
 
 
@@ -1701,7 +1891,10 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
     without clipping, all read at that sync point. global_step and the schedule count attempts, skipped
     ones included. `max_consecutive_skips` (None or 0: no limit): FloatingPointError naming the step once
     more steps than that were skipped in a row -- the outcome of a step is known to the host at the log
-    point when there is a log_fn, otherwise when the next step (or the end of the epoch) settles it."""
+    point when there is a log_fn, otherwise when the next step (or the end of the epoch) settles it.
+
+    An optimizer that bounds the adapters (FusedAdamW(scale_weight_norms)) adds "train/keys_scaled",
+    "train/avg_key_norm" and "train/max_key_norm", the step's max-norm record, read at that sync point too."""
     model.train()
     accum = max(1, int(config.gradient_accumulation_steps))
     guarded = hasattr(optimizer, "_skip_nonfinite") and optimizer._skip_nonfinite()
@@ -1750,6 +1943,10 @@ def train_one_epoch(model, dataloader, optimizer, scheduler, patchifier, device,
                     payload["train/prodigy_d"] = float(optimizer.d)  # the device record, at the same sync point
                 if getattr(optimizer, "ema", None) is not None:
                     payload["train/ema_decay"] = optimizer.ema_decay  # a host value: no sync
+                if getattr(optimizer, "keys_scaled", None) is not None:  # the max-norm pass's record
+                    payload["train/keys_scaled"] = int(optimizer.keys_scaled)
+                    payload["train/avg_key_norm"] = float(optimizer.avg_key_norm)
+                    payload["train/max_key_norm"] = float(optimizer.max_key_norm)
                 for k, v in (loss_dict or {}).items():
                     if not k.startswith("_"):
                         payload[f"train/{k}"] = float(v)
@@ -1811,6 +2008,13 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     FloatingPointError instead of skipping forever. With save_adapters train_state.json gains a "guard" block
     with the skipped count, from which a resumed run continues bitwise.
 
+    `scale_weight_norms` (max_norm_from_config; absent, null or 0 = today's run, call for call and file for
+    file): kohya's max-norm regularisation with that cap. The optimizer gets lora.adapter_pairs(model) and
+    scales, inside every step and on the device, the A and B of every adapter whose |s| ||B A||_F exceeds the
+    cap; "train/keys_scaled", "train/avg_key_norm" and "train/max_key_norm" are logged per step. The rule is a
+    function of the weights, so a checkpoint holds nothing new but the value in the optimizer's param_groups,
+    and a resumed run continues bitwise.
+
     `loss_face_weight`, `loss_face_pad`, `loss_frame0_weight`, `loss_timestep_weighting`
     (loss_weights_from_config, read by every train_step; absent or at their defaults = today's run, launch
     for launch): the velocity loss weighted by the clip's face box (the batches' "face_bbox", which a
@@ -1839,6 +2043,7 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
     max_grad_norm, lr_schedule = schedule_from_config(config, dataloader)
     ema = ema_from_config(config)
     skip_nonfinite, max_consecutive_skips = guard_from_config(config)
+    scale_weight_norms = max_norm_from_config(config)
     spec = optimizer_from_config(config)
     if spec.kind == "prodigy" and lr_schedule is not None:
         lr_schedule.base_lr = spec.lr  # learning_rate: null means 1.0 there
@@ -1853,6 +2058,9 @@ def train_loop(model, config, dataloader, prompt_embeds, prompt_attention_mask, 
                                 sampler=config.rf_sampler, shift=config.rf_shift)
     params = [p for p in model.parameters() if p.requires_grad]
     guard_kw = dict(skip_nonfinite=True) if skip_nonfinite else {}  # absent: today's call
+    if scale_weight_norms is not None:
+        from .lora import adapter_pairs
+        guard_kw.update(scale_weight_norms=scale_weight_norms, norm_pairs=adapter_pairs(model))
     optimizer = spec.build(params, max_grad_norm=max_grad_norm, ema=ema, **guard_kw)
     reducer = None
     if dist.is_available() and dist.is_initialized():
